@@ -12,7 +12,7 @@ layer records (233 GB in HBM) one step is ONE fill launch + one traceback launch
 Pairs are independent: ranks share nothing on the data path, the only collective
 is the final all_gather of int32 scores over RCCL (weak scaling).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 ``python bench.py --gpus N`` (N > 1) outside torchrun starts its own N rank
@@ -20,11 +20,17 @@ processes: a child ``python -m torch.distributed.run --nproc-per-node N bench.py
 launched before this process has touched torch or the GPU; the parent relays
 rank 0's JSON line and the child's exit code.
 
-Prints ONE JSON line on rank 0.  At N=1 the line also carries
-`cpu_baseline` (the C oracle on one host core and on all host cores of this box,
-timed BEFORE the GPU is initialised) and `extra.config2` (BASELINE configs[1],
-1024 pairs x len 512, with the default allocation and with a placement-probed
-buffer), both outside the timed region.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms
+up, times the K steps and prints the line; nothing else.  With ``--full`` the
+N=1 line also carries `cpu_baseline` (the C oracle on one host core and on all
+host cores the run may use, timed BEFORE the GPU is initialised; the GPU's scores of
+the same pairs are compared with the oracle's in `checked`) and `extra.config2`
+(BASELINE configs[1], 1024 pairs x len 512, with the default allocation and with
+a placement-probed buffer), both outside the timed region.
+
+``--dump-outputs DIR`` writes, after the timed steps, what the last timed step
+computed as float arrays (see `dump_outputs`): the gathered scores and rank 0's
+traces.  Inputs are seeded, so the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -36,6 +42,7 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 
 HBM_PEAK_GBPS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (spec)
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files together
 
 
 def _oracle_pair(job):
@@ -94,6 +101,32 @@ def run_steps(batch, count, gather, npairs_total):
     return acc
 
 
+def dump_outputs(outdir, scores, traces, complete):
+    """What a caller of the timed path receives, from its last step, as .npy files (float64 / float32, exact):
+    `scores` (the gathered int32 scores, every pair), and per traced pair `trace_codes` (column codes start->end,
+    one row per pair, padded with -1), `trace_lengths`, `trace_complete` (1 / 0) and `trace_pairs` (the pair's index).
+    Traces of all pairs unless they would exceed DUMP_LIMIT_BYTES; then a fixed seeded sample of pairs."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    scores = np.asarray(scores, dtype=np.float64)
+    lengths = np.array([len(t) for t in traces], dtype=np.int64)
+    width = max(1, int(lengths.max())) if len(traces) else 1
+    row_bytes = 4 * width + 8 + 4 + 8
+    keep = max(0, (DUMP_LIMIT_BYTES - scores.nbytes) // row_bytes)
+    pairs = np.arange(len(traces))
+    if keep < len(traces):
+        pairs = np.sort(np.random.default_rng(0).choice(len(traces), size=keep, replace=False))
+    codes = np.full((len(pairs), width), -1.0, dtype=np.float32)
+    for row, p in enumerate(pairs):
+        codes[row, :lengths[p]] = traces[p]
+    out = {"scores": scores, "trace_codes": codes, "trace_lengths": lengths[pairs].astype(np.float64),
+           "trace_complete": np.asarray(complete, dtype=np.float32)[pairs], "trace_pairs": pairs.astype(np.float64)}
+    for name, arr in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), arr)
+    return {"dir": outdir, "files": sorted(out), "traced_pairs": int(len(pairs)),
+            "bytes": int(sum(a.nbytes for a in out.values()))}
+
+
 VALU_CYCLES = 4  # SIMD cycles one wave64 VALU instruction of this sweep occupies: SQ_ACTIVE_INST_VALU / SQ_INSTS_VALU is
 # exactly one quad-cycle in every pass kept under profiles/, and the sweep's time follows its instruction count, not its
 # occupancy (2 or 3 waves per SIMD) nor its bytes (DESIGN.md section 5; tools/valu_rate.hip has the per-instruction rates)
@@ -144,11 +177,12 @@ def self_launch(args, argv):
     line = None
     for out in proc.stdout:  # the ranks' stderr passes through; of stdout only the JSON line is ours
         try:
-            if "metric" in json.loads(out):
-                line = out.strip()
-                continue
+            obj = json.loads(out)
         except ValueError:
-            pass
+            obj = None
+        if isinstance(obj, dict) and "metric" in obj:  # gloo's interleaved notes can leave a bare number on a line
+            line = out.strip()
+            continue
         sys.stderr.write(out)
     rc = proc.wait()
     if line:
@@ -173,6 +207,10 @@ class DryBatch:
     def scores(self):
         return self._scores
 
+    def traces(self):
+        import numpy as np
+        return [np.zeros(0, dtype=np.uint8) for _ in self._scores], np.ones(len(self._scores), dtype=bool)
+
     def timing(self):
         return {"fill_ms": 1.0, "traceback_ms": 0.0, "fill_launches": 1, "waves_per_pair": 0, "packed_records": 0}
 
@@ -188,12 +226,21 @@ def main():
     ap.add_argument("--pairs", type=int, default=1024, help="pairs per GPU")
     ap.add_argument("--len", type=int, default=1024, dest="length")
     ap.add_argument("--max_shift", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the untimed config-2 block")
+    ap.add_argument("--full", action="store_true",
+                    help="also the untimed extras at N=1: cpu_baseline (with the oracle check of the GPU's scores) "
+                         "and the config-2 block")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the untimed config-2 block")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy")
     ap.add_argument("--reserve-tries", type=int, default=1,
                     help="headline batch: candidate placements of the layer buffer probed in setup (Engine.reserve); "
                          "needs twice the buffer in free HBM, i.e. not possible at the default workload")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    with_cpu_baseline = args.full and not args.no_cpu_baseline
+    with_extra = args.full and not args.no_extra
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args, sys.argv[1:])  # does not return
@@ -209,7 +256,7 @@ def main():
     dry = os.environ.get("BIALIGN_BENCH_REHEARSE") == "dry"
 
     cpu = None
-    if world == 1 and not args.no_cpu_baseline and not dry:  # host cores only, before the GPU is initialised
+    if world == 1 and with_cpu_baseline and not dry:  # host cores only, before the GPU is initialised
         cpu = cpu_baseline(args.length, args.max_shift, 1000, args.pairs)
 
     import numpy as np
@@ -279,9 +326,13 @@ def main():
         total_cells, total_pairs = info["cells"], info["npairs"]
     timing = batch.timing()
     # ---- outside the timed region: what was timed is checked.  Every rank's gathered score vector must hold its own
-    # scores in its block (the gather's layout); rank 0's first pairs are the ones the CPU oracle solved for
-    # `cpu_baseline` -- the GPU's scores of the same pairs must equal them.
+    # scores in its block (the gather's layout); with --full, rank 0's first pairs are the ones the CPU oracle solved
+    # for `cpu_baseline` -- the GPU's scores of the same pairs must equal them.
     gathered = gather_scores(batch.scores(), args.pairs * world)
+    dumped = None
+    if args.dump_outputs and rank == 0:  # the last timed step's results, as a caller of the timed path gets them
+        traces, complete = batch.traces()
+        dumped = dump_outputs(args.dump_outputs, gathered, traces, complete)
     own_ok = bool(np.array_equal(gathered[rank * args.pairs:(rank + 1) * args.pairs], batch.scores()))
     checked = {"gather_layout_ok": own_ok, "gathered_pairs": int(len(gathered))}
     if dry:
@@ -325,10 +376,12 @@ def main():
             "roofline": None if dry else roofline(info, fill_ms, launches, f"protein_{args.pairs}x{args.length}_s{args.max_shift}"),
             "checked": checked,
         }
-        if not args.no_cpu_baseline:
+        if with_cpu_baseline:
             line["cpu_baseline"] = cpu  # measured at N=1 only (None otherwise)
+        if dumped is not None:
+            line["outputs"] = dumped
 
-    if rank == 0 and world == 1 and not args.no_extra and not rehearse:
+    if rank == 0 and world == 1 and with_extra and not rehearse:
         from bialign_amd.batch import make_batch
         # ---- untimed extra: BASELINE configs[1] (1024 pairs x len 512), first on the buffer the engine
         # already holds (default allocation), then on a placement-probed one (profiles/r01e_placement)

@@ -59,3 +59,20 @@ def test_wrong_world_size_is_refused():
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2"] + ARGS, env=env, capture_output=True, text=True,
                        timeout=120, cwd=REPO)
     assert r.returncode != 0 and "WORLD_SIZE=1" in r.stderr
+
+
+def test_dump_outputs_plumbing_dry(tmp_path):
+    """--dump-outputs DIR: rank 0 writes the gathered scores (here the global pair indices) and its traces as float
+    .npy files after the timed steps; the line names them."""
+    import numpy as np
+    for n, sub in ((1, "one"), (2, "two")):
+        out = tmp_path / sub
+        line = _run([sys.executable, "bench.py", "--gpus", str(n)] + ARGS + ["--dump-outputs", str(out)],
+                    self_launched=n > 1)
+        _check(line, n)
+        assert line["outputs"]["files"] == ["scores", "trace_codes", "trace_complete", "trace_lengths", "trace_pairs"]
+        scores = np.load(out / "scores.npy")
+        assert scores.dtype == np.float64
+        np.testing.assert_array_equal(scores, np.arange(3 * n))
+        np.testing.assert_array_equal(np.load(out / "trace_pairs.npy"), np.arange(3))
+        assert np.load(out / "trace_codes.npy").dtype == np.float32

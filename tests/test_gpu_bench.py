@@ -1,11 +1,13 @@
 """bench.py end to end on the GPU box: the self-launched two-rank flow with real kernels (ranks share
 the one GPU, gloo collectives: BIALIGN_BENCH_REHEARSE=1) and the N=1 line's `checked` block (GPU
-scores of the cpu_baseline pairs against the oracle's).  Small shapes: script tests, not numbers."""
+scores of the cpu_baseline pairs against the oracle's, a --full run) and --dump-outputs.  Small shapes: script
+tests, not numbers."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -31,9 +33,36 @@ def test_plain_two_rank_invocation_with_kernels():
 
 
 def test_single_gpu_line_is_checked_against_the_oracle():
-    line = _bench(["--pairs", "6", "--len", "150", "--steps", "2", "--warmup", "1", "--no-extra"])
+    line = _bench(["--pairs", "6", "--len", "150", "--steps", "2", "--warmup", "1", "--full", "--no-extra"])
     c = line["checked"]
     assert c["scores_equal"] and c["pairs"] >= 3 and c["oracle_scores"] == c["gpu_scores"] and c["gather_layout_ok"]
     assert line["cpu_baseline"]["kind"] == "port" and "_scores" not in line["cpu_baseline"]
     r = line["roofline"]
     assert r["bound"] == "hbm" and r["frac"] == pytest.approx(r["achieved"] / r["peak"])
+
+
+def test_dump_outputs_are_the_last_steps_results(tmp_path):
+    """A plain run (no cpu_baseline, no extras) with --dump-outputs, twice: the same float arrays both times, and
+    they are the oracle's scores and traces of the seeded pairs."""
+    from bialign_amd import synth
+    from oracle import oracle
+    args = ["--pairs", "4", "--len", "90", "--steps", "3", "--warmup", "1", "--dump-outputs"]
+    lines = [_bench(args + [str(tmp_path / d)]) for d in ("a", "b")]
+    for line in lines:
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        assert "cpu_baseline" not in line and "extra" not in line
+        assert line["outputs"]["traced_pairs"] == 4 and line["outputs"]["bytes"] <= 64 << 20
+    names = ["scores", "trace_codes", "trace_complete", "trace_lengths", "trace_pairs"]
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in names}
+    for n in names:
+        assert got[n].dtype in (np.float32, np.float64)
+        np.testing.assert_array_equal(got[n], np.load(tmp_path / "b" / f"{n}.npy"))
+    np.testing.assert_array_equal(got["trace_pairs"], np.arange(4))
+    params = dict(synth.PROTEIN_PARAMS)
+    for p in range(4):
+        ref = oracle.solve(*synth.protein_pair(1000 + p, 90), params)
+        assert got["scores"][p] == ref["score"]
+        ln = int(got["trace_lengths"][p])
+        np.testing.assert_array_equal(got["trace_codes"][p, :ln], np.asarray(ref["trace"], dtype=np.float32))
+        assert (got["trace_codes"][p, ln:] == -1).all()
+        assert bool(got["trace_complete"][p]) == ref["complete"]
