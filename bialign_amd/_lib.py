@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # override: A/B builds of the engine (tools/exp_build.sh); a timing-experiment build is refused unless asked for by number
 LIB_PATH = os.environ.get("BIALIGN_LIB_OVERRIDE") or os.path.join(HERE, "libbialign_hip.so")
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 RUN_FILL_ONLY = 1
 RUN_ASYNC = 2
 REC_AUTO, REC_AFFINE, REC_LINEAR = 0, 1, 2
@@ -42,7 +42,8 @@ class Scoring(ctypes.Structure):
 class Pairs(ctypes.Structure):
     _fields_ = [("npairs", ctypes.c_int32), ("len_a", c_i32p), ("len_b", c_i32p),
                 ("off_a", c_i64p), ("off_b", c_i64p), ("seq_a", c_u8p), ("cls_a", c_u8p),
-                ("seq_b", c_u8p), ("cls_b", c_u8p), ("mu2_dense", c_i32p), ("mu2_off", c_i64p)]
+                ("seq_b", c_u8p), ("cls_b", c_u8p), ("mu2_dense", c_i32p), ("mu2_off", c_i64p),
+                ("mu1_dense", c_i32p), ("mu1_off", c_i64p)]
 
 
 class BatchInfo(ctypes.Structure):

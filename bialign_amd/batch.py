@@ -75,13 +75,14 @@ def encode_pairs(pairs, params):
 
 
 def make_batch(pairs, params, engine=None, hbm_budget_bytes=0, recurrence=0, mu2_dense=None,
-               score_only=False, lean_trace=False):
+               score_only=False, lean_trace=False, mu1_dense=None):
+    """``mu1_dense`` / ``mu2_dense``: optional lists of one (len A, len B) int table per pair (engine.Batch)."""
     from .engine import Batch, default_engine  # loads the HIP library (no CPU fallback)
     model, fb = encode_flat(pairs, params)
     return Batch(engine or default_engine(), fb, None, model.s1, model.s2,
                  params["gap_opening_cost"], params["gap_cost"], params["shift_cost"],
                  params["max_shift"], hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence,
-                 mu2_dense=mu2_dense, score_only=score_only, lean_trace=lean_trace)
+                 mu2_dense=mu2_dense, score_only=score_only, lean_trace=lean_trace, mu1_dense=mu1_dense)
 
 
 def shard(npairs, rank, world_size, costs=None):

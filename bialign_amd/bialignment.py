@@ -132,7 +132,7 @@ class BiAligner:
         "full": range(nl),
     }  # data table of pyx:168-177
 
-    def __init__(self, seqA, seqB, strA, strB, **params):
+    def __init__(self, seqA, seqB, strA, strB, seq_similarity=None, **params):
         self._params = params
         # bppA / bppB: optional externally computed base-pair probabilities (see _preprocess_seq)
         bpp_a, bpp_b = params.get("bppA"), params.get("bppB")
@@ -142,6 +142,9 @@ class BiAligner:
         self.beta = self._params["gap_opening_cost"]
         self.max_shift = self._params["max_shift"]
         self._simmatrix = read_simmatrix(self._params["simmatrix"]) if self._params["simmatrix"] else None
+        # seq_similarity: position-specific sequence scores, an (n, m) integer table in the scale of a --simmatrix
+        # table after its x100: mu1(i, j) = table[i-1, j-1] here and on the GPU (dense mu1, include/bialign.h)
+        self._seq_table = None if seq_similarity is None else self._check_seq_table(seq_similarity)
         self._M = None          # DP layers (fetched lazily from HBM)
         self._batch = None      # engine batch holding this pair
         self._score = None
@@ -247,8 +250,21 @@ class BiAligner:
             mol["unp"] = [1.0 - u - d for u, d in zip(mol["up"], mol["down"])]
         return mol
 
+    def _check_seq_table(self, table):
+        t = np.asarray(table)
+        n, m = self.molA["len"], self.molB["len"]
+        if t.shape != (n, m):
+            raise ValueError(f"seq_similarity must have shape (len A, len B) = ({n}, {m}), got {t.shape}")
+        if not np.issubdtype(t.dtype, np.integer):
+            raise ValueError("seq_similarity must hold integers (scores already scaled, e.g. x100)")
+        if t.size and (t.min() < -(1 << 31) or t.max() >= 1 << 31):
+            raise ValueError("seq_similarity entries must fit int32")
+        return np.ascontiguousarray(t, dtype=np.int32)
+
     # ------------------------------------------------------------ score inputs
     def _sequence_similarity(self, i, j):
+        if self._seq_table is not None:
+            return int(self._seq_table[i - 1, j - 1])
         a, b = self.molA["seq"][i - 1], self.molB["seq"][j - 1]
         if self._simmatrix:
             return self._simmatrix[a][b]
@@ -329,7 +345,8 @@ class BiAligner:
                             [(model.encode_sequence(A["seq"]), cls_a)],
                             [(model.encode_sequence(B["seq"]), cls_b)],
                             model.s1, model.s2, self.beta, self.gamma, self._params["shift_cost"],
-                            self.max_shift, recurrence=recurrence, mu2_dense=dense)
+                            self.max_shift, recurrence=recurrence, mu2_dense=dense,
+                            mu1_dense=None if self._seq_table is None else [self._seq_table])
         self._batch.run()
         self._ran_affine = self._batch.affine
         self._score = np.int64(self._batch.scores()[0])

@@ -53,9 +53,10 @@ TeamShape team_shape(const bialign_batch* b, int first, int count, int xcu_resid
   // SIMD up to s=2 (s=2: eight waves only in the diet layout), one at s=3, and needs the whole SIMD beyond
   int tw = std::min(fit, !b->affine ? 8 : (b->S <= 1 ? 8 : (b->S == 2 ? (diet8 ? 8 : 4) : (b->S == 3 ? 4 : 1))));
   while (tw > 1 && lds_of(tw) > 160 * 1024) tw >>= 1;
-  if (b->dense) tw = std::min(tw, b->affine ? 4 : 2);  // dense-mu2 kernels: up to 4 waves (affine), 2 (one layer) per workgroup
+  const bool any_dense = b->dense || b->dense1;
+  if (any_dense) tw = std::min(tw, b->affine ? 4 : 2);  // dense kernels: up to 4 waves (affine), 2 (one layer) per workgroup
   // cross-CU teams (affine LOOKUP kernels only) take any size: the team is a runtime value there
-  int gw = ((!b->affine || b->S <= 3 || !b->dense) && xcu_resident > 0) ? fit_exact : 1;  // (dense affine kernels: s <= 3)
+  int gw = ((!b->affine || b->S <= 3 || !any_dense) && xcu_resident > 0) ? fit_exact : 1;  // (dense affine kernels: s <= 3)
   gw = std::max(1, std::min(gw, xcu_resident / std::max(count, 1)));
   // ... and, for the s=2 sweep, teams of eight-wave workgroups (one per CU, two waves per SIMD)
   int gw8 = (diet8 && xcu8_resident > 0) ? std::min(fit_exact / 8, xcu8_resident / std::max(count, 1)) : 0;
@@ -178,7 +179,7 @@ TeamShape team_shape(const bialign_batch* b, int first, int count, int xcu_resid
     const int g = std::min(gw, std::max(1, 2048 / count));
     // (s=1 affine, the in-workgroup shape leaving a third of the wave slots empty: 1.2 x is enough -- 300 pairs x len 1024 as
     //  teams of 4 in one workgroup 23.3 ms, as eight-wave workgroups in two rounds 25.2, as cross-CU teams of 5 19.9)
-    const bool sparse_s1 = b->affine && b->S == 1 && !b->dense && running * 100 < 2048 * 65;
+    const bool sparse_s1 = b->affine && b->S == 1 && !any_dense && running * 100 < 2048 * 65;
     if (g >= 2 && ((int64_t)count * g * 10 >= running * (sparse_s1 ? 12 : 14) || (t == 8 && g >= 8 && count * 8 <= b->eng->num_cu))) {
       ts.tw = 1;
       ts.gw = g;
@@ -257,16 +258,19 @@ PackInfo pack_info_of() {
 PackInfo pack_info(int S) { return S == 1 ? pack_info_of<1>() : (S == 2 ? pack_info_of<2>() : pack_info_of<3>()); }
 
 // diet: the eight-wave form of the s=2 affine kernel (fill_affine_kernel, DIET): half-length ghost blocks,
-// molecule A's codes not staged
-size_t lds_need(int S, int NL, int team, int k1, int k2, int n, int m, bool dense = false, bool diet = false) {
+// molecule A's codes not staged.  dense1: a dense-mu1 ring per wave, no sequence codes staged.
+size_t lds_need(int S, int NL, int team, int k1, int k2, int n, int m, bool dense = false, bool diet = false,
+                bool dense1 = false) {
   const int W = 2 * S + 1, PADB = S + 1;
   const size_t nv = (NL == 9 ? 12 : 1) * W;
   const size_t npad = diet ? 0 : (n + 3) & ~3, mpad = (m + 2 * PADB + 3) & ~3;
+  const size_t codes = dense1 ? npad + mpad : 2 * npad + 2 * mpad;  // (class codes only)
   const int nd = NL * W, np = nd / 4 + (nd % 4 ? 1 : 0), blk = diet ? 2 : ghost_blk(S);
   const size_t ring_dw = 2 * (((size_t)blk * W * np + 63) / 64 * 64) * 4;  // GhostFeed<S,NL>::RING_DW
   const size_t shared_dw = 16 + (size_t)k1 * k1 + (size_t)k2 * k2;  // progress words + score tables
   const size_t mu2_ring_dw = dense ? 2 * (size_t)blk * 64 : 0;  // Mu2Feed<S>::RING_DW
-  return (team * (ring_dw + nv * NCOL + mu2_ring_dw) + shared_dw) * 4 + 2 * npad + 2 * mpad;
+  const size_t mu1_ring_dw = dense1 ? 2 * (size_t)blk * 64 : 0;  // Mu1Feed<S>::RING_DW
+  return (team * (ring_dw + nv * NCOL + mu2_ring_dw + mu1_ring_dw) + shared_dw) * 4 + codes;
 }
 
 // fill_affine_slim_kernel (bialign_fill_slim.hpp), a workgroup of twelve waves: twelve ghost rings, a block of sentinels,
@@ -524,6 +528,7 @@ int bialign_batch_create(bialign_engine* eng, const bialign_params* prm, const b
   b->k1 = sc->k1;
   b->k2 = sc->k2;
   b->dense = pr->mu2_dense != nullptr;
+  b->dense1 = pr->mu1_dense != nullptr;
   b->lean_trace = (prm->flags & BIALIGN_BATCH_LEAN_TRACE) != 0;
   b->lean = b->lean_trace || (prm->flags & BIALIGN_BATCH_SCORE_ONLY) != 0;
   b->wide = prm->max_shift > BIALIGN_MAX_SHIFT_TILED;  // bialign_wide.hpp: anti-diagonal path, all layers in HBM
@@ -534,6 +539,9 @@ int bialign_batch_create(bialign_engine* eng, const bialign_params* prm, const b
                 BIALIGN_MAX_SHIFT_TILED);
   if (b->dense && !pr->mu2_off) return fail(BIALIGN_E_INVALID, "mu2_dense given without mu2_off");
   if (!b->dense && (!pr->cls_a || !pr->cls_b)) return fail(BIALIGN_E_INVALID, "cls_a / cls_b are NULL (LOOKUP form)");
+  if (b->dense1 && !pr->mu1_off) return fail(BIALIGN_E_INVALID, "mu1_dense given without mu1_off");
+  if (!b->dense1 && (!pr->seq_a || !pr->seq_b)) return fail(BIALIGN_E_INVALID, "seq_a / seq_b are NULL (LOOKUP form)");
+  if (!pr->len_a || !pr->len_b || !pr->off_a || !pr->off_b) return fail(BIALIGN_E_INVALID, "len_a / len_b / off_a / off_b are NULL");
   const int S = b->S, W = 2 * S + 1;
 
   // int32 safety window: finite scores and the drift of "-infinity" cells must
@@ -542,18 +550,20 @@ int bialign_batch_create(bialign_engine* eng, const bialign_params* prm, const b
   for (int t = 0; t < sc->k1 * sc->k1; ++t) amax = std::max<int64_t>(amax, std::llabs((long long)sc->s1[t]));
   int64_t bmax = 0;
   for (int t = 0; t < sc->k2 * sc->k2; ++t) bmax = std::max<int64_t>(bmax, std::llabs((long long)sc->s2[t]));
-  if (b->dense) {  // dense mu2: the bound comes from the tables themselves
-    bmax = 0;
+  auto dense_max = [&](const int32_t* tab, const int64_t* off) {
+    int64_t mx = 0;
     for (int p = 0; p < pr->npairs; ++p) {
       const int64_t cnt = (int64_t)std::max(pr->len_a[p], 0) * std::max(pr->len_b[p], 0);
-      for (int64_t t = 0; t < cnt; ++t)
-        bmax = std::max<int64_t>(bmax, std::llabs((long long)pr->mu2_dense[pr->mu2_off[p] + t]));
+      for (int64_t t = 0; t < cnt; ++t) mx = std::max<int64_t>(mx, std::llabs((long long)tab[off[p] + t]));
     }
-  }
+    return mx;
+  };
+  if (b->dense) bmax = dense_max(pr->mu2_dense, pr->mu2_off);   // dense mu2: the bound comes from the tables themselves
+  if (b->dense1) amax = dense_max(pr->mu1_dense, pr->mu1_off);  // ... and so for dense mu1
   const int64_t colmax = amax + bmax + 2 * (std::llabs((long long)prm->gap_cost) + std::llabs((long long)prm->gap_opening_cost)) +
                          2 * std::llabs((long long)prm->shift_cost);
 
-  int64_t tot_a = 0, tot_b = 0, tot_mu2 = 0;
+  int64_t tot_a = 0, tot_b = 0, tot_tab = 0;
   b->pairs.resize(pr->npairs);
   std::vector<int64_t> pair_dwords(pr->npairs);
   for (int p = 0; p < pr->npairs; ++p) {
@@ -572,23 +582,24 @@ int bialign_batch_create(bialign_engine* eng, const bialign_params* prm, const b
     d.seq_a = pr->off_a[p];
     d.seq_b = pr->off_b[p];
     d.trace_off = b->trace_bytes;
-    d.mu2_off = b->dense ? pr->mu2_off[p] : 0;
-    if (b->dense) tot_mu2 = std::max<int64_t>(tot_mu2, pr->mu2_off[p] + (int64_t)n * m);
+    d.tab_off = tot_tab;  // dense forms: the pair's tables, end to end (mu2's, then mu1's)
+    tot_tab += (int64_t)n * m * ((b->dense ? 1 : 0) + (b->dense1 ? 1 : 0));
     b->trace_bytes += d.trace_cap;
     b->cells += cells_of(n, m, S);
     tot_a = std::max<int64_t>(tot_a, pr->off_a[p] + n);
     tot_b = std::max<int64_t>(tot_b, pr->off_b[p] + m);
     if (!b->wide) {
-      b->lds_bytes = std::max(b->lds_bytes, lds_need(S, b->NL, 1, sc->k1, sc->k2, n, m, b->dense));
-      b->lds_base = std::max(b->lds_base, lds_need(S, b->NL, 0, sc->k1, sc->k2, n, m, b->dense));
+      b->lds_bytes = std::max(b->lds_bytes, lds_need(S, b->NL, 1, sc->k1, sc->k2, n, m, b->dense, false, b->dense1));
+      b->lds_base = std::max(b->lds_base, lds_need(S, b->NL, 0, sc->k1, sc->k2, n, m, b->dense, false, b->dense1));
       b->lds_diet8 = std::max(b->lds_diet8, lds_need(S, b->NL, 8, sc->k1, sc->k2, n, m, false, true));
       b->lds_slim_codes = std::max(b->lds_slim_codes, lds_need_slim_codes(S, n, m));
     }
     b->lds_trace = std::max<size_t>(b->lds_trace, ((size_t)sc->k1 * sc->k1 + (size_t)sc->k2 * sc->k2) * 4 +
-                                                      2 * (size_t)((n + 3) & ~3) + 2 * (size_t)((m + 3) & ~3));
+                                                      (b->dense1 ? 1 : 2) * ((size_t)((n + 3) & ~3) + (size_t)((m + 3) & ~3)));
   }
   if (!b->wide)
-    b->lds_per_wave = lds_need(S, b->NL, 1, sc->k1, sc->k2, 1, 1, b->dense) - lds_need(S, b->NL, 0, sc->k1, sc->k2, 1, 1, b->dense);
+    b->lds_per_wave = lds_need(S, b->NL, 1, sc->k1, sc->k2, 1, 1, b->dense, false, b->dense1) -
+                      lds_need(S, b->NL, 0, sc->k1, sc->k2, 1, 1, b->dense, false, b->dense1);
   if (!b->wide) b->lds_slim_base = lds_need_slim_base(S, sc->k1, sc->k2);
   if (std::max(b->lds_bytes, b->lds_trace) > 160 * 1024)
     return fail(BIALIGN_E_UNSUPPORTED, "molecules too long for the LDS staging (%zu bytes needed, 160 KiB per workgroup)",
@@ -599,7 +610,8 @@ int bialign_batch_create(bialign_engine* eng, const bialign_params* prm, const b
     const char* e = getenv("BIALIGN_PACK");  // "0" never, "1" wherever the layout allows (tests), unset: when it pays
     const bool force = e && e[0] == '1';
     const PackInfo pki = pack_info(S);
-    bool ok = b->affine && S >= 1 && S <= BIALIGN_MAX_SHIFT_PACKED && !b->lean && prm->gap_opening_cost <= 0 && !(e && e[0] == '0') &&
+    bool ok = b->affine && S >= 1 && S <= BIALIGN_MAX_SHIFT_PACKED && !b->lean && !b->dense1 && prm->gap_opening_cost <= 0 &&
+              !(e && e[0] == '0') &&
               (force || colmax < 8192) &&  // offsets span a few column scores (measured: up to 2.5): beyond this they will not fit
               // s=3 runs one wave per SIMD and is bound by issue: packing pays where the device is full (512 pairs x len 512
               // +7 %, 86 pairs in cross-CU teams of 11 +25 %), not for a few long pairs (21 x len 1024: -14 %, 8 x len 2048: -15 %)
@@ -717,13 +729,23 @@ int bialign_batch_create(bialign_engine* eng, const bialign_params* prm, const b
   HIP_TRY(b->d_order.upload(b->order.data(), b->order.size(), st));
   HIP_TRY(b->d_s1.upload(sc->s1, (size_t)sc->k1 * sc->k1, st));
   HIP_TRY(b->d_s2.upload(sc->s2, (size_t)sc->k2 * sc->k2, st));
-  HIP_TRY(b->d_seq_a.upload(pr->seq_a, tot_a, st));
   std::vector<uint8_t> zeros;
-  if (b->dense) zeros.assign((size_t)std::max(tot_a, tot_b), 0);  // class codes are unused in dense mode
+  if (b->dense || b->dense1) zeros.assign((size_t)std::max(tot_a, tot_b), 0);  // codes a dense form replaces are unused
+  HIP_TRY(b->d_seq_a.upload(b->dense1 ? zeros.data() : pr->seq_a, tot_a, st));
   HIP_TRY(b->d_cls_a.upload(b->dense ? zeros.data() : pr->cls_a, tot_a, st));
-  HIP_TRY(b->d_seq_b.upload(pr->seq_b, tot_b, st));
+  HIP_TRY(b->d_seq_b.upload(b->dense1 ? zeros.data() : pr->seq_b, tot_b, st));
   HIP_TRY(b->d_cls_b.upload(b->dense ? zeros.data() : pr->cls_b, tot_b, st));
-  if (b->dense) HIP_TRY(b->d_mu2.upload(pr->mu2_dense, (size_t)tot_mu2, st));
+  std::vector<int32_t> tabs;
+  if (b->dense || b->dense1) {  // the pairs' tables end to end (PairDesc::tab_off): mu2's, then mu1's
+    tabs.resize((size_t)tot_tab);
+    for (int p = 0; p < pr->npairs; ++p) {
+      const size_t nm = (size_t)pr->len_a[p] * pr->len_b[p];
+      int32_t* dst = tabs.data() + b->pairs[p].tab_off;
+      if (b->dense) std::memcpy(dst, pr->mu2_dense + pr->mu2_off[p], nm * sizeof(int32_t)), dst += nm;
+      if (b->dense1) std::memcpy(dst, pr->mu1_dense + pr->mu1_off[p], nm * sizeof(int32_t));
+    }
+    HIP_TRY(b->d_tab.upload(tabs.data(), tabs.size(), st));
+  }
   if (getenv("BIALIGN_DEBUG")) {  // placement study: address and plain streaming-write rate of the layer buffer
     float ms = 0;
     for (int rep = 0; rep < 2; ++rep) {

@@ -214,4 +214,39 @@ struct Mu2Feed {
   }
 };
 
+// ---------------------------------------------------------------------------
+// Dense-mu1 feed (position-specific sequence scores: a PSSM, embedding-derived or
+// masked substitution scores).  A lane needs ONE value per step, mu1(i, j) of its row
+// and the column it works on; the values of a block of steps come by LDS-DMA one block
+// ahead, issued right after the ghost and dense-mu2 DMAs and retired by the same wait.
+// The row follows the strip change (j wraps at P), like the sweep's set_row.  Lattice
+// points outside 1..n x 1..m read a clamped entry: no case that is taken there uses it.
+// ---------------------------------------------------------------------------
+template <int S>
+struct Mu1Feed {
+  static constexpr int BLK = GhostFeed<S, 9>::BLK;
+  static constexpr int RING_DW = 2 * BLK * 64;
+  // this lane's columns at the BLK steps of the block are jj0, jj0+1, ... (before wrapping), its strip `strip`
+  __device__ static __forceinline__ void issue(const int32_t* tab, int n, int m, int P, int jj0, int strip,
+                                               int T, int w, int il, uint32_t lds_base) {
+    constexpr int RR = Geo<S>::RR;
+#pragma unroll
+    for (int t = 0; t < BLK; ++t) {
+      int jf = jj0 + t, q = strip;
+      if (jf >= P) { jf -= P; ++q; }
+      const int i = (q * T + w) * RR + il - 1;
+      const int ic = min(max(i, 1), n), jc = min(max(jf, 1), m);
+      const int32_t* p = tab + (int64_t)(ic - 1) * m + (jc - 1);
+      const uint32_t dst = lds_base + t * 256;  // lane l lands at dst + 4*l
+      uint32_t keep;
+      asm volatile(
+          "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+          "global_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
+          : "=&s"(keep)
+          : "v"(p), "s"(dst)
+          : "memory");
+    }
+  }
+};
+
 }  // namespace bialign

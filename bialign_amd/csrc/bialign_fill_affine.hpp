@@ -72,8 +72,9 @@ __device__ __forceinline__ void store_chunk(int32_t* p, v4i v, bool wt) {
 //   A.resw_k strips per round, independent of each other, each into its own scratch slot); the
 //   strip the walk stands in is swept only up to the walk's column.  One wave per strip.
 //   PACK: interior steps store packed records, the others full records in the pair's second region (Pack<S>).
+//   DENSE1: mu1(i,j) from the pair's dense table (Mu1Feed) instead of s1 and the sequence codes, which are then not staged.
 template <int S, bool BETA_NONPOS, int TW, bool XCU, bool DENSE = false, bool LEAN = false, bool RESW = false,
-          bool PACK = false>
+          bool PACK = false, bool DENSE1 = false>
 __global__ void __launch_bounds__(64 * TW) BIALIGN_WPE_ATTR fill_affine_kernel(const DeviceBatch A) {
   static_assert(!PACK || (!LEAN && !RESW && S >= 1), "packed records: full-storage sweeps with a band");
   using PK_ = Pack<S>;
@@ -86,7 +87,8 @@ __global__ void __launch_bounds__(64 * TW) BIALIGN_WPE_ATTR fill_affine_kernel(c
   // 160 KB of LDS only with half-length ghost blocks and molecule A's codes left in global memory (they
   // are read once per strip, in set_row).
   constexpr bool DIET = TW == 8 && S == 2;
-  static_assert(!DIET || (!DENSE && !RESW), "the diet variant exists for LOOKUP sweeps only");
+  static_assert(!DIET || (!DENSE && !DENSE1 && !RESW), "the diet variant exists for LOOKUP sweeps only");
+  static_assert(!DENSE1 || !PACK, "dense mu1: full records");
   static_assert(!RESW || (TW == 1 && !XCU && !LEAN), "strip re-sweeps: one wave, full records");
   using G_ = Geo<S>;
   using R_ = Rec<S, 9, LEAN>;
@@ -128,18 +130,21 @@ __global__ void __launch_bounds__(64 * TW) BIALIGN_WPE_ATTR fill_affine_kernel(c
   //      words, score tables, sequence codes
   using GF = GhostFeed<S, 9, LEAN || RESW, DIET ? 2 : 0>;  // a re-sweep replays LEAN records
   using MF = Mu2Feed<S>;
-  constexpr int PERW = GF::RING_DW + NV * NCOL + (DENSE ? MF::RING_DW : 0);  // dwords per wave
+  using M1F = Mu1Feed<S>;
+  constexpr int MU2W = DENSE ? MF::RING_DW : 0;
+  constexpr int PERW = GF::RING_DW + NV * NCOL + MU2W + (DENSE1 ? M1F::RING_DW : 0);  // dwords per wave
   v4i* ring = reinterpret_cast<v4i*>(smem + wl * GF::RING_DW);   // ghost-row ring, two halves
   int32_t* xch = smem + TW * GF::RING_DW + wl * (NV * NCOL);     // exchange array [NCOL lanes][NV]
   int32_t* mu2ring = smem + TW * (GF::RING_DW + NV * NCOL) + wl * MF::RING_DW;  // dense-mu2 ring
+  int32_t* mu1ring = smem + TW * (GF::RING_DW + NV * NCOL + MU2W) + wl * M1F::RING_DW;  // dense-mu1 ring
   volatile int32_t* prog_lds = smem + TW * PERW;                  // [16] (in-workgroup teams)
   int32_t* s1 = smem + TW * PERW + 16;                            // [k1*k1]
   int32_t* s2 = s1 + k1 * k1;                                   // [k2*k2]
   const int npad = (n + 3) & ~3, mpad = (m + 2 * PADB + 3) & ~3;
   uint8_t* sa = reinterpret_cast<uint8_t*>(s2 + k2 * k2);  // seq A codes, [i-1]   (DIET: not staged)
-  uint8_t* ca = sa + npad;                                  // cls A,       [k-1]
+  uint8_t* ca = sa + (DENSE1 ? 0 : npad);                   // cls A,       [k-1]   (DENSE1: no sequence codes)
   uint8_t* sb = DIET ? sa : ca + npad;                      // seq B codes, [j-1+PADB]
-  uint8_t* cb = sb + mpad;                                  // cls B,       [l-1+PADB]
+  uint8_t* cb = sb + (DENSE1 ? 0 : mpad);                   // cls B,       [l-1+PADB]
 
   for (int t = threadIdx.x; t < TW * PERW; t += 64 * TW) smem[t] = SENT;
   if (threadIdx.x < 16) prog_lds[threadIdx.x] = 0;
@@ -147,13 +152,13 @@ __global__ void __launch_bounds__(64 * TW) BIALIGN_WPE_ATTR fill_affine_kernel(c
   for (int t = threadIdx.x; t < k2 * k2; t += 64 * TW) s2[t] = A.s2[t];
   if (!DIET)
     for (int t = threadIdx.x; t < n; t += 64 * TW) {
-      sa[t] = A.seq_a[pd.seq_a + t];
+      if (!DENSE1) sa[t] = A.seq_a[pd.seq_a + t];
       ca[t] = A.cls_a[pd.seq_a + t];
     }
   for (int t = threadIdx.x; t < m + 2 * PADB; t += 64 * TW) {
     const int src = t - PADB;
     const bool ok = src >= 0 && src < m;
-    sb[t] = ok ? A.seq_b[pd.seq_b + src] : 0;
+    if (!DENSE1) sb[t] = ok ? A.seq_b[pd.seq_b + src] : 0;
     cb[t] = ok ? A.cls_b[pd.seq_b + src] : 0;
   }
   __syncthreads();
@@ -191,7 +196,7 @@ __global__ void __launch_bounds__(64 * TW) BIALIGN_WPE_ATTR fill_affine_kernel(c
       s2row = (k >= 1 && k <= n) ? A.cls_a[pd.seq_a + k - 1] * k2 : 0;
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     } else {
-      s1row = (i >= 1 && i <= n) ? sa[i - 1] * k1 : 0;
+      s1row = (!DENSE1 && i >= 1 && i <= n) ? sa[i - 1] * k1 : 0;
       s2row = (k >= 1 && k <= n) ? ca[k - 1] * k2 : 0;
     }
   };
@@ -262,7 +267,14 @@ __global__ void __launch_bounds__(64 * TW) BIALIGN_WPE_ATTR fill_affine_kernel(c
   const uint32_t mu2_lds = __builtin_amdgcn_readfirstlane(
       (uint32_t)(uintptr_t)(__attribute__((address_space(3))) int32_t*)smem) +
       (TW * (GF::RING_DW + NV * NCOL) + wl * MF::RING_DW) * 4;
-  const int32_t* const mu2tab = DENSE ? A.mu2_dense + pd.mu2_off : nullptr;
+  const int32_t* const mu2tab = DENSE ? A.dense_tab + pd.tab_off : nullptr;
+  uint32_t mu1_lds = 0;
+  const int32_t* mu1tab = nullptr;
+  if constexpr (DENSE1) {
+    mu1_lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) int32_t*)smem) +
+              (TW * (GF::RING_DW + NV * NCOL + MU2W) + wl * M1F::RING_DW) * 4;
+    mu1tab = A.dense_tab + pd.tab_off + (DENSE ? (int64_t)n * m : 0);
+  }
   int mu2w[W];  // dense-mu2 mode: mu2(k, j-s .. j+s) of this lane's row
 #pragma unroll
   for (int bb = 0; bb < W; ++bb) mu2w[bb] = 0;
@@ -275,6 +287,7 @@ __global__ void __launch_bounds__(64 * TW) BIALIGN_WPE_ATTR fill_affine_kernel(c
     else
       GF::issue(lay, h0 + Qbase * P, blk_q, blk_rem, P, T, w, GOFF, rec_last, L, ring_lds + half * GF::SLOTS * 16);
     if (DENSE) MF::issue(mu2tab, n, m, P, jj0, Qbase + strip, T, w, il, aa, mu2_lds + half * MF::BLK * 256);
+    if constexpr (DENSE1) M1F::issue(mu1tab, n, m, P, jj0, Qbase + strip, T, w, il, mu1_lds + half * M1F::BLK * 256);
     blk_rem += GF::BLK;
     if (blk_rem >= P) { blk_rem -= P; ++blk_q; }
   };
@@ -320,7 +333,7 @@ __global__ void __launch_bounds__(64 * TW) BIALIGN_WPE_ATTR fill_affine_kernel(c
   int mu1n = 0, mu2n[W];
   auto lookup_mu = [&]() __attribute__((always_inline)) {  // score inputs of the column this lane works on next (LOOKUP form)
     const int jc = min(max(jj, 0), m + 1);
-    mu1n = s1[s1row + sb[jc - 1 + PADB]];
+    if (!DENSE1) mu1n = s1[s1row + sb[jc - 1 + PADB]];
 #pragma unroll
     for (int bb = 0; bb < W; ++bb) mu2n[bb] = DENSE ? 0 : s2[s2row + cb[jc + bb]];  // l-1+PADB = jc+bb
   };
@@ -332,7 +345,7 @@ __global__ void __launch_bounds__(64 * TW) BIALIGN_WPE_ATTR fill_affine_kernel(c
   int sbn = 0, cbn = 0;
   auto fetch_codes = [&]() __attribute__((always_inline)) {
     const int jc1 = min(max(jj + 1, 0), m + 1);
-    sbn = sb[jc1 - 1 + PADB];
+    sbn = DENSE1 ? 0 : sb[jc1 - 1 + PADB];
     cbn = DENSE ? 0 : cb[jc1 + W - 1];
   };
   if (PREF) {
@@ -480,7 +493,9 @@ __global__ void __launch_bounds__(64 * TW) BIALIGN_WPE_ATTR fill_affine_kernel(c
 
     // ---- 2. score inputs of this column (pyx:260-261; LOOKUP form)
     const int jc = INTERIOR ? jj : min(max(jj, 0), m + 1);
-    const int mu1 = PREF ? mu1n : s1[s1row + sb[jc - 1 + PADB]];
+    int mu1;
+    if constexpr (DENSE1) mu1 = mu1ring[(ghalf * M1F::BLK + gt) * 64 + L];
+    else mu1 = PREF ? mu1n : s1[s1row + sb[jc - 1 + PADB]];
     int mu2[W];
     if (DENSE) {  // slide the window, take this step's new value from the ring
 #pragma unroll
@@ -815,7 +830,7 @@ __global__ void __launch_bounds__(64 * TW) BIALIGN_WPE_ATTR fill_affine_kernel(c
     }
     if (PREF) {
       if (INTERIOR) {  // same row, next column, everything inside the molecule: the window slides by one, and the
-        mu1n = s1[s1row + sbn];  // two codes it needs were fetched at the end of the step before
+        if (!DENSE1) mu1n = s1[s1row + sbn];  // two codes it needs were fetched at the end of the step before
         if (!DENSE) {
 #pragma unroll
           for (int bb = 0; bb + 1 < W; ++bb) dmov(mu2n[bb], mu2[bb + 1]);

@@ -12,7 +12,8 @@ namespace bialign {
 // ---------------------------------------------------------------------------
 //   XCU: the team is A.team one-wave workgroups on any CUs (progress words in HBM, write-through
 //   stores), as in fill_affine_kernel -- for a handful of long pairs, e.g. one pair from the CLI.
-template <int S, int TW, bool DENSE = false, bool LEAN = false, bool RESW = false, bool XCU = false>
+//   DENSE1: mu1(i,j) from the pair's dense table (Mu1Feed), as in fill_affine_kernel.
+template <int S, int TW, bool DENSE = false, bool LEAN = false, bool RESW = false, bool XCU = false, bool DENSE1 = false>
 __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch A) {
   static_assert(!XCU || (TW == 1 && !RESW), "cross-CU teams are built from one-wave workgroups");
   using G_ = Geo<S>;
@@ -48,31 +49,34 @@ __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch 
 
   using GF = GhostFeed<S, 1, LEAN || RESW>;
   using MF = Mu2Feed<S>;
-  constexpr int PERW = GF::RING_DW + NV * NCOL + (DENSE ? MF::RING_DW : 0);
+  using M1F = Mu1Feed<S>;
+  constexpr int MU2W = DENSE ? MF::RING_DW : 0;
+  constexpr int PERW = GF::RING_DW + NV * NCOL + MU2W + (DENSE1 ? M1F::RING_DW : 0);
   v4i* ring = reinterpret_cast<v4i*>(smem + wl * GF::RING_DW);
   int32_t* xch = smem + TW * GF::RING_DW + wl * (NV * NCOL);
   int32_t* mu2ring = smem + TW * (GF::RING_DW + NV * NCOL) + wl * MF::RING_DW;
+  int32_t* mu1ring = smem + TW * (GF::RING_DW + NV * NCOL + MU2W) + wl * M1F::RING_DW;
   volatile int32_t* prog = smem + TW * PERW;  // [16] steps with acknowledged stores
   int32_t* s1 = smem + TW * PERW + 16;
   int32_t* s2 = s1 + k1 * k1;
   const int npad = (n + 3) & ~3, mpad = (m + 2 * PADB + 3) & ~3;
   uint8_t* sa = reinterpret_cast<uint8_t*>(s2 + k2 * k2);
-  uint8_t* ca = sa + npad;
+  uint8_t* ca = sa + (DENSE1 ? 0 : npad);  // (DENSE1: no sequence codes)
   uint8_t* sb = ca + npad;
-  uint8_t* cb = sb + mpad;
+  uint8_t* cb = sb + (DENSE1 ? 0 : mpad);
 
   for (int t = threadIdx.x; t < TW * PERW; t += 64 * TW) smem[t] = SENT;
   if (threadIdx.x < 16) prog[threadIdx.x] = 0;
   for (int t = threadIdx.x; t < k1 * k1; t += 64 * TW) s1[t] = A.s1[t];
   for (int t = threadIdx.x; t < k2 * k2; t += 64 * TW) s2[t] = A.s2[t];
   for (int t = threadIdx.x; t < n; t += 64 * TW) {
-    sa[t] = A.seq_a[pd.seq_a + t];
+    if (!DENSE1) sa[t] = A.seq_a[pd.seq_a + t];
     ca[t] = A.cls_a[pd.seq_a + t];
   }
   for (int t = threadIdx.x; t < m + 2 * PADB; t += 64 * TW) {
     const int src = t - PADB;
     const bool ok = src >= 0 && src < m;
-    sb[t] = ok ? A.seq_b[pd.seq_b + src] : 0;
+    if (!DENSE1) sb[t] = ok ? A.seq_b[pd.seq_b + src] : 0;
     cb[t] = ok ? A.cls_b[pd.seq_b + src] : 0;
   }
   __syncthreads();
@@ -96,7 +100,7 @@ __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch 
     i = (Qbase + q * T + w) * RR + il - 1;
     const int k = i + aa - S;
     act_row = live && i >= 0 && i <= n && k >= 0 && k <= n;
-    s1row = (i >= 1 && i <= n) ? sa[i - 1] * k1 : 0;
+    s1row = (!DENSE1 && i >= 1 && i <= n) ? sa[i - 1] * k1 : 0;
     s2row = (k >= 1 && k <= n) ? ca[k - 1] * k2 : 0;
   };
   set_row(0);
@@ -143,7 +147,11 @@ __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch 
   const uint32_t mu2_lds = __builtin_amdgcn_readfirstlane(
       (uint32_t)(uintptr_t)(__attribute__((address_space(3))) int32_t*)smem) +
       (TW * (GF::RING_DW + NV * NCOL) + wl * MF::RING_DW) * 4;
-  const int32_t* const mu2tab = DENSE ? A.mu2_dense + pd.mu2_off : nullptr;
+  const int32_t* const mu2tab = DENSE ? A.dense_tab + pd.tab_off : nullptr;
+  const uint32_t mu1_lds = __builtin_amdgcn_readfirstlane(
+      (uint32_t)(uintptr_t)(__attribute__((address_space(3))) int32_t*)smem) +
+      (TW * (GF::RING_DW + NV * NCOL + MU2W) + wl * M1F::RING_DW) * 4;
+  const int32_t* const mu1tab = DENSE1 ? A.dense_tab + pd.tab_off + (DENSE ? (int64_t)n * m : 0) : nullptr;
   int mu2w[W];
 #pragma unroll
   for (int bb = 0; bb < W; ++bb) mu2w[bb] = 0;
@@ -151,6 +159,7 @@ __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch 
     wait_partner(h0 + GF::BLK - 1);
     GF::issue(lay, h0 + Qbase * P, blk_q, blk_rem, P, T, w, GOFF, rec_last, L, ring_lds + half * GF::SLOTS * 16);
     if (DENSE) MF::issue(mu2tab, n, m, P, jj0, Qbase + strip, T, w, il, aa, mu2_lds + half * MF::BLK * 256);
+    if (DENSE1) M1F::issue(mu1tab, n, m, P, jj0, Qbase + strip, T, w, il, mu1_lds + half * M1F::BLK * 256);
     blk_rem += GF::BLK;
     if (blk_rem >= P) { blk_rem -= P; ++blk_q; }
   };
@@ -182,7 +191,7 @@ __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch 
       inL1[bb] = xch[bb * NCOL + colL1];
     }
     const int jc = min(max(jj, 0), m + 1);
-    const int mu1 = s1[s1row + sb[jc - 1 + PADB]];
+    const int mu1 = DENSE1 ? mu1ring[(ghalf * M1F::BLK + gt) * 64 + L] : s1[s1row + sb[jc - 1 + PADB]];
     int mu2[W];
     if (DENSE) {
 #pragma unroll

@@ -130,10 +130,11 @@ struct bialign_batch {
   bool packed_sizing = false;          // chunks and pair offsets were planned with the packed sizes
   std::vector<int64_t> full_dwords;    // per pair: dwords of its full-record form (for the fallback's re-plan)
   DevBuf<uint8_t> d_seq_a, d_cls_a, d_seq_b, d_cls_b, d_trace;
-  DevBuf<int32_t> d_mu2;  // dense-mu2 mode: all pairs' n x m tables
+  DevBuf<int32_t> d_tab;  // dense forms: all pairs' n x m tables (per pair mu2's, then mu1's; PairDesc::tab_off)
   DevBuf<int32_t> d_wide_ring;  // wide-band affine sweep: derived values of the last levels (bialign_wide.hpp)
   DevBuf<int64_t> d_wide_off;   // ... per pair of a launch: offset of its ring
-  bool dense = false;
+  bool dense = false;       // mu2 in DENSE form
+  bool dense1 = false;      // mu1 in DENSE form (kernels with DENSE1 / D1 set; no packed records, no slim or diet sweeps)
   bool wide = false;        // max_shift above the tiled kernels: anti-diagonal path (bialign_wide.hpp), reference-order layers
   bool lean = false;        // LEAN records: the sweep keeps only the strip-bottom rows
   bool lean_trace = false;  // ... and tracebacks re-sweep one strip at a time into a scratch area
@@ -165,7 +166,8 @@ struct bialign_batch {
     v.trace_len = d_tlen.p;
     v.complete = d_complete.p;
     v.errflag = d_err.p;
-    v.mu2_dense = dense ? d_mu2.p : nullptr;
+    v.dense_tab = (dense || dense1) ? d_tab.p : nullptr;
+    v.dense_forms = (dense ? 1 : 0) | (dense1 ? 2 : 0);
     v.scratch = d_layers.p;  // a pair's scratch records follow its LEAN records in the same buffer
     v.tstate = d_tstate.p;
     v.resw_k = resw_k;
@@ -188,28 +190,29 @@ struct TeamShape {
 inline bool slim_available(const bialign_batch* b) {
   const char* sw = getenv("BIALIGN_SLIM");  // "0": tests / A-B, the two-wave kernels only
   const bool off = sw && atoi(sw) == 0;
-  return !off && b->affine && b->S == 1 && !b->dense && !b->wide && b->prm.gap_opening_cost <= 0 && (b->lean || b->pack_now());
+  return !off && b->affine && b->S == 1 && !b->dense && !b->dense1 && !b->wide && b->prm.gap_opening_cost <= 0 && (b->lean || b->pack_now());
 }
 
 // xcu_resident: one-wave workgroups of the cross-CU kernel the device holds at once (0: no such kernel);
 // xcu8_resident: likewise its eight-wave workgroups (s=2 affine sweep only, else 0)
 TeamShape team_shape(const bialign_batch* b, int first, int count, int xcu_resident, int xcu8_resident = 0);
 inline bool diet8_available(const bialign_batch* b) {  // the eight-wave s=2 affine kernel and its LDS layout
-  return b->affine && b->S == 2 && !b->dense && b->lds_diet8 <= 160 * 1024;
+  return b->affine && b->S == 2 && !b->dense && !b->dense1 && b->lds_diet8 <= 160 * 1024;
 }
 // Cross-CU launches of all engines of this process on one device run one after the other (each needs
 // the whole device's wave slots): the stream waits for the previous such launch, the new one is recorded.
 int xcu_serial_begin(bialign_engine* e);
 int xcu_serial_end(bialign_engine* e);
 
-template <int S, bool BETA_NONPOS, int TW, bool XCU, bool DENSE = false, bool LEAN = false, bool PACK = false>
+template <int S, bool BETA_NONPOS, int TW, bool XCU, bool DENSE = false, bool LEAN = false, bool PACK = false,
+          bool DENSE1 = false>
 int launch_fill_affine_t(bialign_batch* b, const DeviceBatch& v, int first, int count, int gw) {
   DeviceBatch w = v;
   w.order = v.order + first;
   w.team = gw;
   b->packed_layers = PACK;
   if (PACK) b->used_pack = true;
-  auto kern = fill_affine_kernel<S, BETA_NONPOS, TW, XCU, DENSE, LEAN, false, PACK>;
+  auto kern = fill_affine_kernel<S, BETA_NONPOS, TW, XCU, DENSE, LEAN, false, PACK, DENSE1>;
   const size_t lds = (S == 2 && TW == 8) ? b->lds_diet8 : b->lds_base + (size_t)TW * b->lds_per_wave;
   if (lds > 64 * 1024)
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -266,14 +269,14 @@ int launch_fill_affine_slim(bialign_batch* b, const DeviceBatch& v, int first, i
 
 // One-wave workgroups of the cross-CU kernel <S, LEAN> the device can hold at once, from the runtime's
 // occupancy calculation for the actual code object (registers, LDS): the cap of a cross-CU grid.
-template <int S, bool LEAN, int TW = 1, bool DENSE = false>
+template <int S, bool LEAN, int TW = 1, bool DENSE = false, bool DENSE1 = false>
 int xcu_resident_blocks(bialign_batch* b) {
   int& cached = b->xcu_resident[(LEAN ? 1 : 0) + (TW == 8 ? 2 : 0)];  // (a batch is either DENSE or not)
   if (cached >= 0) return cached;
   cached = 0;
-  if constexpr ((DENSE ? S <= 3 : true) && (TW == 1 || S == 2)) {
+  if constexpr ((DENSE || DENSE1 ? S <= 3 : true) && (TW == 1 || S == 2)) {
     if (TW == 8 && !diet8_available(b)) return cached;
-    auto kern = fill_affine_kernel<S, true, TW, true, DENSE, LEAN>;
+    auto kern = fill_affine_kernel<S, true, TW, true, DENSE, LEAN, false, false, DENSE1>;
     const size_t lds = TW == 8 ? b->lds_diet8 : b->lds_base + b->lds_per_wave;
     if (lds > 64 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
@@ -290,8 +293,31 @@ int xcu_resident_blocks(bialign_batch* b) {
   return cached;
 }
 
+// Dense-mu1 sweeps: the launch shapes of the dense-mu2 ones (one-wave cross-CU teams up to s=3, in-workgroup teams of
+// 4 and 2, one wave), full or LEAN records.
+template <int S, bool LEAN, bool DENSE>
+int launch_fill_affine_dense1(bialign_batch* b, const DeviceBatch& v, int first, int count) {
+  if (b->prm.gap_opening_cost > 0) {
+    b->last_team = 1;
+    return launch_fill_affine_t<S, false, 1, false, DENSE, LEAN, false, true>(b, v, first, count, 1);
+  }
+  const TeamShape ts = team_shape(b, first, count, !b->no_xcu ? xcu_resident_blocks<S, LEAN, 1, DENSE, true>(b) : 0, 0);
+  b->last_team = ts.waves() * (ts.gw > 1 ? -1 : 1);
+  if constexpr (S <= 3) {
+    if (ts.gw > 1) return launch_fill_affine_t<S, true, 1, true, DENSE, LEAN, false, true>(b, v, first, count, ts.gw);
+    b->last_team = std::min(ts.tw, 4);
+    if (ts.tw >= 4) return launch_fill_affine_t<S, true, 4, false, DENSE, LEAN, false, true>(b, v, first, count, 1);
+    if (ts.tw >= 2) return launch_fill_affine_t<S, true, 2, false, DENSE, LEAN, false, true>(b, v, first, count, 1);
+  }
+  b->last_team = 1;
+  return launch_fill_affine_t<S, true, 1, false, DENSE, LEAN, false, true>(b, v, first, count, 1);
+}
+
 template <int S, bool LEAN>
 int launch_fill_affine_l(bialign_batch* b, const DeviceBatch& v, int first, int count) {
+  if (b->dense1)  // dense mu1 (with or without dense mu2)
+    return b->dense ? launch_fill_affine_dense1<S, LEAN, true>(b, v, first, count)
+                    : launch_fill_affine_dense1<S, LEAN, false>(b, v, first, count);
   if (b->prm.gap_opening_cost > 0) {  // rare: general-beta algebra, one wave per pair
     b->last_team = 1;
     return b->dense ? launch_fill_affine_t<S, false, 1, false, true, LEAN>(b, v, first, count, 1)
@@ -370,6 +396,13 @@ int launch_resweep_affine(bialign_batch* b, const DeviceBatch& v, int first, int
     HIP_TRY(hipGetLastError());
     return BIALIGN_OK;
   };
+  if (b->dense1) {
+    if (b->dense)
+      return b->prm.gap_opening_cost > 0 ? go(fill_affine_kernel<S, false, 1, false, true, false, true, false, true>)
+                                         : go(fill_affine_kernel<S, true, 1, false, true, false, true, false, true>);
+    return b->prm.gap_opening_cost > 0 ? go(fill_affine_kernel<S, false, 1, false, false, false, true, false, true>)
+                                       : go(fill_affine_kernel<S, true, 1, false, false, false, true, false, true>);
+  }
   if (b->dense)
     return b->prm.gap_opening_cost > 0 ? go(fill_affine_kernel<S, false, 1, false, true, false, true>)
                                        : go(fill_affine_kernel<S, true, 1, false, true, false, true>);
@@ -382,7 +415,7 @@ template <int S>
 int launch_traceback_affine_strip(const bialign_batch* b, const DeviceBatch& v, int first, int count) {
   DeviceBatch w = v;
   w.order = v.order + first;
-  auto kern = traceback_affine_kernel<S, true, true>;
+  auto kern = b->dense1 ? traceback_affine_kernel<S, true, true, false, false, true> : traceback_affine_kernel<S, true, true>;
   if (b->lds_trace > 64 * 1024)
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_trace));
@@ -397,6 +430,15 @@ int launch_traceback_affine(const bialign_batch* b, const DeviceBatch& v, int fi
   DeviceBatch w = v;
   w.order = v.order + first;
   const int blocks = count;  // one wave per pair
+  if (b->dense1 && do_trace) {  // (the score-only form reads no scores: the LOOKUP kernel serves below)
+    auto kern = traceback_affine_kernel<S, true, false, false, false, true>;
+    if (b->lds_trace > 64 * 1024)
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)b->lds_trace));
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), b->lds_trace, b->eng->stream, w, count);
+    HIP_TRY(hipGetLastError());
+    return BIALIGN_OK;
+  }
   if (b->lds_trace > 64 * 1024)
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(traceback_affine_kernel<S, true>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_trace));
@@ -423,13 +465,13 @@ int launch_traceback_affine(const bialign_batch* b, const DeviceBatch& v, int fi
   return BIALIGN_OK;
 }
 
-template <int S, int TW, bool DENSE = false, bool LEAN = false, bool XCU = false>
+template <int S, int TW, bool DENSE = false, bool LEAN = false, bool XCU = false, bool DENSE1 = false>
 int launch_fill_linear_t(bialign_batch* b, const DeviceBatch& v, int first, int count, int gw = 1) {
   DeviceBatch w = v;
   w.order = v.order + first;
   w.team = gw;
   b->packed_layers = false;
-  auto kern = fill_linear_kernel<S, TW, DENSE, LEAN, false, XCU>;
+  auto kern = fill_linear_kernel<S, TW, DENSE, LEAN, false, XCU, DENSE1>;
   const size_t lds = b->lds_base + (size_t)TW * b->lds_per_wave;
   if (lds > 64 * 1024)
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -453,12 +495,12 @@ int launch_fill_linear_t(bialign_batch* b, const DeviceBatch& v, int first, int 
 }
 
 // one-wave workgroups of the one-layer cross-CU kernel the device holds at once
-template <int S, bool LEAN, bool DENSE = false>
+template <int S, bool LEAN, bool DENSE = false, bool DENSE1 = false>
 int xcu_resident_linear(bialign_batch* b) {
   int& cached = b->xcu_resident[LEAN ? 1 : 0];
   if (cached >= 0) return cached;
   cached = 0;
-  auto kern = fill_linear_kernel<S, 1, DENSE, LEAN, false, true>;
+  auto kern = fill_linear_kernel<S, 1, DENSE, LEAN, false, true, DENSE1>;
   const size_t lds = b->lds_base + b->lds_per_wave;
   if (lds > 64 * 1024 &&
       hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
@@ -473,8 +515,21 @@ int xcu_resident_linear(bialign_batch* b) {
   return cached = per_cu * b->eng->num_cu;
 }
 
+// dense mu1 (with or without dense mu2): one-wave cross-CU teams, in-workgroup teams of 2, one wave
+template <int S, bool LEAN, bool DENSE>
+int launch_fill_linear_dense1(bialign_batch* b, const DeviceBatch& v, int first, int count) {
+  const TeamShape ts = team_shape(b, first, count, !b->no_xcu ? xcu_resident_linear<S, LEAN, DENSE, true>(b) : 0);
+  b->last_team = ts.waves() * (ts.gw > 1 ? -1 : 1);
+  if (ts.gw > 1) return launch_fill_linear_t<S, 1, DENSE, LEAN, true, true>(b, v, first, count, ts.gw);
+  return ts.tw >= 2 ? launch_fill_linear_t<S, 2, DENSE, LEAN, false, true>(b, v, first, count)
+                    : launch_fill_linear_t<S, 1, DENSE, LEAN, false, true>(b, v, first, count);
+}
+
 template <int S, bool LEAN>
 int launch_fill_linear_l(bialign_batch* b, const DeviceBatch& v, int first, int count) {
+  if (b->dense1)
+    return b->dense ? launch_fill_linear_dense1<S, LEAN, true>(b, v, first, count)
+                    : launch_fill_linear_dense1<S, LEAN, false>(b, v, first, count);
   const bool xcu_ok = !b->no_xcu;
   const TeamShape ts = team_shape(b, first, count, !xcu_ok ? 0 : (b->dense ? xcu_resident_linear<S, LEAN, true>(b)
                                                                              : xcu_resident_linear<S, LEAN>(b)));
@@ -511,6 +566,9 @@ int launch_resweep_linear(bialign_batch* b, const DeviceBatch& v, int first, int
     HIP_TRY(hipGetLastError());
     return BIALIGN_OK;
   };
+  if (b->dense1)
+    return b->dense ? go(fill_linear_kernel<S, 1, true, false, true, false, true>)
+                    : go(fill_linear_kernel<S, 1, false, false, true, false, true>);
   return b->dense ? go(fill_linear_kernel<S, 1, true, false, true>) : go(fill_linear_kernel<S, 1, false, false, true>);
 }
 
@@ -518,7 +576,7 @@ template <int S>
 int launch_traceback_linear_strip(const bialign_batch* b, const DeviceBatch& v, int first, int count) {
   DeviceBatch w = v;
   w.order = v.order + first;
-  auto kern = traceback_linear_kernel<S, true, true>;
+  auto kern = b->dense1 ? traceback_linear_kernel<S, true, true, false, true> : traceback_linear_kernel<S, true, true>;
   if (b->lds_trace > 64 * 1024)
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_trace));
@@ -533,6 +591,15 @@ int launch_traceback_linear(const bialign_batch* b, const DeviceBatch& v, int fi
   DeviceBatch w = v;
   w.order = v.order + first;
   const int blocks = count;  // one wave per pair
+  if (b->dense1 && do_trace) {  // (the score-only form reads no scores: the LOOKUP kernel serves below)
+    auto kern = traceback_linear_kernel<S, true, false, false, true>;
+    if (b->lds_trace > 64 * 1024)
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)b->lds_trace));
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), b->lds_trace, b->eng->stream, w, count);
+    HIP_TRY(hipGetLastError());
+    return BIALIGN_OK;
+  }
   if (b->lds_trace > 64 * 1024)
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(traceback_linear_kernel<S, true>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_trace));

@@ -23,23 +23,25 @@ struct TraceInputs {
   const int32_t *s1, *s2;
   const uint8_t *sa, *ca, *sb, *cb;
 };
+// D1 (dense mu1): the sequence codes are not staged (sa, sb are then unused).
+template <bool D1 = false>
 __device__ __forceinline__ TraceInputs stage_trace_inputs(const DeviceBatch& A, const PairDesc& pd,
                                                           int32_t* smem) {
   const int k1 = A.k1, k2 = A.k2, n = pd.n, m = pd.m;
   int32_t* s1 = smem;
   int32_t* s2 = s1 + k1 * k1;
   uint8_t* sa = reinterpret_cast<uint8_t*>(s2 + k2 * k2);
-  uint8_t* ca = sa + ((n + 3) & ~3);
+  uint8_t* ca = sa + (D1 ? 0 : ((n + 3) & ~3));
   uint8_t* sb = ca + ((n + 3) & ~3);
-  uint8_t* cb = sb + ((m + 3) & ~3);
+  uint8_t* cb = sb + (D1 ? 0 : ((m + 3) & ~3));
   for (int t = threadIdx.x; t < k1 * k1; t += 64) s1[t] = A.s1[t];
   for (int t = threadIdx.x; t < k2 * k2; t += 64) s2[t] = A.s2[t];
   for (int t = threadIdx.x; t < n; t += 64) {
-    sa[t] = A.seq_a[pd.seq_a + t];
+    if (!D1) sa[t] = A.seq_a[pd.seq_a + t];
     ca[t] = A.cls_a[pd.seq_a + t];
   }
   for (int t = threadIdx.x; t < m; t += 64) {
-    sb[t] = A.seq_b[pd.seq_b + t];
+    if (!D1) sb[t] = A.seq_b[pd.seq_b + t];
     cb[t] = A.cls_b[pd.seq_b + t];
   }
   __syncthreads();
@@ -62,7 +64,8 @@ __device__ __forceinline__ int wave_min16(int v) {  // min over lanes 0..15, val
 //   WIDE (max_shift beyond the tiled kernels, bialign_wide.hpp): the band half-width is the runtime
 //   value A.wide_s and the layers lie in the reference's own order; S is then a dummy (0).
 //   PACK: the sweep stored packed records in interior steps (Pack<S>).
-template <int S, bool DO_TRACE, bool STRIP = false, bool WIDE = false, bool PACK = false>
+//   D1: mu1 from the pair's dense table (DeviceBatch::dense_forms bit 1), mu2 dense if bit 0 is set.
+template <int S, bool DO_TRACE, bool STRIP = false, bool WIDE = false, bool PACK = false, bool D1 = false>
 __global__ void __launch_bounds__(64) traceback_affine_kernel(const DeviceBatch A, int npairs) {
   static_assert(!WIDE || !STRIP, "no lean traceback on the wide-band path");
   static_assert(!PACK || (!WIDE && !STRIP), "packed records: full-storage tiled sweeps");
@@ -112,8 +115,9 @@ __global__ void __launch_bounds__(64) traceback_affine_kernel(const DeviceBatch 
   } else {
     i = ts.i; j = ts.j; k = ts.k; l = ts.l; st = ts.st; cur = ts.cur; d0 = ts.d0; d1 = ts.d1; len = ts.len;
   }
-  const TraceInputs in = stage_trace_inputs(A, pd, smem);
+  const TraceInputs in = stage_trace_inputs<D1>(A, pd, smem);
   const uint8_t *sa = in.sa, *ca = in.ca, *sb = in.sb, *cb = in.cb;
+  const int32_t* const mu1tab = D1 ? mu1_table(A, pd) : nullptr;
 
   uint8_t* out = A.trace + pd.trace_off;
   bool finished = true;  // STRIP: false when the walk merely left this strip
@@ -125,10 +129,13 @@ __global__ void __launch_bounds__(64) traceback_affine_kernel(const DeviceBatch 
     if (STRIP && i < Qlo * RR) { finished = false; break; }  // above the re-swept strips: next round
     const int hU = st / 3, hV = st - 3 * hU;
     const int u0 = hU >= 1, u1 = hU != 1, v0 = hV >= 1, v1 = hV != 1;
-    const int mu1 = (i >= 1 && j >= 1) ? in.s1[sa[i - 1] * A.k1 + sb[j - 1]] : 0;
+    const int mu1 = (i >= 1 && j >= 1)
+                        ? (D1 ? mu1tab[(int64_t)(i - 1) * m + (j - 1)] : in.s1[sa[i - 1] * A.k1 + sb[j - 1]])
+                        : 0;
     const int mu2 = (k >= 1 && l >= 1)
-                        ? (A.mu2_dense ? A.mu2_dense[pd.mu2_off + (int64_t)(k - 1) * m + (l - 1)]
-                                       : in.s2[ca[k - 1] * A.k2 + cb[l - 1]])
+                        ? ((D1 ? (A.dense_forms & 1) != 0 : A.dense_tab != nullptr)
+                               ? A.dense_tab[pd.tab_off + (int64_t)(k - 1) * m + (l - 1)]
+                               : in.s2[ca[k - 1] * A.k2 + cb[l - 1]])
                         : 0;
     const int valU = hU == 2 ? mu1 : gamma, valV = hV == 2 ? mu2 : gamma;
 
@@ -193,7 +200,7 @@ __global__ void __launch_bounds__(64) traceback_affine_kernel(const DeviceBatch 
 // Non-affine traceback (pyx:513-531): the first case, in generator order, that is
 // guard-valid and reproduces the cell; stops when none does (the origin).  One wave
 // per pair, lane c < 13 = case c; "first" = wave-min over the matching lane ids.
-template <int S, bool DO_TRACE, bool STRIP = false, bool WIDE = false>  // STRIP, WIDE: see traceback_affine_kernel
+template <int S, bool DO_TRACE, bool STRIP = false, bool WIDE = false, bool D1 = false>  // STRIP, WIDE, D1: see traceback_affine_kernel
 __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch A, int npairs) {
   static_assert(!WIDE || !STRIP, "no lean traceback on the wide-band path");
   const int SR = WIDE ? A.wide_s : S;
@@ -225,8 +232,9 @@ __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch 
   int cur = (STRIP && ts.started) ? ts.cur : cell(n, m, SR, SR);
   if (c == 0 && !(STRIP && ts.started)) A.scores[pid] = cur;  // pyx:471
   if (!DO_TRACE) return;
-  const TraceInputs in = stage_trace_inputs(A, pd, smem);
+  const TraceInputs in = stage_trace_inputs<D1>(A, pd, smem);
   const uint8_t *sa = in.sa, *ca = in.ca, *sb = in.sb, *cb = in.cb;
+  const int32_t* const mu1tab = D1 ? mu1_table(A, pd) : nullptr;
 
   // offsets of the thirteen cases as bit masks o0*8+o1*4+o2*2+o3 (pyx:233-248), per lane
   constexpr int OFF[16] = {15, 10, 5, 12, 3, 8, 4, 2, 1, 11, 7, 14, 13, 0, 0, 0};
@@ -246,10 +254,13 @@ __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch 
   bool finished = true;
   while (true) {
     if (STRIP && i < Qlo * RR) { finished = false; break; }
-    const int mu1 = (i >= 1 && j >= 1) ? in.s1[sa[i - 1] * A.k1 + sb[j - 1]] : 0;
+    const int mu1 = (i >= 1 && j >= 1)
+                        ? (D1 ? mu1tab[(int64_t)(i - 1) * m + (j - 1)] : in.s1[sa[i - 1] * A.k1 + sb[j - 1]])
+                        : 0;
     const int mu2 = (k >= 1 && l >= 1)
-                        ? (A.mu2_dense ? A.mu2_dense[pd.mu2_off + (int64_t)(k - 1) * m + (l - 1)]
-                                       : in.s2[ca[k - 1] * A.k2 + cb[l - 1]])
+                        ? ((D1 ? (A.dense_forms & 1) != 0 : A.dense_tab != nullptr)
+                               ? A.dense_tab[pd.tab_off + (int64_t)(k - 1) * m + (l - 1)]
+                               : in.s2[ca[k - 1] * A.k2 + cb[l - 1]])
                         : 0;
     const int sc = kconst + (use1 ? mu1 : 0) + (use2 ? mu2 : 0);
     const int pi = i - o0, pj = j - o1, pk = k - o2, pl = l - o3;

@@ -17,7 +17,7 @@ struct PairDesc {
   int64_t seq_a, seq_b;   // offsets into the code arrays
   int64_t layer_off;      // dword offset of this pair's records in the chunk buffer
   int64_t trace_off;      // byte offset in the trace buffer
-  int64_t mu2_off;        // dense-mu2 mode: start of this pair's n x m table
+  int64_t tab_off;        // dense forms: start of this pair's tables in DeviceBatch::dense_tab (n x m each, mu2's first)
   int64_t scratch_off;    // lean traceback: dword offset of this pair's one-strip scratch records
 };
 
@@ -44,7 +44,7 @@ struct DeviceBatch {
   int32_t* trace_len;   // [npairs]
   int32_t* complete;    // [npairs]
   int32_t* errflag;     // [1] sticky device-side error (team protocol timeout)
-  const int32_t* mu2_dense;  // dense-mu2 mode: mu2(k,l) tables (else nullptr: LOOKUP form)
+  const int32_t* dense_tab;  // dense forms (DeviceBatch::dense_forms): the pairs' mu2(k,l) / mu1(i,j) tables (else nullptr)
   int32_t* prog;        // cross-CU teams: [pairs in launch][PROG_WORDS] progress words, zeroed per launch
   int32_t team;         // cross-CU teams: workgroups (= waves) per pair
   int32_t* scratch;     // lean traceback: full records of resw_k strips per pair
@@ -58,7 +58,18 @@ struct DeviceBatch {
   int32_t wide_score_only;       // ... 1: no layers are stored, the last level's point writes the score
   int32_t launch_pairs;     // fill_affine_slim_kernel: pairs of this launch (a workgroup holds several)
   int32_t slim_code_bytes;  // fill_affine_slim_kernel: LDS bytes of one pair's sequence and class codes
+  // Which scores come as dense tables: bit 0 mu2, bit 1 mu1.  The kernels built for a LOOKUP mu1 only look at
+  // dense_tab (non-null = dense mu2); those built for a dense mu1 read the bits.  (It fills what was the struct's
+  // tail padding: the kernel argument block of the existing kernels keeps its size.)
+  int32_t dense_forms;
 };
+static_assert(sizeof(DeviceBatch) == 224, "DeviceBatch grew: the kernels' argument blocks would change");
+
+// Dense mu1 (DeviceBatch::dense_forms bit 1): pair pd's n x m table, mu1(i,j) at [(i-1)*m + (j-1)].  It follows the
+// pair's mu2 table when that one is dense too.
+__host__ __device__ inline const int32_t* mu1_table(const DeviceBatch& A, const PairDesc& pd) {
+  return A.dense_tab + pd.tab_off + ((A.dense_forms & 1) ? (int64_t)pd.n * pd.m : 0);
+}
 
 template <int S>
 struct Geo {

@@ -8,8 +8,10 @@ int launch_fill_wide(bialign_batch* b, const DeviceBatch& v, int first, int coun
   DeviceBatch w = v;
   w.order = v.order + first;
   b->packed_layers = false;
-  const void* kern = b->affine ? reinterpret_cast<const void*>(fill_wide_affine_kernel<0>)
-                               : reinterpret_cast<const void*>(fill_wide_linear_kernel<0>);
+  const void* kern = b->affine ? (b->dense1 ? reinterpret_cast<const void*>(fill_wide_affine_kernel<1>)
+                                           : reinterpret_cast<const void*>(fill_wide_affine_kernel<0>))
+                               : (b->dense1 ? reinterpret_cast<const void*>(fill_wide_linear_kernel<1>)
+                                            : reinterpret_cast<const void*>(fill_wide_linear_kernel<0>));
   // Workgroups ("parts") per pair: as many as keep the device busy and can all be resident at once (they meet at a
   // counter after every level), no more than a level has work for; one after a lost-co-residency recovery.
   int parts = 1;
@@ -54,8 +56,12 @@ int launch_fill_wide(bialign_batch* b, const DeviceBatch& v, int first, int coun
     b->used_xcu = true;
     if (int rc = xcu_serial_begin(b->eng)) return rc;
   }
-  if (b->affine)
+  if (b->affine && b->dense1)
+    hipLaunchKernelGGL(fill_wide_affine_kernel<1>, dim3(count * parts), dim3(WIDE_THREADS), 0, b->eng->stream, w, b->S);
+  else if (b->affine)
     hipLaunchKernelGGL(fill_wide_affine_kernel<0>, dim3(count * parts), dim3(WIDE_THREADS), 0, b->eng->stream, w, b->S);
+  else if (b->dense1)
+    hipLaunchKernelGGL(fill_wide_linear_kernel<1>, dim3(count * parts), dim3(WIDE_THREADS), 0, b->eng->stream, w, b->S);
   else
     hipLaunchKernelGGL(fill_wide_linear_kernel<0>, dim3(count * parts), dim3(WIDE_THREADS), 0, b->eng->stream, w, b->S);
   const hipError_t launched = hipGetLastError();
@@ -77,6 +83,9 @@ int launch_traceback_wide(const bialign_batch* b, const DeviceBatch& v, int firs
     HIP_TRY(hipGetLastError());
     return BIALIGN_OK;
   };
+  if (b->dense1 && do_trace)  // (without the walk no score is read: the LOOKUP kernels serve)
+    return b->affine ? go(traceback_affine_kernel<0, true, false, true, false, true>, b->lds_trace)
+                     : go(traceback_linear_kernel<0, true, false, true, true>, b->lds_trace);
   if (b->affine)
     return do_trace ? go(traceback_affine_kernel<0, true, false, true>, b->lds_trace)
                     : go(traceback_affine_kernel<0, false, false, true>, 0);

@@ -35,8 +35,11 @@ struct WideCtx {
   int k1, k2;
   const uint8_t *sa, *ca, *sb, *cb;  // this pair's codes (global memory)
   const int32_t* mu2tab;             // dense mu2 table of this pair or nullptr
+  const int32_t* mu1tab;             // dense mu1 table of this pair (read by mu1<true> only)
   int32_t* lay;                      // this pair's layers
+  template <bool D1 = false>
   __device__ __forceinline__ int mu1(int i, int j) const {  // pyx:435-436 (never contributes at i=0 or j=0)
+    if (D1) return (i >= 1 && j >= 1) ? mu1tab[(int64_t)(i - 1) * m + (j - 1)] : 0;
     return (i >= 1 && j >= 1) ? s1[sa[i - 1] * k1 + sb[j - 1]] : 0;
   }
   __device__ __forceinline__ int mu2(int k, int l) const {  // pyx:438-440
@@ -164,7 +167,9 @@ __device__ __forceinline__ int wfY(int y, int x, int m, int beta) { return max(y
 __device__ __forceinline__ int wfX(int y, int x, int m, int beta) { return max(x, beta + max(y, m)); }
 __device__ __forceinline__ int wfM(int y, int x, int m) { return max(max(y, x), m); }
 
-template <int UNUSED = 0>  // (a template so that only bialign_wide.hip instantiates it)
+// D1 = 1: mu1 from the pair's dense table (DeviceBatch::dense_forms bit 1).  (A template also so that only
+// bialign_wide.hip instantiates it.)
+template <int D1 = 0>
 __global__ void __launch_bounds__(WIDE_THREADS) fill_wide_affine_kernel(const DeviceBatch A, int S) {
   const int parts = A.team, slot = blockIdx.x / parts, part = blockIdx.x - slot * parts;
   const int pid = A.order[slot];
@@ -174,7 +179,8 @@ __global__ void __launch_bounds__(WIDE_THREADS) fill_wide_affine_kernel(const De
   c.beta = A.beta; c.gamma = A.gamma; c.delta = A.delta;
   c.s1 = A.s1; c.s2 = A.s2; c.k1 = A.k1; c.k2 = A.k2;
   c.sa = A.seq_a + pd.seq_a; c.ca = A.cls_a + pd.seq_a; c.sb = A.seq_b + pd.seq_b; c.cb = A.cls_b + pd.seq_b;
-  c.mu2tab = A.mu2_dense ? A.mu2_dense + pd.mu2_off : nullptr;
+  c.mu2tab = (D1 ? (A.dense_forms & 1) != 0 : A.dense_tab != nullptr) ? A.dense_tab + pd.tab_off : nullptr;
+  c.mu1tab = D1 ? mu1_table(A, pd) : nullptr;
   c.lay = A.layers + pd.layer_off;
   const int n = c.n, m = c.m, W = c.W, HW = (W + 1) / 2;
   const int beta = c.beta, gamma = c.gamma, delta = c.delta;
@@ -228,7 +234,7 @@ __global__ void __launch_bounds__(WIDE_THREADS) fill_wide_affine_kernel(const De
             h3[3 * hU + hV] = __hip_atomic_load(src[c3] + (18 + 3 * hU + hV) * LV, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
         }
-        const int mu1 = c.mu1(i, j), mu2 = c.mu2(k, l);
+        const int mu1 = c.template mu1<D1 != 0>(i, j), mu2 = c.mu2(k, l);
 #if BIALIGN_EXP == 8
         stamp(0);  // address arithmetic, loads issued
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -317,7 +323,7 @@ __global__ void __launch_bounds__(WIDE_THREADS) fill_wide_affine_kernel(const De
 // ---------------------------------------------------------------------------
 // Non-affine fill (pyx:443-471): thirteen cases (pyx:233-248), one layer.
 // ---------------------------------------------------------------------------
-template <int UNUSED = 0>
+template <int D1 = 0>  // see fill_wide_affine_kernel
 __global__ void __launch_bounds__(WIDE_THREADS) fill_wide_linear_kernel(const DeviceBatch A, int S) {
   const int parts = A.team, slot = blockIdx.x / parts, part = blockIdx.x - slot * parts;
   const int pid = A.order[slot];
@@ -327,7 +333,8 @@ __global__ void __launch_bounds__(WIDE_THREADS) fill_wide_linear_kernel(const De
   c.beta = A.beta; c.gamma = A.gamma; c.delta = A.delta;
   c.s1 = A.s1; c.s2 = A.s2; c.k1 = A.k1; c.k2 = A.k2;
   c.sa = A.seq_a + pd.seq_a; c.ca = A.cls_a + pd.seq_a; c.sb = A.seq_b + pd.seq_b; c.cb = A.cls_b + pd.seq_b;
-  c.mu2tab = A.mu2_dense ? A.mu2_dense + pd.mu2_off : nullptr;
+  c.mu2tab = (D1 ? (A.dense_forms & 1) != 0 : A.dense_tab != nullptr) ? A.dense_tab + pd.tab_off : nullptr;
+  c.mu1tab = D1 ? mu1_table(A, pd) : nullptr;
   c.lay = A.layers + pd.layer_off;
   const int n = c.n, m = c.m, W = c.W;
   const int gamma = c.gamma, delta = c.delta, gD = gamma + delta;
@@ -351,7 +358,7 @@ __global__ void __launch_bounds__(WIDE_THREADS) fill_wide_linear_kernel(const De
         const int32_t* src = ok[t] ? c.lay + wide_dword(m, W, 1, pi, pj, pk - pi + S, pl - pj + S, 0) : out;
         pv[t] = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
-      const int mu1 = c.mu1(i, j), mu2 = c.mu2(k, l);
+      const int mu1 = c.template mu1<D1 != 0>(i, j), mu2 = c.mu2(k, l);
       bool any = false;
       int best = NEG;
 #pragma unroll

@@ -74,6 +74,8 @@ class Batch:
     ``s1`` / ``s2``: int32 score tables (k1 x k1, k2 x k2).
     ``mu2_dense``: optional list of int32 arrays, pair p's of shape (n_p, m_p) with entry
     [k-1, l-1] = mu2(k, l); replaces the class codes / ``s2`` (DENSE form of include/bialign.h).
+    ``mu1_dense``: likewise for the sequence scores, entry [i-1, j-1] = mu1(i, j) (position-specific
+    scores, e.g. a PSSM: ``scoring.dense_mu1_from_pssm``); replaces the sequence codes / ``s1``.
     ``score_only``: the batch will never be traced back (BIALIGN_BATCH_SCORE_ONLY): the sweep keeps
     only the rows the next strip needs; ``traces()`` / ``dump_layers()`` raise.
     ``lean_trace``: scores AND traces from that reduced storage (BIALIGN_BATCH_LEAN_TRACE): the
@@ -82,7 +84,7 @@ class Batch:
 
     def __init__(self, engine, mols_a, mols_b, s1, s2, gap_opening_cost, gap_cost, shift_cost,
                  max_shift, hbm_budget_bytes=0, recurrence=0, mu2_dense=None, score_only=False,
-                 lean_trace=False):
+                 lean_trace=False, mu1_dense=None):
         if mols_b is None and hasattr(mols_a, "seq_a"):  # a batch.FlatBatch: the arrays are the ABI's already
             fb = mols_a
             if not len(fb.len_a):
@@ -113,20 +115,13 @@ class Batch:
             raise ValueError("sequence code outside the S1 table")
         if cls_a.size and (cls_a.max() >= s2.shape[0] or cls_b.max() >= s2.shape[0]):
             raise ValueError("structure class outside the S2 table")
-        mu2_ptr, mu2_off_ptr = None, None
-        if mu2_dense is not None:
-            if len(mu2_dense) != self.npairs:
-                raise ValueError("mu2_dense needs one table per pair")
-            flat = []
-            for p, tab in enumerate(mu2_dense):
-                tab = np.ascontiguousarray(tab, dtype=np.int32)
-                if tab.shape != (int(self.len_a[p]), int(self.len_b[p])):
-                    raise ValueError(f"mu2_dense[{p}] must have shape (len A, len B)")
-                flat.append(tab.ravel())
-            mu2_off = np.zeros(self.npairs, dtype=np.int64)
-            mu2_off[1:] = np.cumsum([f.size for f in flat[:-1]])
-            mu2_flat = np.ascontiguousarray(np.concatenate(flat))
+        mu2_flat, mu2_off = self._dense_tables(mu2_dense, "mu2_dense")
+        mu1_flat, mu1_off = self._dense_tables(mu1_dense, "mu1_dense")
+        mu2_ptr = mu2_off_ptr = mu1_ptr = mu1_off_ptr = None
+        if mu2_flat is not None:
             mu2_ptr, mu2_off_ptr = _ptr(mu2_flat, ctypes.c_int32), _ptr(mu2_off, ctypes.c_int64)
+        if mu1_flat is not None:
+            mu1_ptr, mu1_off_ptr = _ptr(mu1_flat, ctypes.c_int32), _ptr(mu1_off, ctypes.c_int64)
         prm = _lib.Params(int(gap_opening_cost), int(gap_cost), int(shift_cost), int(max_shift),
                           int(recurrence), (_lib.BATCH_SCORE_ONLY if score_only else 0) |
                           (_lib.BATCH_LEAN_TRACE if lean_trace else 0))
@@ -134,13 +129,31 @@ class Batch:
         pr = _lib.Pairs(self.npairs, _ptr(self.len_a, ctypes.c_int32), _ptr(self.len_b, ctypes.c_int32),
                         _ptr(off_a, ctypes.c_int64), _ptr(off_b, ctypes.c_int64),
                         _ptr(seq_a, ctypes.c_uint8), _ptr(cls_a, ctypes.c_uint8),
-                        _ptr(seq_b, ctypes.c_uint8), _ptr(cls_b, ctypes.c_uint8), mu2_ptr, mu2_off_ptr)
+                        _ptr(seq_b, ctypes.c_uint8), _ptr(cls_b, ctypes.c_uint8), mu2_ptr, mu2_off_ptr,
+                        mu1_ptr, mu1_off_ptr)
         self._h = ctypes.c_void_p()
         check(lib.bialign_batch_create(engine._h, ctypes.byref(prm), ctypes.byref(sc), ctypes.byref(pr),
                                        int(hbm_budget_bytes), ctypes.byref(self._h)))
         engine._batches.add(self)
         self.info = self.current_info()
         self.affine = bool(self.info["affine"])
+
+    def _dense_tables(self, tables, name):
+        """One (len A, len B) integer table per pair -> (flat int32 array, int64 offsets), or (None, None)."""
+        if tables is None:
+            return None, None
+        if len(tables) != self.npairs:
+            raise ValueError(f"{name} needs one table per pair")
+        flat = []
+        for p, tab in enumerate(tables):
+            tab = np.asarray(tab)
+            if tab.shape != (int(self.len_a[p]), int(self.len_b[p])):
+                raise ValueError(f"{name}[{p}] must have shape (len A, len B) = "
+                                 f"({int(self.len_a[p])}, {int(self.len_b[p])}), got {tab.shape}")
+            flat.append(np.ascontiguousarray(tab, dtype=np.int32).ravel())
+        off = np.zeros(self.npairs, dtype=np.int64)
+        off[1:] = np.cumsum([f.size for f in flat[:-1]])
+        return np.ascontiguousarray(np.concatenate(flat)), off
 
     def current_info(self):
         """bialign_batch_get_info now (``info`` is the answer at creation; a fallback to full records may re-chunk)."""

@@ -193,3 +193,22 @@ def dense_mu2_from_features(mol_a, mol_b, structure_weight):
         terms.append(np.sqrt(prod))
     total = (terms[0] + terms[1]) + terms[2]
     return np.trunc(structure_weight * total).astype(np.int32)
+
+
+def dense_mu1_from_pssm(pssm, alphabet, seq_b):
+    """int32 (n, m) dense mu1 table of a position-specific score matrix of molecule A against the letters of
+    molecule B: entry [i-1, j-1] = pssm[i-1, alphabet.index(seq_b[j-1])] (i, j 1-based).  ``pssm`` is (n, len
+    alphabet), integer scores in the engine's scale (a ``--simmatrix`` table after its x100).  A letter of
+    ``seq_b`` outside ``alphabet`` raises ValueError."""
+    pssm = np.asarray(pssm)
+    if pssm.ndim != 2 or pssm.shape[1] != len(alphabet):
+        raise ValueError(f"pssm must have shape (len A, len alphabet) = (n, {len(alphabet)}), got {pssm.shape}")
+    if not np.issubdtype(pssm.dtype, np.integer):
+        raise ValueError("pssm must hold integers (scores already scaled, e.g. x100)")
+    index = {c: x for x, c in enumerate(alphabet)}
+    cols = []
+    for j, c in enumerate(seq_b):
+        if c not in index:
+            raise ValueError(f"letter {c!r} at position {j + 1} of molecule B is not in the alphabet")
+        cols.append(index[c])
+    return np.ascontiguousarray(pssm[:, np.asarray(cols, dtype=np.int64)], dtype=np.int32)

@@ -16,9 +16,9 @@
  * one.  Pairs are given in LOOKUP form:
  *     mu1(i,j) = s1[seq_a[i-1] * k1 + seq_b[j-1]]     (pyx:405-412, 435-436)
  *     mu2(k,l) = s2[cls_a[k-1] * k2 + cls_b[l-1]]     (pyx:414-429, 438-440)
- * with uint8 codes prepared by the host side (bialign_amd/scoring.py).
- *
- * or, for mu2 only, in DENSE form (bialign_pairs.mu2_dense).
+ * with uint8 codes prepared by the host side (bialign_amd/scoring.py),
+ * or, either of them or both, in DENSE form: one n x m table per pair
+ * (bialign_pairs.mu1_dense / mu2_dense), for scores that depend on position.
  *
  * The engine is GPU only.  There is no CPU fallback behind this ABI.
  */
@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define BIALIGN_ABI_VERSION 9
+#define BIALIGN_ABI_VERSION 10
 
 #define BIALIGN_OK 0
 #define BIALIGN_E_INVALID (-1)     /* bad argument (message says which) */
@@ -92,8 +92,8 @@ typedef struct bialign_params {
 
 /* Score tables, row-major, values already scaled (nonpyx:33: x100). */
 typedef struct bialign_scoring {
-  int32_t k1;        /* sequence alphabet size, 1..256 */
-  const int32_t* s1; /* k1*k1 */
+  int32_t k1;        /* sequence alphabet size, 1..256 (1 with a one-entry s1 when mu1 is DENSE) */
+  const int32_t* s1; /* k1*k1, unused when mu1 is DENSE */
   int32_t k2;        /* structure class count, 1..256 */
   const int32_t* s2; /* k2*k2 */
 } bialign_scoring;
@@ -116,6 +116,14 @@ typedef struct bialign_pairs {
    * cls_a / cls_b are then ignored (may be NULL). */
   const int32_t* mu2_dense;
   const int64_t* mu2_off;
+  /* Optional DENSE form of mu1 (NULL = LOOKUP form, ABI 10): position-specific sequence scores --
+   * a profile / PSSM of one molecule, scores derived from embeddings, per-position weights.  Pair
+   * p's table is mu1_dense[mu1_off[p] + (i-1)*m + (j-1)], i=1..n, j=1..m, values in the scale of
+   * s1 (x100); seq_a / seq_b and s1 are then ignored (seq_a / seq_b may be NULL, k1 may be 1).
+   * Works in every mode, alone or with dense mu2; mu1_dense without mu1_off is BIALIGN_E_INVALID,
+   * and tables whose magnitude could leave the int32 safety window are BIALIGN_E_RANGE. */
+  const int32_t* mu1_dense;
+  const int64_t* mu1_off;
 } bialign_pairs;
 
 typedef struct bialign_batch_info {
