@@ -85,6 +85,45 @@ def make_batch(pairs, params, engine=None, hbm_budget_bytes=0, recurrence=0, mu2
                  mu2_dense=mu2_dense, score_only=score_only, lean_trace=lean_trace, mu1_dense=mu1_dense)
 
 
+def make_feature_batch(molecules, pair_index, params, engine=None, hbm_budget_bytes=0, recurrence=0,
+                       score_only=False, lean_trace=False, mu1_dense=None):
+    """Batch with mu2 in FEATURE form (include/bialign.h, bialign_features): RNA molecules with real-valued
+    structure features, e.g. from predicted base-pair probabilities.  ``molecules``: a list of
+    ``(seq, (up, down, unp))``, three numbers per residue as ``scoring.rna_features`` makes them; ``pair_index``: a
+    list of ``(ia, ib)`` into it.  Every molecule is encoded, checked and uploaded once and the pairs point into it,
+    so an all-against-all batch costs O(sum of lengths) on the host; the GPU builds each chunk's score tables.
+    The structure weight is ``params["structure_weight"]``.  Bad arguments raise ValueError before the library is
+    called: an index outside ``molecules``, ragged or mis-sized feature arrays, a NaN or infinite feature, and
+    ValueError("math domain error") for a negative one."""
+    from .scoring import check_features
+    molecules = list(molecules)
+    pair_index = [(int(ia), int(ib)) for ia, ib in pair_index]
+    if not molecules or not pair_index:
+        raise ValueError("need at least one molecule and one pair")
+    for p, (ia, ib) in enumerate(pair_index):
+        if not (0 <= ia < len(molecules) and 0 <= ib < len(molecules)):
+            raise ValueError(f"pair {p}: molecule index ({ia}, {ib}) out of range (0..{len(molecules) - 1})")
+    seqs = [str(seq) for seq, _ in molecules]
+    feats = [check_features(f, len(seq), f"molecule {t}") for t, (seq, (_, f)) in enumerate(zip(seqs, molecules))]
+    model = ScoreModel(params, sequences=seqs, structures=["."])
+    lens = np.fromiter(map(len, seqs), dtype=np.int32, count=len(seqs))
+    offs = _offsets(lens)
+    ia, ib = (np.fromiter(x, dtype=np.int64, count=len(pair_index)) for x in zip(*pair_index))
+    fb = FlatBatch()
+    fb.len_a, fb.len_b = np.ascontiguousarray(lens[ia]), np.ascontiguousarray(lens[ib])
+    fb.off_a, fb.off_b = np.ascontiguousarray(offs[ia]), np.ascontiguousarray(offs[ib])
+    codes = [model.encode_sequence(x) for x in seqs]
+    fb.seq_a = fb.seq_b = np.ascontiguousarray(np.concatenate(codes))
+    fb.cls_a = fb.cls_b = np.zeros(len(fb.seq_a), dtype=np.uint8)  # (unused: the FEATURE form replaces the classes)
+    flat = tuple(np.ascontiguousarray(np.concatenate([f[x] for f in feats])) for x in range(3))
+    from .engine import Batch, default_engine  # loads the HIP library (no CPU fallback)
+    return Batch(engine or default_engine(), fb, None, model.s1, model.s2,
+                 params["gap_opening_cost"], params["gap_cost"], params["shift_cost"],
+                 params["max_shift"], hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence,
+                 score_only=score_only, lean_trace=lean_trace, mu1_dense=mu1_dense,
+                 mu2_features=(int(params["structure_weight"]), flat, flat))
+
+
 def shard(npairs, rank, world_size, costs=None):
     """Contiguous block of pair indices owned by ``rank`` (pairs are independent, so sharding
     needs no data-path collective).  Without ``costs`` the blocks hold equal numbers of pairs;

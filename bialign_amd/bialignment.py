@@ -21,6 +21,7 @@ from .molecule_io import read_simmatrix
 from .presentation import (consensus_sbpp, consensus_sequence, highlight_sequence_identity,  # noqa: F401
                            highlight_structure_identity, highlight_structure_similarity, mea,
                            parse_dotbracket)
+from . import scoring as _scoring
 from .scoring import ScoreModel
 
 __version__ = molecule_io.__version__
@@ -104,13 +105,7 @@ _LINEAR_OFFSETS = ((1, 1, 1, 1), (1, 0, 1, 0), (0, 1, 0, 1), (1, 1, 0, 0), (0, 0
                    (1, 0, 1, 1), (0, 1, 1, 1), (1, 1, 1, 0), (1, 1, 0, 1))  # pyx:233-248
 
 
-def _sequential_row_sums(mat):
-    """Row sums accumulated strictly left to right (ufunc.accumulate), i.e. the doubles Python's
-    sum() produces on this interpreter; numpy's .sum() adds pairwise and rounds differently."""
-    mat = np.asarray(mat, dtype=float)
-    if mat.shape[1] == 0:
-        return np.zeros(mat.shape[0])
-    return np.add.accumulate(mat, axis=1)[:, -1]
+_sequential_row_sums = _scoring.sequential_row_sums
 
 
 def _binary_features(mol):
@@ -170,32 +165,13 @@ class BiAligner:
     # ------------------------------------------------------- input preparation
     @staticmethod
     def _symmetrize_bpps(bpp):
-        """Upper-triangular pair probabilities -> symmetric matrix with unpaired
-        probabilities on the diagonal; 1-based (pyx:326-338)."""
-        n = len(bpp) - 1
-        upper = np.triu(np.asarray(bpp, dtype=float)[: n + 1, : n + 1], k=1)
-        upper[0, :] = 0.0
-        sym = upper + upper.T
-        # diagonal: 1.0 - (left-to-right sum of the row), the reference's Python sum() (pyx:335-336)
-        sym[np.arange(1, n + 1), np.arange(1, n + 1)] = 1.0 - _sequential_row_sums(sym[:, 1:])[1:]
-        return sym
+        """pyx:326-338 (scoring.symmetrize_bpps)."""
+        return _scoring.symmetrize_bpps(bpp)
 
     @staticmethod
     def _bp_matrix_from_fixed_structure(structure):
-        """0/1 pair matrix of a dot-bracket string, unpaired positions on the
-        diagonal; 1-based (pyx:378-392)."""
-        n = len(structure)
-        bpm = np.zeros((n + 1, n + 1), dtype="float")
-        pending = []
-        for pos, ch in enumerate(structure, start=1):
-            if ch == "(":
-                pending.append(pos)
-            elif ch == ")":
-                mate = pending.pop()
-                bpm[pos, mate] = bpm[mate, pos] = 1.0
-            else:
-                bpm[pos, pos] = 1.0
-        return bpm
+        """pyx:378-392 (scoring.bp_matrix_from_fixed_structure)."""
+        return _scoring.bp_matrix_from_fixed_structure(structure)
 
     @staticmethod
     def _expected_pairing(mol):
@@ -238,16 +214,10 @@ class BiAligner:
             if self._is_rna:
                 mol["sbpp"] = BiAligner._bp_matrix_from_fixed_structure(structure)
         if self._is_rna:
-            # features, 1-based with an ignored entry 0 (pyx:366-374): "up" sums the
-            # partners j <= i-2, "down" the partners j > i
-            # Sums run left to right like the reference's sum(): with real-valued probabilities
-            # the rounding order reaches mu2 through int() (pyx:416-423).
-            n, sbpp = mol["len"], np.asarray(mol["sbpp"], dtype=float)
-            col = np.arange(n + 1)
-            low = (col[None, :] >= 1) & (col[None, :] <= col[:, None] - 2)
-            mol["up"] = [float(v) for v in _sequential_row_sums(np.where(low, sbpp, 0.0))]
-            mol["down"] = [float(v) for v in _sequential_row_sums(np.where(col[None, :] > col[:, None], sbpp, 0.0))]
-            mol["unp"] = [1.0 - u - d for u, d in zip(mol["up"], mol["down"])]
+            # features, 1-based with an ignored entry 0 (pyx:366-374): scoring.features_from_sbpp, the code
+            # scoring.rna_features runs too
+            up, down, unp = _scoring.features_from_sbpp(mol["sbpp"], mol["len"])
+            mol["up"], mol["down"], mol["unp"] = ([float(v) for v in f] for f in (up, down, unp))
         return mol
 
     def _check_seq_table(self, table):
@@ -332,11 +302,13 @@ class BiAligner:
         if self._batch is not None:
             self._batch.close()
         device = int(self._params.get("device", os.environ.get("BIALIGN_DEVICE", 0)) or 0)
-        dense = None
+        features = None
         if self._is_rna and any(m.get("predicted") or not _binary_features(m) for m in (A, B)):
-            # predicted structures: the features are real numbers, mu2 goes to the engine as a table
-            from .scoring import dense_mu2_from_features
-            dense = [dense_mu2_from_features(A, B, self._params["structure_weight"])]
+            # predicted structures: the features are real numbers; they go to the engine as they are (FEATURE form of
+            # mu2) and the GPU builds the score table (scoring.dense_mu2_from_features is its host-side twin)
+            features = (int(self._params["structure_weight"]),
+                        [tuple(A[key][1:] for key in ("up", "down", "unp"))],
+                        [tuple(B[key][1:] for key in ("up", "down", "unp"))])
             cls_a = np.zeros(A["len"], dtype=np.uint8)
             cls_b = np.zeros(B["len"], dtype=np.uint8)
         else:
@@ -345,7 +317,7 @@ class BiAligner:
                             [(model.encode_sequence(A["seq"]), cls_a)],
                             [(model.encode_sequence(B["seq"]), cls_b)],
                             model.s1, model.s2, self.beta, self.gamma, self._params["shift_cost"],
-                            self.max_shift, recurrence=recurrence, mu2_dense=dense,
+                            self.max_shift, recurrence=recurrence, mu2_features=features,
                             mu1_dense=None if self._seq_table is None else [self._seq_table])
         self._batch.run()
         self._ran_affine = self._batch.affine

@@ -6,6 +6,8 @@
 // path exists here: if the device or a kernel is unavailable the call fails.
 #include "bialign_host.hpp"
 #include <cmath>
+#include <cstdint>
+#include <unordered_map>
 
 using namespace bialign;
 
@@ -387,31 +389,46 @@ int launch_dump_any(const bialign_batch* b, const DeviceBatch& v, int pid, int32
 // Cut the batch into chunks of at most budget_dw dwords of layer storage and lay the pairs of each chunk end to
 // end: as few chunks as the budget allows, of about equal size (an undersized last chunk would leave SIMDs
 // idle); inside a chunk the longest sweeps are launched first.
-int plan_chunks(bialign_batch* b, const std::vector<int64_t>& pair_dwords, int64_t budget_dw) {
+//   FEATURE-form batches: a pair's mu2 table (bialign_batch::tab_dwords) is per-chunk scratch in a buffer of its own
+// and counts toward the budget with the pair's layers; its tables lie end to end like the layers (PairDesc::tab_off).
+// layer_cap / tab_cap: a re-plan within buffers the batch already holds -- neither kind may outgrow its buffer.
+int plan_chunks(bialign_batch* b, const std::vector<int64_t>& pair_dwords, int64_t budget_dw, int64_t layer_cap = INT64_MAX,
+                int64_t tab_cap = INT64_MAX) {
   const int npairs = b->npairs;
+  const bool feat = b->feat;
+  auto tab_of = [&](int p) { return feat ? b->tab_dwords[p] : (int64_t)0; };
   b->order.resize(npairs);
   std::iota(b->order.begin(), b->order.end(), 0);
   b->chunk_begin.assign(1, 0);
   b->max_chunk_dwords = 0;
+  b->max_chunk_tab_dwords = 0;
   int64_t total_dw = 0;
   for (int p = 0; p < npairs; ++p) {
-    if (pair_dwords[p] > budget_dw)
-      return fail(BIALIGN_E_NOMEM, "pair %d needs %lld bytes of layers, budget is %lld", p,
-                  (long long)pair_dwords[p] * 4, (long long)budget_dw * 4);
-    total_dw += pair_dwords[p];
+    if (pair_dwords[p] + tab_of(p) > budget_dw)
+      return feat ? fail(BIALIGN_E_NOMEM, "pair %d needs %lld bytes of layers and %lld of mu2 table, budget is %lld", p,
+                         (long long)pair_dwords[p] * 4, (long long)tab_of(p) * 4, (long long)budget_dw * 4)
+                  : fail(BIALIGN_E_NOMEM, "pair %d needs %lld bytes of layers, budget is %lld", p,
+                         (long long)pair_dwords[p] * 4, (long long)budget_dw * 4);
+    total_dw += pair_dwords[p] + tab_of(p);
   }
   const int64_t want_chunks = (total_dw + budget_dw - 1) / budget_dw;
   const int64_t target_dw = std::min(budget_dw, (total_dw + want_chunks - 1) / want_chunks);
-  int64_t used = 0;
+  int64_t used = 0, used_tab = 0;  // layer dwords, table dwords of the chunk so far
   for (int p = 0; p < npairs; ++p) {
-    if (used > 0 && (used + pair_dwords[p] > budget_dw || used >= target_dw)) {
+    if (used + used_tab > 0 && (used + used_tab + pair_dwords[p] + tab_of(p) > budget_dw || used + used_tab >= target_dw ||
+                                used + pair_dwords[p] > layer_cap || used_tab + tab_of(p) > tab_cap)) {
       b->chunk_begin.push_back(p);
-      used = 0;
+      used = used_tab = 0;
     }
     b->pairs[p].scratch_off += used - b->pairs[p].layer_off;  // (relative to the pair's start until the first plan)
     b->pairs[p].layer_off = used;
     used += pair_dwords[p];
     b->max_chunk_dwords = std::max(b->max_chunk_dwords, used);
+    if (feat) {
+      b->pairs[p].tab_off = used_tab;
+      used_tab += tab_of(p);
+      b->max_chunk_tab_dwords = std::max(b->max_chunk_tab_dwords, used_tab);
+    }
   }
   b->chunk_begin.push_back(npairs);
   for (size_t c = 0; c + 1 < b->chunk_begin.size(); ++c)
@@ -433,7 +450,11 @@ int replan_full(bialign_batch* b) {
   HIP_TRY(hipStreamSynchronize(st));
   const int64_t need = *std::max_element(b->full_dwords.begin(), b->full_dwords.end());
   if ((int64_t)b->d_layers.n < need + 16) HIP_TRY(b->d_layers.alloc((size_t)need + 16));
-  if (int rc = plan_chunks(b, b->full_dwords, (int64_t)b->d_layers.n - 16)) return rc;
+  if (b->feat) {  // layers and tables each within the buffer they have: the batch's HBM use does not grow
+    if (int rc = plan_chunks(b, b->full_dwords, (int64_t)b->d_layers.n - 16 + (int64_t)b->d_tab.n, (int64_t)b->d_layers.n - 16,
+                             (int64_t)b->d_tab.n))
+      return rc;
+  } else if (int rc = plan_chunks(b, b->full_dwords, (int64_t)b->d_layers.n - 16)) return rc;
   HIP_TRY(hipMemcpy(b->d_pairs.p, b->pairs.data(), b->pairs.size() * sizeof(PairDesc), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(b->d_order.p, b->order.data(), b->order.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   return BIALIGN_OK;
@@ -503,8 +524,9 @@ void bialign_engine_destroy(bialign_engine* e) {
   delete e;
 }
 
-int bialign_batch_create(bialign_engine* eng, const bialign_params* prm, const bialign_scoring* sc,
-                         const bialign_pairs* pr, int64_t hbm_budget, bialign_batch** out) {
+// bialign_batch_create (ft == nullptr) and bialign_batch_create_features
+static int create_batch(bialign_engine* eng, const bialign_params* prm, const bialign_scoring* sc,
+                        const bialign_pairs* pr, const bialign_features* ft, int64_t hbm_budget, bialign_batch** out) {
   if (!eng || !prm || !sc || !pr || !out) return fail(BIALIGN_E_INVALID, "NULL argument");
   *out = nullptr;
   if (pr->npairs < 1) return fail(BIALIGN_E_INVALID, "npairs must be >= 1");
@@ -527,7 +549,9 @@ int bialign_batch_create(bialign_engine* eng, const bialign_params* prm, const b
   b->npairs = pr->npairs;
   b->k1 = sc->k1;
   b->k2 = sc->k2;
-  b->dense = pr->mu2_dense != nullptr;
+  b->feat = ft != nullptr;
+  b->dense = b->feat || pr->mu2_dense != nullptr;  // (the FEATURE form's tables feed the DENSE consumers)
+  if (b->feat) b->feat_sw = ft->structure_weight;
   b->dense1 = pr->mu1_dense != nullptr;
   b->lean_trace = (prm->flags & BIALIGN_BATCH_LEAN_TRACE) != 0;
   b->lean = b->lean_trace || (prm->flags & BIALIGN_BATCH_SCORE_ONLY) != 0;
@@ -537,7 +561,7 @@ int bialign_batch_create(bialign_engine* eng, const bialign_params* prm, const b
   if (b->wide && b->lean && (b->lean_trace || !b->affine))
     return fail(BIALIGN_E_UNSUPPORTED, "LEAN_TRACE, and SCORE_ONLY of the non-affine recurrence, exist for max_shift <= %d only",
                 BIALIGN_MAX_SHIFT_TILED);
-  if (b->dense && !pr->mu2_off) return fail(BIALIGN_E_INVALID, "mu2_dense given without mu2_off");
+  if (b->dense && !b->feat && !pr->mu2_off) return fail(BIALIGN_E_INVALID, "mu2_dense given without mu2_off");
   if (!b->dense && (!pr->cls_a || !pr->cls_b)) return fail(BIALIGN_E_INVALID, "cls_a / cls_b are NULL (LOOKUP form)");
   if (b->dense1 && !pr->mu1_off) return fail(BIALIGN_E_INVALID, "mu1_dense given without mu1_off");
   if (!b->dense1 && (!pr->seq_a || !pr->seq_b)) return fail(BIALIGN_E_INVALID, "seq_a / seq_b are NULL (LOOKUP form)");
@@ -558,7 +582,42 @@ int bialign_batch_create(bialign_engine* eng, const bialign_params* prm, const b
     }
     return mx;
   };
-  if (b->dense) bmax = dense_max(pr->mu2_dense, pr->mu2_off);   // dense mu2: the bound comes from the tables themselves
+  if (b->dense && !b->feat) bmax = dense_max(pr->mu2_dense, pr->mu2_off);   // dense mu2: the bound comes from the tables themselves
+  if (b->feat) {  // FEATURE form: every number finite and >= 0; the bound from the molecules' largest features
+    struct MolMax { int32_t len; double up, down, unp; };
+    std::unordered_map<int64_t, MolMax> seen[2];  // per side: start offset -> what was checked there (molecules are shared)
+    auto check = [&](int side, int p, int64_t off, int32_t len, const double* up, const double* down, const double* unp,
+                     const MolMax** res) {
+      MolMax& mm = seen[side][off];
+      if (mm.len < len) {
+        const double* arr[3] = {up, down, unp};
+        static const char* const names[3] = {"up", "down", "unp"};
+        double mx[3] = {0, 0, 0};
+        for (int f = 0; f < 3; ++f)
+          for (int32_t r = 0; r < len; ++r) {
+            const double x = arr[f][off + r];
+            if (!(x >= 0.0) || std::isinf(x))  // (NaN fails the comparison)
+              return fail(BIALIGN_E_INVALID, "pair %d: feature %s_%c at position %d is %g: features must be finite and >= 0", p,
+                          names[f], side ? 'b' : 'a', r + 1, x);
+            mx[f] = std::max(mx[f], x);
+          }
+        mm = MolMax{len, mx[0], mx[1], mx[2]};
+      }
+      *res = &mm;
+      return BIALIGN_OK;
+    };
+    bmax = 0;
+    for (int p = 0; p < pr->npairs; ++p) {
+      const MolMax *ma = nullptr, *mb = nullptr;
+      if (int rc = check(0, p, pr->off_a[p], std::max(pr->len_a[p], 0), ft->up_a, ft->down_a, ft->unp_a, &ma)) return rc;
+      if (int rc = check(1, p, pr->off_b[p], std::max(pr->len_b[p], 0), ft->up_b, ft->down_b, ft->unp_b, &mb)) return rc;
+      const double bound = std::fabs((double)ft->structure_weight) *
+                           (std::sqrt(ma->up * mb->up) + std::sqrt(ma->down * mb->down) + std::sqrt(ma->unp * mb->unp));
+      if (!(bound < 1073741824.0))  // 2^30: outside any window, and an int64 could not hold much more
+        return fail(BIALIGN_E_RANGE, "pair %d: structure scores may leave the int32 safety window (bound %g)", p, bound);
+      bmax = std::max<int64_t>(bmax, (int64_t)std::ceil(bound));
+    }
+  }
   if (b->dense1) amax = dense_max(pr->mu1_dense, pr->mu1_off);  // ... and so for dense mu1
   const int64_t colmax = amax + bmax + 2 * (std::llabs((long long)prm->gap_cost) + std::llabs((long long)prm->gap_opening_cost)) +
                          2 * std::llabs((long long)prm->shift_cost);
@@ -582,8 +641,9 @@ int bialign_batch_create(bialign_engine* eng, const bialign_params* prm, const b
     d.seq_a = pr->off_a[p];
     d.seq_b = pr->off_b[p];
     d.trace_off = b->trace_bytes;
-    d.tab_off = tot_tab;  // dense forms: the pair's tables, end to end (mu2's, then mu1's)
+    d.tab_off = tot_tab;  // dense forms: the pair's tables, end to end (mu2's, then mu1's); FEATURE form: plan_chunks
     tot_tab += (int64_t)n * m * ((b->dense ? 1 : 0) + (b->dense1 ? 1 : 0));
+    if (b->feat) b->tab_dwords.push_back((int64_t)n * m * (b->dense1 ? 2 : 1));
     b->trace_bytes += d.trace_cap;
     b->cells += cells_of(n, m, S);
     tot_a = std::max<int64_t>(tot_a, pr->off_a[p] + n);
@@ -631,6 +691,7 @@ int bialign_batch_create(bialign_engine* eng, const bialign_params* prm, const b
   size_t free_b = 0, total_b = 0;
   HIP_TRY(hipMemGetInfo(&free_b, &total_b));
   free_b += (eng->layer_cache.n + eng->layer_cache2.n) * sizeof(int32_t);  // reused or released below, ours either way
+  if (b->feat) free_b += eng->tab_cache.n * sizeof(int32_t);               // ... and so the cached table buffer
   int64_t budget = hbm_budget > 0 ? hbm_budget : (int64_t)(free_b * 0.85);
   budget = std::min<int64_t>(budget, (int64_t)(free_b * 0.95));
   const int64_t budget_dw = budget / 4;
@@ -653,6 +714,12 @@ int bialign_batch_create(bialign_engine* eng, const bialign_params* prm, const b
         pair_dwords[p] = pack_info(S).pair_dwords(d.G, d.P, d.m);
     }
   };
+  // what the largest pair needs inside the budget: its layers, and in FEATURE form its mu2 table
+  auto max_need = [&]() {
+    int64_t mx = 0;
+    for (int p = 0; p < pr->npairs; ++p) mx = std::max(mx, pair_dwords[p] + (b->feat ? b->tab_dwords[p] : 0));
+    return mx;
+  };
   // lean traceback: few pairs -> several strips per round (they re-sweep in parallel), as memory allows
   auto pick_resw_k = [&]() {
     // as many strips per round as keep ~2048 waves busy -- re-sweeps of different strips are independent, so a
@@ -662,7 +729,7 @@ int bialign_batch_create(bialign_engine* eng, const bialign_params* prm, const b
     for (const PairDesc& d : b->pairs) ns_max = std::max(ns_max, d.NS);
     b->resw_k = (int)std::min<int64_t>(std::min<int64_t>(256, std::max(1, ns_max / 4)), std::max<int64_t>(1, 2048 / pr->npairs));
     if (const char* e = getenv("BIALIGN_RESW_K")) b->resw_k = std::min(256, std::max(1, atoi(e)));  // tests
-    for (size_pairs(); b->resw_k > 1 && *std::max_element(pair_dwords.begin(), pair_dwords.end()) > budget_dw; size_pairs())
+    for (size_pairs(); b->resw_k > 1 && max_need() > budget_dw; size_pairs())
       b->resw_k /= 2;
   };
   if (b->lean_trace) pick_resw_k();
@@ -671,15 +738,14 @@ int bialign_batch_create(bialign_engine* eng, const bialign_params* prm, const b
   // (memory-lean traceback, ~1.3x the time).
   if (b->pack) {  // the fallback to full records must be possible within the same budget
     int64_t full_max = 0;
-    for (const PairDesc& d : b->pairs)
-      full_max = std::max(full_max, (int64_t)d.G * pack_info(S).full_recdw);
-    if (std::max(full_max, *std::max_element(pair_dwords.begin(), pair_dwords.end())) > budget_dw) {
+    for (int p = 0; p < pr->npairs; ++p)
+      full_max = std::max(full_max, (int64_t)b->pairs[p].G * pack_info(S).full_recdw + (b->feat ? b->tab_dwords[p] : 0));
+    if (std::max(full_max, max_need()) > budget_dw) {
       b->pack = false;
       size_pairs();
     }
   }
-  if (!b->lean && !b->wide &&
-      *std::max_element(pair_dwords.begin(), pair_dwords.end()) > budget_dw) {
+  if (!b->lean && !b->wide && max_need() > budget_dw) {
     b->lean = b->lean_trace = true;
     b->pack = false;
     pick_resw_k();
@@ -716,11 +782,27 @@ int bialign_batch_create(bialign_engine* eng, const bialign_params* prm, const b
     (void)hipGetLastError();
     b->d_layers.p = nullptr;
     b->d_layers.n = 0;
-    const int64_t smaller = (int64_t)b->max_chunk_dwords * 3 / 4;
-    if (attempt >= 3 || smaller < *std::max_element(pair_dwords.begin(), pair_dwords.end()))
+    const int64_t smaller = (int64_t)(b->max_chunk_dwords + b->max_chunk_tab_dwords) * 3 / 4;
+    if (attempt >= 3 || smaller < max_need())
       return fail(BIALIGN_E_DEVICE, "hipMalloc of %zu bytes of layer storage failed: %s", layer_dw * 4, hipGetErrorString(err));
     for (PairDesc& d : b->pairs) d.scratch_off -= d.layer_off, d.layer_off = 0;  // back to pair-relative, as before the first plan
     if (int rc = plan_chunks(b.get(), pair_dwords, smaller)) return rc;
+  }
+
+  // ---- FEATURE form: the table buffer of the largest chunk, the engine's cached one if that is large enough
+  if (b->feat) {
+    const size_t tab_dw = (size_t)b->max_chunk_tab_dwords;
+    if (eng->tab_cache.p && eng->tab_cache.n >= tab_dw) {
+      b->d_tab.swap(eng->tab_cache);
+    } else {
+      eng->tab_cache.release();
+      if (b->d_tab.alloc(tab_dw) != hipSuccess) {
+        const hipError_t err = hipGetLastError();
+        b->d_tab.p = nullptr;
+        b->d_tab.n = 0;
+        return fail(BIALIGN_E_DEVICE, "hipMalloc of %zu bytes of mu2 table storage failed: %s", tab_dw * 4, hipGetErrorString(err));
+      }
+    }
   }
 
   // ---- upload (own stream: a batch can be prepared while another one sweeps)
@@ -736,7 +818,29 @@ int bialign_batch_create(bialign_engine* eng, const bialign_params* prm, const b
   HIP_TRY(b->d_seq_b.upload(b->dense1 ? zeros.data() : pr->seq_b, tot_b, st));
   HIP_TRY(b->d_cls_b.upload(b->dense ? zeros.data() : pr->cls_b, tot_b, st));
   std::vector<int32_t> tabs;
-  if (b->dense || b->dense1) {  // the pairs' tables end to end (PairDesc::tab_off): mu2's, then mu1's
+  std::vector<int64_t> mu1_offs;
+  if (b->feat) {  // the molecules' features, three planes per side; a dense mu1's tables resident, pair after pair
+    b->feat_tot_a = tot_a;
+    b->feat_tot_b = tot_b;
+    const double* src_a[3] = {ft->up_a, ft->down_a, ft->unp_a};
+    const double* src_b[3] = {ft->up_b, ft->down_b, ft->unp_b};
+    HIP_TRY(b->d_feat_a.alloc(3 * (size_t)tot_a));
+    HIP_TRY(b->d_feat_b.alloc(3 * (size_t)tot_b));
+    for (int f = 0; f < 3; ++f) {
+      HIP_TRY(hipMemcpyAsync(b->d_feat_a.p + (size_t)f * tot_a, src_a[f], (size_t)tot_a * sizeof(double), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(b->d_feat_b.p + (size_t)f * tot_b, src_b[f], (size_t)tot_b * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    if (b->dense1) {
+      mu1_offs.resize(pr->npairs);
+      size_t tot1 = 0;
+      for (int p = 0; p < pr->npairs; ++p) mu1_offs[p] = (int64_t)tot1, tot1 += (size_t)pr->len_a[p] * pr->len_b[p];
+      tabs.resize(tot1);
+      for (int p = 0; p < pr->npairs; ++p)
+        std::memcpy(tabs.data() + mu1_offs[p], pr->mu1_dense + pr->mu1_off[p], (size_t)pr->len_a[p] * pr->len_b[p] * sizeof(int32_t));
+      HIP_TRY(b->d_mu1.upload(tabs.data(), tabs.size(), st));
+      HIP_TRY(b->d_mu1_off.upload(mu1_offs.data(), mu1_offs.size(), st));
+    }
+  } else if (b->dense || b->dense1) {  // the pairs' tables end to end (PairDesc::tab_off): mu2's, then mu1's
     tabs.resize((size_t)tot_tab);
     for (int p = 0; p < pr->npairs; ++p) {
       const size_t nm = (size_t)pr->len_a[p] * pr->len_b[p];
@@ -776,6 +880,21 @@ int bialign_batch_create(bialign_engine* eng, const bialign_params* prm, const b
   return BIALIGN_OK;
 }
 
+int bialign_batch_create(bialign_engine* eng, const bialign_params* prm, const bialign_scoring* sc,
+                         const bialign_pairs* pr, int64_t hbm_budget, bialign_batch** out) {
+  return create_batch(eng, prm, sc, pr, nullptr, hbm_budget, out);
+}
+
+int bialign_batch_create_features(bialign_engine* eng, const bialign_params* prm, const bialign_scoring* sc,
+                                  const bialign_pairs* pr, const bialign_features* ft, int64_t hbm_budget,
+                                  bialign_batch** out) {
+  if (out) *out = nullptr;
+  if (!ft) return fail(BIALIGN_E_INVALID, "feat is NULL");
+  if (!ft->up_a || !ft->down_a || !ft->unp_a || !ft->up_b || !ft->down_b || !ft->unp_b)
+    return fail(BIALIGN_E_INVALID, "a feature array is NULL");
+  return create_batch(eng, prm, sc, pr, ft, hbm_budget, out);
+}
+
 void bialign_batch_destroy(bialign_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->eng->device);
@@ -786,6 +905,10 @@ void bialign_batch_destroy(bialign_batch* b) {
     DevBuf<int32_t>* slot = !eng->layer_cache.p ? &eng->layer_cache : (!eng->layer_cache2.p ? &eng->layer_cache2 : nullptr);
     if (!slot) slot = eng->layer_cache.n <= eng->layer_cache2.n ? &eng->layer_cache : &eng->layer_cache2;
     if (!slot->p || b->d_layers.n > slot->n) slot->swap(b->d_layers);
+  }
+  if (b->feat && b->d_tab.p && !eng->closing) {  // ... and so the table buffer (the stream is idle here or was never used)
+    (void)hipStreamSynchronize(eng->stream);
+    if (!eng->tab_cache.p || b->d_tab.n > eng->tab_cache.n) eng->tab_cache.swap(b->d_tab);
   }
   delete b;
   if (--eng->live_batches == 0 && eng->closing) bialign_engine_destroy(eng);
@@ -843,6 +966,7 @@ int bialign_engine_trim(bialign_engine* e) {
   HIP_TRY(hipSetDevice(e->device));
   e->layer_cache.release();
   e->layer_cache2.release();
+  e->tab_cache.release();
   return BIALIGN_OK;
 }
 
@@ -876,10 +1000,26 @@ static int enqueue_run(bialign_batch* b, uint32_t flags) {
     HIP_TRY(hipEventCreate(&e));
     b->evs.push_back(e);
   }
+  while (b->feat && (int)b->build_evs.size() < 2 * nchunks) {
+    hipEvent_t e = nullptr;
+    HIP_TRY(hipEventCreate(&e));
+    b->build_evs.push_back(e);
+  }
+  b->build_ms = 0;
+  b->build_launches = 0;
   HIP_TRY(hipStreamWaitEvent(st, b->uploaded, 0));
   HIP_TRY(hipMemsetAsync(b->d_err.p, 0, sizeof(int32_t), st));  // the flag is per run
   for (int c = 0; c < nchunks; ++c) {  // stream order keeps chunk c's traceback ahead of chunk c+1's sweep
     const int first = b->chunk_begin[c], count = b->chunk_begin[c + 1] - first;
+    if (b->feat) {
+      // FEATURE form: the chunk's mu2 tables, built into the table buffer ahead of the sweep (timed on its own, outside
+      // fill_ms).  They stay until the next chunk's build, which stream order puts behind this chunk's tracebacks -- every
+      // lean re-sweep round included -- so no round has to build them again.
+      HIP_TRY(hipEventRecord(b->build_evs[2 * c], st));
+      if (int rc = launch_build_mu2(b, first, count)) return rc;
+      HIP_TRY(hipEventRecord(b->build_evs[2 * c + 1], st));
+      ++b->build_launches;
+    }
     HIP_TRY(hipEventRecord(b->evs[3 * c], st));
     int rc = launch_fill(b, v, first, count);
     if (rc) return rc;
@@ -917,6 +1057,10 @@ int bialign_batch_wait(bialign_batch* b) {
       HIP_TRY(hipEventElapsedTime(&t, b->evs[3 * c + 1], b->evs[3 * c + 2]));
       b->timing.fill_ms += f;
       b->timing.traceback_ms += t;
+      if (b->feat) {
+        HIP_TRY(hipEventElapsedTime(&f, b->build_evs[2 * c], b->build_evs[2 * c + 1]));
+        b->build_ms += f;
+      }
     }
     int32_t err = 0;
     HIP_TRY(hipMemcpy(&err, b->d_err.p, sizeof err, hipMemcpyDeviceToHost));
@@ -1000,7 +1144,8 @@ int bialign_batch_dump_layers(bialign_batch* b, int32_t pair, int32_t* out) {
   DeviceBatch v = b->view();
   HIP_TRY(hipMemsetAsync(b->d_err.p, 0, sizeof(int32_t), st));
   b->used_xcu = b->used_pack = false;
-  int rc = launch_fill(b, v, pos, 1);
+  int rc = launch_build_mu2(b, pos, 1);  // FEATURE form: the table buffer may hold another chunk's tables by now
+  if (rc == BIALIGN_OK) rc = launch_fill(b, v, pos, 1);
   if (rc) return rc;
   if ((b->used_xcu && !b->no_xcu) || (b->used_pack && !b->pack_failed)) {  // forms a launch can fall back from, as in a run
     HIP_TRY(hipStreamSynchronize(st));
@@ -1018,7 +1163,8 @@ int bialign_batch_dump_layers(bialign_batch* b, int32_t pair, int32_t* out) {
       }
       ++b->recovered;
       HIP_TRY(hipMemsetAsync(b->d_err.p, 0, sizeof(int32_t), st));
-      rc = launch_fill(b, v, pos, 1);
+      rc = launch_build_mu2(b, pos, 1);  // (a re-plan moved the pair's table)
+      if (rc == BIALIGN_OK) rc = launch_fill(b, v, pos, 1);
       if (rc) return rc;
     }
   }
@@ -1033,6 +1179,37 @@ int bialign_batch_dump_layers(bialign_batch* b, int32_t pair, int32_t* out) {
   HIP_TRY(hipStreamSynchronize(st));
   // scores and traces live in their own buffers and stay valid; only the layer region was rewritten
   return check_device_error(b);
+}
+
+int bialign_batch_dump_mu2(bialign_batch* b, int32_t pair, int32_t* out) {
+  if (!b || !out) return fail(BIALIGN_E_INVALID, "NULL argument");
+  if (pair < 0 || pair >= b->npairs) return fail(BIALIGN_E_INVALID, "pair %d out of range", pair);
+  if (!b->dense) return fail(BIALIGN_E_INVALID, "mu2 of this batch is in LOOKUP form: there is no table to dump");
+  if (int rc = bialign_batch_wait(b)) return rc;
+  HIP_TRY(hipSetDevice(b->eng->device));
+  hipStream_t st = b->eng->stream;
+  HIP_TRY(hipStreamWaitEvent(st, b->uploaded, 0));
+  if (b->feat) {  // build the pair's table in its place in the chunk buffer (results of a run live elsewhere)
+    const int pos = (int)(std::find(b->order.begin(), b->order.end(), pair) - b->order.begin());
+    if (int rc = launch_build_mu2(b, pos, 1)) return rc;
+  }
+  const PairDesc& d = b->pairs[pair];
+  HIP_TRY(hipMemcpyAsync(out, b->d_tab.p + d.tab_off, (size_t)d.n * d.m * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return BIALIGN_OK;
+}
+
+int bialign_batch_get_feature_info(const bialign_batch* b, bialign_feature_info* info) {
+  if (!b || !info) return fail(BIALIGN_E_INVALID, "NULL argument");
+  if (int rc = bialign_batch_wait(const_cast<bialign_batch*>(b))) return rc;
+  info->form = b->feat ? BIALIGN_MU2_FEATURE : (b->dense ? BIALIGN_MU2_DENSE : BIALIGN_MU2_LOOKUP);
+  info->build_launches = b->build_launches;
+  int64_t dense_dw = 0;  // DENSE: every pair's mu2 table is resident
+  if (b->dense && !b->feat)
+    for (const PairDesc& d : b->pairs) dense_dw += (int64_t)d.n * d.m;
+  info->table_bytes = 4 * (b->feat ? b->max_chunk_tab_dwords : dense_dw);
+  info->build_ms = b->build_ms;
+  return BIALIGN_OK;
 }
 
 }  // extern "C"

@@ -89,6 +89,7 @@ struct bialign_engine {
   bool closing = false;   // bialign_engine_destroy was called while batches were alive: the last one finishes the job
   DevBuf<int32_t> layer_cache;
   DevBuf<int32_t> layer_cache2;  // second slot: filled only when two batches were alive at once (pipelined use)
+  DevBuf<int32_t> tab_cache;     // FEATURE-form batches: the per-chunk mu2 table buffer of the last one, kept likewise
 };
 
 struct bialign_batch {
@@ -133,7 +134,20 @@ struct bialign_batch {
   DevBuf<int32_t> d_tab;  // dense forms: all pairs' n x m tables (per pair mu2's, then mu1's; PairDesc::tab_off)
   DevBuf<int32_t> d_wide_ring;  // wide-band affine sweep: derived values of the last levels (bialign_wide.hpp)
   DevBuf<int64_t> d_wide_off;   // ... per pair of a launch: offset of its ring
-  bool dense = false;       // mu2 in DENSE form
+  bool dense = false;       // mu2 in DENSE form (also set for the FEATURE form: its consumers are the DENSE ones)
+  // FEATURE form of mu2 (bialign_batch_create_features, bialign_mu2_build.hpp): per-residue doubles in HBM, d_tab is
+  // per-chunk scratch the builder kernel fills ahead of each chunk's sweep; PairDesc::tab_off is chunk-relative.
+  bool feat = false;
+  int32_t feat_sw = 0;
+  DevBuf<double> d_feat_a, d_feat_b;   // three planes each (up, down, unp), feat_tot_a / feat_tot_b doubles per plane
+  int64_t feat_tot_a = 0, feat_tot_b = 0;
+  std::vector<int64_t> tab_dwords;     // per pair: table dwords in the chunk buffer (n*m; twice with a dense mu1 riding along)
+  int64_t max_chunk_tab_dwords = 0;    // table dwords of the largest chunk
+  DevBuf<int32_t> d_mu1;               // a dense mu1 next to feature mu2: its tables stay resident here, pair after pair,
+  DevBuf<int64_t> d_mu1_off;           // ... and the builder copies a chunk's behind the mu2 tables it writes
+  std::vector<hipEvent_t> build_evs;   // two per chunk, around the builder's launch
+  double build_ms = 0;                 // HIP-event time of the builder launches of the last run (not part of fill_ms)
+  int build_launches = 0;
   bool dense1 = false;      // mu1 in DENSE form (kernels with DENSE1 / D1 set; no packed records, no slim or diet sweeps)
   bool wide = false;        // max_shift above the tiled kernels: anti-diagonal path (bialign_wide.hpp), reference-order layers
   bool lean = false;        // LEAN records: the sweep keeps only the strip-bottom rows
@@ -148,6 +162,8 @@ struct bialign_batch {
   hipEvent_t uploaded = nullptr;                // inputs are in HBM (recorded on the copy stream)
   ~bialign_batch() {
     for (hipEvent_t e : evs)
+      if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : build_evs)
       if (e) (void)hipEventDestroy(e);
     if (uploaded) (void)hipEventDestroy(uploaded);
   }
@@ -203,6 +219,10 @@ inline bool diet8_available(const bialign_batch* b) {  // the eight-wave s=2 aff
 // the whole device's wave slots): the stream waits for the previous such launch, the new one is recorded.
 int xcu_serial_begin(bialign_engine* e);
 int xcu_serial_end(bialign_engine* e);
+
+// FEATURE form of mu2: build the tables of pairs order[first .. first+count) into the chunk's table buffer, on the
+// engine's stream (bialign_mu2_build.hip).  The pairs' tab_off must be the device's.
+int launch_build_mu2(bialign_batch* b, int first, int count);
 
 template <int S, bool BETA_NONPOS, int TW, bool XCU, bool DENSE = false, bool LEAN = false, bool PACK = false,
           bool DENSE1 = false>

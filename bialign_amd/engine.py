@@ -80,11 +80,20 @@ class Batch:
     only the rows the next strip needs; ``traces()`` / ``dump_layers()`` raise.
     ``lean_trace``: scores AND traces from that reduced storage (BIALIGN_BATCH_LEAN_TRACE): the
     traceback re-sweeps one strip at a time; for pairs whose full layers would not fit in HBM.
+    ``mu2_features``: ``(structure_weight, feats_a, feats_b)``, mu2 in FEATURE form (include/bialign.h,
+    bialign_features): the RNA structure score of real-valued per-residue features (predicted structures), whose
+    n x m tables the GPU builds itself, chunk by chunk.  With molecule lists ``feats_a[p]`` / ``feats_b[p]`` is
+    pair p's ``(up, down, unp)`` (``scoring.rna_features``); with a ``batch.FlatBatch`` they are triples of flat
+    float64 arrays indexed like ``seq_a`` / ``seq_b``, so that pairs may share molecules
+    (``batch.make_feature_batch``).  Replaces the class codes / ``s2``; excludes ``mu2_dense``.
     """
 
     def __init__(self, engine, mols_a, mols_b, s1, s2, gap_opening_cost, gap_cost, shift_cost,
                  max_shift, hbm_budget_bytes=0, recurrence=0, mu2_dense=None, score_only=False,
-                 lean_trace=False, mu1_dense=None):
+                 lean_trace=False, mu1_dense=None, mu2_features=None):
+        if mu2_features is not None and mu2_dense is not None:
+            raise ValueError("mu2_features and mu2_dense exclude each other")
+        flat = mols_b is None and hasattr(mols_a, "seq_a")
         if mols_b is None and hasattr(mols_a, "seq_a"):  # a batch.FlatBatch: the arrays are the ABI's already
             fb = mols_a
             if not len(fb.len_a):
@@ -115,6 +124,7 @@ class Batch:
             raise ValueError("sequence code outside the S1 table")
         if cls_a.size and (cls_a.max() >= s2.shape[0] or cls_b.max() >= s2.shape[0]):
             raise ValueError("structure class outside the S2 table")
+        feat = None if mu2_features is None else self._features(mu2_features, flat, len(seq_a), len(seq_b), off_a, off_b)
         mu2_flat, mu2_off = self._dense_tables(mu2_dense, "mu2_dense")
         mu1_flat, mu1_off = self._dense_tables(mu1_dense, "mu1_dense")
         mu2_ptr = mu2_off_ptr = mu1_ptr = mu1_off_ptr = None
@@ -132,11 +142,38 @@ class Batch:
                         _ptr(seq_b, ctypes.c_uint8), _ptr(cls_b, ctypes.c_uint8), mu2_ptr, mu2_off_ptr,
                         mu1_ptr, mu1_off_ptr)
         self._h = ctypes.c_void_p()
-        check(lib.bialign_batch_create(engine._h, ctypes.byref(prm), ctypes.byref(sc), ctypes.byref(pr),
-                                       int(hbm_budget_bytes), ctypes.byref(self._h)))
+        if feat is None:
+            check(lib.bialign_batch_create(engine._h, ctypes.byref(prm), ctypes.byref(sc), ctypes.byref(pr),
+                                           int(hbm_budget_bytes), ctypes.byref(self._h)))
+        else:
+            sw, fa, fb = feat
+            ft = _lib.Features(sw, *(_ptr(x, ctypes.c_double) for x in fa + fb))
+            check(lib.bialign_batch_create_features(engine._h, ctypes.byref(prm), ctypes.byref(sc), ctypes.byref(pr),
+                                                    ctypes.byref(ft), int(hbm_budget_bytes), ctypes.byref(self._h)))
         engine._batches.add(self)
         self.info = self.current_info()
         self.affine = bool(self.info["affine"])
+
+    def _features(self, mu2_features, flat, tot_a, tot_b, off_a, off_b):
+        """``mu2_features`` -> (int structure weight, three flat float64 arrays for side A, three for side B),
+        validated as the C ABI validates them (scoring.check_features) before the library is called."""
+        from .scoring import check_features
+        try:
+            sw, feats_a, feats_b = mu2_features
+        except (TypeError, ValueError):
+            raise ValueError("mu2_features must be (structure_weight, feats_a, feats_b)") from None
+        if int(sw) != sw:
+            raise ValueError("structure_weight must be an integer")
+        sides = []
+        for side, feats, tot, lens in (("A", feats_a, tot_a, self.len_a), ("B", feats_b, tot_b, self.len_b)):
+            if flat:
+                sides.append(check_features(feats, tot, f"molecules {side}"))
+                continue
+            if len(feats) != self.npairs:
+                raise ValueError(f"mu2_features needs one (up, down, unp) per pair for side {side}")
+            per = [check_features(f, int(lens[p]), f"pair {p}, molecule {side}") for p, f in enumerate(feats)]
+            sides.append(tuple(np.ascontiguousarray(np.concatenate([f[x] for f in per])) for x in range(3)))
+        return int(sw), sides[0], sides[1]
 
     def _dense_tables(self, tables, name):
         """One (len A, len B) integer table per pair -> (flat int32 array, int64 offsets), or (None, None)."""
@@ -160,6 +197,23 @@ class Batch:
         info = _lib.BatchInfo()
         check(lib.bialign_batch_get_info(self._h, ctypes.byref(info)))
         return {k: getattr(info, k) for k, _ in info._fields_}
+
+    def feature_info(self):
+        """bialign_batch_get_feature_info: the form mu2 came in ("lookup", "dense", "feature"), the table bytes (of the
+        largest chunk in FEATURE form), and the table builder's kernel time and launches of the last run."""
+        fi = _lib.FeatureInfo()
+        check(lib.bialign_batch_get_feature_info(self._h, ctypes.byref(fi)))
+        return dict(form=("lookup", "dense", "feature")[fi.form], table_bytes=fi.table_bytes,
+                    build_ms=fi.build_ms, build_launches=fi.build_launches)
+
+    def dump_mu2(self, pair):
+        """The (len A, len B) int32 mu2 table of one pair as the sweep reads it (DENSE or FEATURE form)."""
+        fn = getattr(lib, "bialign_batch_dump_mu2", None)
+        if fn is None:
+            raise _lib.BialignError(_lib.E_UNSUPPORTED, "this build of the library has no bialign_batch_dump_mu2")
+        out = np.empty((int(self.len_a[pair]), int(self.len_b[pair])), dtype=np.int32)
+        check(fn(self._h, int(pair), _ptr(out, ctypes.c_int32)))
+        return out
 
     def close(self):
         if getattr(self, "_h", None):

@@ -179,6 +179,102 @@ class ScoreModel:
         return int(self.s2[cls_a, cls_b])
 
 
+def sequential_row_sums(mat):
+    """Row sums accumulated strictly left to right (ufunc.accumulate), i.e. the doubles Python's
+    sum() produces on this interpreter; numpy's .sum() adds pairwise and rounds differently."""
+    mat = np.asarray(mat, dtype=float)
+    if mat.shape[1] == 0:
+        return np.zeros(mat.shape[0])
+    return np.add.accumulate(mat, axis=1)[:, -1]
+
+
+def symmetrize_bpps(bpp):
+    """Upper-triangular pair probabilities -> symmetric matrix with unpaired
+    probabilities on the diagonal; 1-based (pyx:326-338)."""
+    n = len(bpp) - 1
+    upper = np.triu(np.asarray(bpp, dtype=float)[: n + 1, : n + 1], k=1)
+    upper[0, :] = 0.0
+    sym = upper + upper.T
+    # diagonal: 1.0 - (left-to-right sum of the row), the reference's Python sum() (pyx:335-336)
+    sym[np.arange(1, n + 1), np.arange(1, n + 1)] = 1.0 - sequential_row_sums(sym[:, 1:])[1:]
+    return sym
+
+
+def bp_matrix_from_fixed_structure(structure):
+    """0/1 pair matrix of a dot-bracket string, unpaired positions on the
+    diagonal; 1-based (pyx:378-392)."""
+    n = len(structure)
+    bpm = np.zeros((n + 1, n + 1), dtype="float")
+    pending = []
+    for pos, ch in enumerate(structure, start=1):
+        if ch == "(":
+            pending.append(pos)
+        elif ch == ")":
+            mate = pending.pop()
+            bpm[pos, mate] = bpm[mate, pos] = 1.0
+        else:
+            bpm[pos, pos] = 1.0
+    return bpm
+
+
+def features_from_sbpp(sbpp, n):
+    """(up, down, unp) of a symmetric 1-based pair-probability matrix: float64 arrays of n + 1 entries with an
+    ignored entry 0 (pyx:366-374).  "up" sums the partners j <= i-2, "down" the partners j > i.  The sums run
+    left to right like the reference's sum(): with real-valued probabilities the rounding order reaches mu2
+    through int() (pyx:416-423)."""
+    sbpp = np.asarray(sbpp, dtype=float)
+    col = np.arange(n + 1)
+    low = (col[None, :] >= 1) & (col[None, :] <= col[:, None] - 2)
+    up = sequential_row_sums(np.where(low, sbpp, 0.0))
+    down = sequential_row_sums(np.where(col[None, :] > col[:, None], sbpp, 0.0))
+    return up, down, 1.0 - up - down
+
+
+def rna_features(seq, structure=None, bpp=None):
+    """Three float64 arrays (up, down, unp), 0-based, one entry per residue of an RNA molecule: the numbers the
+    FEATURE form of mu2 takes (``batch.make_feature_batch``, include/bialign.h bialign_features) and
+    ``BiAligner`` keeps in ``mol["up" | "down" | "unp"][1:]``.  From base-pair probabilities ``bpp`` in the
+    layout of ViennaRNA's ``fold_compound.bpp()`` ((n+1) x (n+1), 1-based, upper triangle), else from a fixed
+    dot-bracket ``structure``, else from ViennaRNA's partition function of ``seq`` (needs ``import RNA``)."""
+    n = len(seq)
+    if bpp is not None:
+        if len(bpp) != n + 1:
+            raise ValueError("Provided base pair probabilities and sequence must have matching size.")
+        sbpp = symmetrize_bpps(bpp)
+    elif structure is not None:
+        if len(structure) != n:
+            raise ValueError("Provided structure and sequence must have the same length.")
+        sbpp = bp_matrix_from_fixed_structure(structure)
+    else:
+        import RNA  # ViennaRNA, exactly as the reference requires (pyx:347)
+        fc = RNA.fold_compound(str(seq))
+        fc.pf()
+        sbpp = symmetrize_bpps(fc.bpp())
+    return tuple(np.ascontiguousarray(f[1:]) for f in features_from_sbpp(sbpp, n))
+
+
+def check_features(feats, length, what):
+    """Validate one molecule's (up, down, unp) as the C ABI does (bialign_batch_create_features) and return them
+    as three contiguous float64 arrays.  ValueError for ragged arrays, a length other than the molecule's, a NaN
+    or infinite entry; ValueError("math domain error") for a negative one (the reference raises that from
+    math.sqrt when a product is negative; the engine refuses the sign outright)."""
+    try:
+        up, down, unp = feats
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: features must be a triple (up, down, unp)") from None
+    out = []
+    for name, arr in (("up", up), ("down", down), ("unp", unp)):
+        arr = np.ascontiguousarray(arr, dtype=np.float64)
+        if arr.ndim != 1 or arr.shape[0] != length:
+            raise ValueError(f"{what}: feature {name!r} must hold one number per residue ({length}), got shape {arr.shape}")
+        if not np.isfinite(arr).all():
+            raise ValueError(f"{what}: feature {name!r} holds a NaN or infinite entry")
+        if (arr < 0).any():
+            raise ValueError("math domain error")
+        out.append(arr)
+    return tuple(out)
+
+
 def dense_mu2_from_features(mol_a, mol_b, structure_weight):
     """int32 (n, m) table of the reference's RNA structure similarity for real-valued features
     (predicted structures): int(sw * (sqrt(upA upB) + sqrt(dnA dnB) + sqrt(unpA unpB))), entry

@@ -18,7 +18,9 @@
  *     mu2(k,l) = s2[cls_a[k-1] * k2 + cls_b[l-1]]     (pyx:414-429, 438-440)
  * with uint8 codes prepared by the host side (bialign_amd/scoring.py),
  * or, either of them or both, in DENSE form: one n x m table per pair
- * (bialign_pairs.mu1_dense / mu2_dense), for scores that depend on position.
+ * (bialign_pairs.mu1_dense / mu2_dense), for scores that depend on position,
+ * or, mu2 only, in FEATURE form (bialign_features, bialign_batch_create_features):
+ * three doubles per residue from which the GPU builds each pair's table itself.
  *
  * The engine is GPU only.  There is no CPU fallback behind this ABI.
  */
@@ -126,6 +128,35 @@ typedef struct bialign_pairs {
   const int64_t* mu1_off;
 } bialign_pairs;
 
+/* mu2 in FEATURE form: the reference's RNA mode with predicted structures (pyx:416-423),
+ *     mu2(k,l) = int(sw * (sqrt(upA[k] upB[l]) + sqrt(dnA[k] dnB[l]) + sqrt(unpA[k] unpB[l])))
+ * from three real numbers per residue.  Residue r (0-based) of pair p's A molecule is at [off_a[p] + r] of up_a /
+ * down_a / unp_a, of its B molecule at [off_b[p] + r] of up_b / down_b / unp_b (off_a / off_b of bialign_pairs, as
+ * for the code arrays): pairs may share molecules, an all-against-all batch uploads every molecule's numbers once.
+ * The upload is O(sum of lengths); the GPU builds the int32 tables of a chunk just before it sweeps the chunk, with
+ * the reference's IEEE double operations in the reference's order (the result equals the DENSE form's bit for bit),
+ * into a scratch buffer that is part of the HBM chunk plan (hbm_budget_bytes).
+ * Every feature must be finite and >= 0.  (The reference raises "math domain error" from math.sqrt only when a
+ * PRODUCT is negative, so two negative numbers pass there; this ABI is stricter and refuses the sign outright.) */
+typedef struct bialign_features {
+  int32_t structure_weight;            /* sw, an int as in bialign.py */
+  const double *up_a, *down_a, *unp_a; /* residue r (0-based) of pair p's A molecule at [off_a[p] + r] */
+  const double *up_b, *down_b, *unp_b; /* ... B molecule at [off_b[p] + r] */
+} bialign_features;
+
+/* bialign_feature_info.form */
+#define BIALIGN_MU2_LOOKUP 0
+#define BIALIGN_MU2_DENSE 1
+#define BIALIGN_MU2_FEATURE 2
+
+typedef struct bialign_feature_info {
+  int32_t form;           /* BIALIGN_MU2_* of this batch */
+  int32_t build_launches; /* table-builder launches of the last run (FEATURE form: one per chunk; else 0) */
+  int64_t table_bytes;    /* FEATURE: mu2 table bytes of the largest chunk (the scratch buffer's use, inside the HBM
+                             budget); DENSE: bytes of all resident tables; LOOKUP: 0 */
+  double build_ms;        /* HIP-event time of the builder launches of the last run; not part of fill_ms */
+} bialign_feature_info;
+
 typedef struct bialign_batch_info {
   int32_t npairs;
   int32_t nchunks;        /* HBM-budgeted chunks the batch is processed in */
@@ -189,7 +220,18 @@ int bialign_engine_reserve(bialign_engine* eng, int64_t bytes, int tries, double
 int bialign_batch_create(bialign_engine* eng, const bialign_params* params,
                          const bialign_scoring* scoring, const bialign_pairs* pairs,
                          int64_t hbm_budget_bytes, bialign_batch** out);
+/* As bialign_batch_create, with mu2 in FEATURE form (new in ABI 10 as added symbols: no existing struct or function
+ * changes).  pairs->cls_a / cls_b / mu2_dense / mu2_off are ignored (may be NULL); mu1 is whatever `pairs` says, LOOKUP
+ * or dense.  (A dense mu1 stays resident as in bialign_batch_create; a chunk's tables are copied behind its mu2 tables
+ * and count in the chunk plan too.)  feat or any of its arrays NULL, a NaN, infinite or negative feature:
+ * BIALIGN_E_INVALID (the message names pair and position).  A pair whose bound
+ * |sw| * (sqrt(max upA max upB) + sqrt(max dnA max dnB) + sqrt(max unpA max unpB)), rounded up, could leave the int32
+ * safety window: BIALIGN_E_RANGE.  A single pair whose table and layers exceed the budget: BIALIGN_E_NOMEM. */
+int bialign_batch_create_features(bialign_engine* eng, const bialign_params* params,
+                                  const bialign_scoring* scoring, const bialign_pairs* pairs,
+                                  const bialign_features* feat, int64_t hbm_budget_bytes, bialign_batch** out);
 void bialign_batch_destroy(bialign_batch* b);
+int bialign_batch_get_feature_info(const bialign_batch* b, bialign_feature_info* info);
 int bialign_batch_get_info(const bialign_batch* b, bialign_batch_info* info);
 
 /* BiAligner.optimize() (pyx:443-509) followed -- unless BIALIGN_RUN_FILL_ONLY --
@@ -220,6 +262,9 @@ int bialign_batch_get_traces(const bialign_batch* b, uint8_t* trace, int64_t* tr
  * itertools.product order, cells the reference never writes left 0.
  * out must hold nlayers*(n+1)*(m+1)*(2s+1)^2 int32. */
 int bialign_batch_dump_layers(bialign_batch* b, int32_t pair, int32_t* out);
+/* dump_mu2: pair's mu2 table as the sweep reads it, out[(k-1)*m + (l-1)], n*m int32.  FEATURE form: the table is built
+ * anew for this pair; DENSE form: the uploaded table; LOOKUP form: BIALIGN_E_INVALID. */
+int bialign_batch_dump_mu2(bialign_batch* b, int32_t pair, int32_t* out);
 
 #ifdef __cplusplus
 }
