@@ -25,6 +25,30 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
+// What the host needs of the kernels' compile-time geometry, for a run-time (max_shift, recurrence): read from the types
+// the kernels are built from, so a change there reaches the LDS sizes, layer strides and sweep lengths computed here.
+struct SweepInfo {
+  int W, R, RR, MAXOFF, PADB;   // Geo<S>
+  int recdw, lean_recdw;        // dwords of a step's record, full and LEAN (Rec<S,NL>, Rec<S,NL,true>)
+  int blk, min_goff;            // ghost feed: steps per prefetch block, age of a record when it is read
+  int ring_dw, diet_ring_dw;    // ... dwords of a wave's ring, and in the DIET layout (half-length blocks)
+  int ghost_np;                 // ... 16-byte pieces per (step, a)
+  int mu2_ring_dw, mu1_ring_dw; // dense-mu2 and dense-mu1 rings of a wave
+  int xch_dw;                   // exchange array of a wave: NCOL lanes x (XCH_ROWS per band column, affine) W values
+};
+template <int S, int NL>
+constexpr SweepInfo sweep_info_of() {
+  using G = Geo<S>;
+  using GF = GhostFeed<S, NL>;
+  return SweepInfo{G::W, G::R, G::RR, G::MAXOFF, G::PADB, Rec<S, NL>::RECDW, Rec<S, NL, true>::RECDW, GF::BLK, GF::MIN_GOFF,
+                   GF::RING_DW, GhostFeed<S, NL, false, 2>::RING_DW, GF::NP, Mu2Feed<S>::RING_DW, Mu1Feed<S>::RING_DW,
+                   (NL == 9 ? XCH_ROWS : 1) * G::W * NCOL};
+}
+#define BIALIGN_SWEEP_INFO(S, X) {sweep_info_of<S, 1>(), sweep_info_of<S, 9>()},
+static const SweepInfo g_sweep_info[][2] = {BIALIGN_FOR_EACH_S(BIALIGN_SWEEP_INFO, )};
+#undef BIALIGN_SWEEP_INFO
+static const SweepInfo& sweep_info(const bialign_batch* b) { return g_sweep_info[b->S][b->affine ? 1 : 0]; }  // tiled batches only
+
 // Waves per pair.  More waves per pair = more waves per SIMD when a launch has fewer pairs than
 // the chip has wave slots worth filling (256 CUs x 4 SIMDs x 2).  Wave w trails wave w-1 by
 // `lag` steps and wave 0 may lead wave T-1 by at most P - lag, so T waves run without mutual
@@ -38,8 +62,8 @@ int fail(int code, const char* fmt, ...) {
 //    for the actual kernel (xcu_resident; 0 = cross-CU teams not available for this launch).
 TeamShape team_shape(const bialign_batch* b, int first, int count, int xcu_resident, int xcu8_resident) {
   TeamShape ts;
-  const int W = 2 * b->S + 1, R = 64 / W;
-  const int lag = 2 * (R - 1) + 2 * ghost_blk(b->S) + 16;
+  const SweepInfo& geo = sweep_info(b);
+  const int lag = 2 * (geo.R - 1) + 2 * geo.blk + 16;
   int fit_exact = PROG_WORDS;  // largest team the pairs of this launch allow: T*lag + 64 <= P (P >= 256), two strips per wave
   for (int t = first; t < first + count; ++t) {
     const PairDesc& d = b->pairs[b->order[t]];
@@ -227,14 +251,12 @@ int xcu_serial_end(bialign_engine* e) {
 
 namespace {
 
-// Sweep geometry of one pair (mirrors the kernel's Geo<S>): strips, period, steps.
-void sweep_geometry(int n, int m, int S, int* NS, int* P, int* G) {
-  const int W = 2 * S + 1, R = 64 / W, RR = R - 1;
-  const int min_goff = 2 * ghost_blk(S) + 8;  // GhostFeed<S,.>::MIN_GOFF
-  *NS = (n + 1 + RR - 1) / RR;
+// Sweep geometry of one pair: strips, period, steps.
+void sweep_geometry(const SweepInfo& g, int n, int m, int* NS, int* P, int* G) {
+  *NS = (n + 1 + g.RR - 1) / g.RR;
   // one idle column between strips (P >= m+2) and ghost records old enough to prefetch
-  *P = std::max(m + 2, 2 * (R - 1) + min_goff);
-  *G = (*NS - 1) * *P + m + 2 * (R - 1) + (W - 1) + 1;
+  *P = std::max(m + 2, 2 * (g.R - 1) + g.min_goff);
+  *G = (*NS - 1) * *P + m + g.MAXOFF + 1;
 }
 
 int64_t cells_of(int n, int m, int s) {
@@ -259,58 +281,45 @@ PackInfo pack_info_of() {
 }
 PackInfo pack_info(int S) { return S == 1 ? pack_info_of<1>() : (S == 2 ? pack_info_of<2>() : pack_info_of<3>()); }
 
+// Dynamic LDS of a sweep's workgroup of `team` waves: per wave a ghost ring, an exchange array and the rings of the dense
+// forms; shared: progress words, score tables, the molecules' codes.
 // diet: the eight-wave form of the s=2 affine kernel (fill_affine_kernel, DIET): half-length ghost blocks,
 // molecule A's codes not staged.  dense1: a dense-mu1 ring per wave, no sequence codes staged.
-size_t lds_need(int S, int NL, int team, int k1, int k2, int n, int m, bool dense = false, bool diet = false,
-                bool dense1 = false) {
-  const int W = 2 * S + 1, PADB = S + 1;
-  const size_t nv = (NL == 9 ? 12 : 1) * W;
-  const size_t npad = diet ? 0 : (n + 3) & ~3, mpad = (m + 2 * PADB + 3) & ~3;
+size_t lds_need(const SweepInfo& g, int team, int k1, int k2, int n, int m, bool dense = false, bool diet = false, bool dense1 = false) {
+  const size_t npad = diet ? 0 : code_pad(n), mpad = code_pad(m, g.PADB);
   const size_t codes = dense1 ? npad + mpad : 2 * npad + 2 * mpad;  // (class codes only)
-  const int nd = NL * W, np = nd / 4 + (nd % 4 ? 1 : 0), blk = diet ? 2 : ghost_blk(S);
-  const size_t ring_dw = 2 * (((size_t)blk * W * np + 63) / 64 * 64) * 4;  // GhostFeed<S,NL>::RING_DW
-  const size_t shared_dw = 16 + (size_t)k1 * k1 + (size_t)k2 * k2;  // progress words + score tables
-  const size_t mu2_ring_dw = dense ? 2 * (size_t)blk * 64 : 0;  // Mu2Feed<S>::RING_DW
-  const size_t mu1_ring_dw = dense1 ? 2 * (size_t)blk * 64 : 0;  // Mu1Feed<S>::RING_DW
-  return (team * (ring_dw + nv * NCOL + mu2_ring_dw + mu1_ring_dw) + shared_dw) * 4 + codes;
+  const size_t wave_dw = (diet ? g.diet_ring_dw : g.ring_dw) + g.xch_dw + (dense ? g.mu2_ring_dw : 0) + (dense1 ? g.mu1_ring_dw : 0);
+  const size_t shared_dw = LDS_PROG_WORDS + (size_t)k1 * k1 + (size_t)k2 * k2;
+  return (team * wave_dw + shared_dw) * 4 + codes;
 }
 
 // fill_affine_slim_kernel (bialign_fill_slim.hpp), a workgroup of twelve waves: twelve ghost rings, a block of sentinels,
 // progress words, score tables (lds_need_slim_base); per pair of the workgroup both molecules' codes (lds_need_slim_codes)
-size_t lds_need_slim_base(int S, int k1, int k2) {
-  const int W = 2 * S + 1;
-  const int nd = 9 * W, np = nd / 4 + (nd % 4 ? 1 : 0), blk = ghost_blk(S);
-  const size_t ring_dw = 2 * (((size_t)blk * W * np + 63) / 64 * 64) * 4;  // GhostFeed<S,9>::RING_DW
-  return (12 * ring_dw + 4 * np + 16 + (size_t)k1 * k1 + (size_t)k2 * k2) * 4;
+size_t lds_need_slim_base(const SweepInfo& g, int k1, int k2) {
+  return (12 * (size_t)g.ring_dw + 4 * g.ghost_np + LDS_PROG_WORDS + (size_t)k1 * k1 + (size_t)k2 * k2) * 4;
 }
-size_t lds_need_slim_codes(int S, int n, int m) {
-  const int PADB = S + 1;
-  const size_t npad = (n + 3) & ~3, mpad = (m + 2 * PADB + 3) & ~3;
-  return 2 * npad + 2 * mpad;
+size_t lds_need_slim_codes(const SweepInfo& g, int n, int m) { return 2 * (size_t)code_pad(n) + 2 * (size_t)code_pad(m, g.PADB); }
+
+// The tiled kernels are templates on max_shift: fn(std::integral_constant<int, S>{}) for the batch's run-time S.
+template <typename Fn>
+int with_shift(const bialign_batch* b, const char* what, Fn&& fn) {
+  switch (b->S) {
+    case 0: return fn(std::integral_constant<int, 0>{});
+    case 1: return fn(std::integral_constant<int, 1>{});
+    case 2: return fn(std::integral_constant<int, 2>{});
+    case 3: return fn(std::integral_constant<int, 3>{});
+    case 4: return fn(std::integral_constant<int, 4>{});
+    case 5: return fn(std::integral_constant<int, 5>{});
+  }
+  return fail(BIALIGN_E_UNSUPPORTED, "no %s kernel for affine=%d max_shift=%d", what, b->affine, b->S);
 }
 
 int launch_fill(bialign_batch* b, const DeviceBatch& v, int first, int count) {
   if (b->wide) return launch_fill_wide(b, v, first, count);
-  if (b->affine) {
-    switch (b->S) {
-      case 0: return launch_fill_affine<0>(b, v, first, count);
-      case 1: return launch_fill_affine<1>(b, v, first, count);
-      case 2: return launch_fill_affine<2>(b, v, first, count);
-      case 3: return launch_fill_affine<3>(b, v, first, count);
-      case 4: return launch_fill_affine<4>(b, v, first, count);
-      case 5: return launch_fill_affine<5>(b, v, first, count);
-    }
-  } else {
-    switch (b->S) {
-      case 0: return launch_fill_linear<0>(b, v, first, count);
-      case 1: return launch_fill_linear<1>(b, v, first, count);
-      case 2: return launch_fill_linear<2>(b, v, first, count);
-      case 3: return launch_fill_linear<3>(b, v, first, count);
-      case 4: return launch_fill_linear<4>(b, v, first, count);
-      case 5: return launch_fill_linear<5>(b, v, first, count);
-    }
-  }
-  return fail(BIALIGN_E_UNSUPPORTED, "no fill kernel for affine=%d max_shift=%d", b->affine, b->S);
+  return with_shift(b, "fill", [&](auto s) {
+    constexpr int S = decltype(s)::value;
+    return b->affine ? launch_fill_affine<S>(b, v, first, count) : launch_fill_linear<S>(b, v, first, count);
+  });
 }
 
 // Lean traceback of one chunk: as many (re-sweep, walk) rounds as its longest pair has strips.
@@ -320,70 +329,32 @@ int lean_traceback_rounds(bialign_batch* b, const DeviceBatch& v, int first, int
   int rounds = 0;
   for (int t = first; t < first + count; ++t) rounds = std::max(rounds, b->pairs[b->order[t]].NS);
   rounds = (rounds + b->resw_k - 1) / b->resw_k;
-  for (int r = 0; r < rounds; ++r) {
-    int rc = BIALIGN_E_UNSUPPORTED;
-#define BIALIGN_ROUND(S)                                                                              \
-  case S:                                                                                             \
-    rc = b->affine ? launch_resweep_affine<S>(b, v, first, count) : launch_resweep_linear<S>(b, v, first, count);          \
-    if (rc == BIALIGN_OK)                                                                             \
-      rc = b->affine ? launch_traceback_affine_strip<S>(b, v, first, count)                           \
-                     : launch_traceback_linear_strip<S>(b, v, first, count);                          \
-    break;
-    switch (b->S) {
-      BIALIGN_ROUND(0) BIALIGN_ROUND(1) BIALIGN_ROUND(2) BIALIGN_ROUND(3) BIALIGN_ROUND(4) BIALIGN_ROUND(5)
+  return with_shift(b, "re-sweep", [&](auto s) {
+    constexpr int S = decltype(s)::value;
+    for (int r = 0; r < rounds; ++r) {
+      int rc = b->affine ? launch_resweep_affine<S>(b, v, first, count) : launch_resweep_linear<S>(b, v, first, count);
+      if (rc == BIALIGN_OK)
+        rc = b->affine ? launch_traceback_affine_strip<S>(b, v, first, count) : launch_traceback_linear_strip<S>(b, v, first, count);
+      if (rc) return rc;
     }
-#undef BIALIGN_ROUND
-    if (rc) return rc;
-  }
-  return BIALIGN_OK;
+    return (int)BIALIGN_OK;
+  });
 }
 
 int launch_traceback(const bialign_batch* b, const DeviceBatch& v, int first, int count, bool do_trace) {
   if (b->wide) return launch_traceback_wide(b, v, first, count, do_trace);
-  if (b->affine) {
-    switch (b->S) {
-      case 0: return launch_traceback_affine<0>(b, v, first, count, do_trace);
-      case 1: return launch_traceback_affine<1>(b, v, first, count, do_trace);
-      case 2: return launch_traceback_affine<2>(b, v, first, count, do_trace);
-      case 3: return launch_traceback_affine<3>(b, v, first, count, do_trace);
-      case 4: return launch_traceback_affine<4>(b, v, first, count, do_trace);
-      case 5: return launch_traceback_affine<5>(b, v, first, count, do_trace);
-    }
-  } else {
-    switch (b->S) {
-      case 0: return launch_traceback_linear<0>(b, v, first, count, do_trace);
-      case 1: return launch_traceback_linear<1>(b, v, first, count, do_trace);
-      case 2: return launch_traceback_linear<2>(b, v, first, count, do_trace);
-      case 3: return launch_traceback_linear<3>(b, v, first, count, do_trace);
-      case 4: return launch_traceback_linear<4>(b, v, first, count, do_trace);
-      case 5: return launch_traceback_linear<5>(b, v, first, count, do_trace);
-    }
-  }
-  return fail(BIALIGN_E_UNSUPPORTED, "no traceback kernel for affine=%d max_shift=%d", b->affine, b->S);
+  return with_shift(b, "traceback", [&](auto s) {
+    constexpr int S = decltype(s)::value;
+    return b->affine ? launch_traceback_affine<S>(b, v, first, count, do_trace) : launch_traceback_linear<S>(b, v, first, count, do_trace);
+  });
 }
 
 int launch_dump_any(const bialign_batch* b, const DeviceBatch& v, int pid, int32_t* d_out) {
   if (b->wide) return launch_dump_wide(b, v, pid, d_out);
-  if (b->affine) {
-    switch (b->S) {
-      case 0: return launch_dump<0, 9>(b, v, pid, d_out);
-      case 1: return launch_dump<1, 9>(b, v, pid, d_out);
-      case 2: return launch_dump<2, 9>(b, v, pid, d_out);
-      case 3: return launch_dump<3, 9>(b, v, pid, d_out);
-      case 4: return launch_dump<4, 9>(b, v, pid, d_out);
-      case 5: return launch_dump<5, 9>(b, v, pid, d_out);
-    }
-  } else {
-    switch (b->S) {
-      case 0: return launch_dump<0, 1>(b, v, pid, d_out);
-      case 1: return launch_dump<1, 1>(b, v, pid, d_out);
-      case 2: return launch_dump<2, 1>(b, v, pid, d_out);
-      case 3: return launch_dump<3, 1>(b, v, pid, d_out);
-      case 4: return launch_dump<4, 1>(b, v, pid, d_out);
-      case 5: return launch_dump<5, 1>(b, v, pid, d_out);
-    }
-  }
-  return fail(BIALIGN_E_UNSUPPORTED, "no dump kernel for affine=%d max_shift=%d", b->affine, b->S);
+  return with_shift(b, "dump", [&](auto s) {
+    constexpr int S = decltype(s)::value;
+    return b->affine ? launch_dump<S, 9>(b, v, pid, d_out) : launch_dump<S, 1>(b, v, pid, d_out);
+  });
 }
 
 // Cut the batch into chunks of at most budget_dw dwords of layer storage and lay the pairs of each chunk end to
@@ -566,7 +537,8 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
   if (b->dense1 && !pr->mu1_off) return fail(BIALIGN_E_INVALID, "mu1_dense given without mu1_off");
   if (!b->dense1 && (!pr->seq_a || !pr->seq_b)) return fail(BIALIGN_E_INVALID, "seq_a / seq_b are NULL (LOOKUP form)");
   if (!pr->len_a || !pr->len_b || !pr->off_a || !pr->off_b) return fail(BIALIGN_E_INVALID, "len_a / len_b / off_a / off_b are NULL");
-  const int S = b->S, W = 2 * S + 1;
+  const int S = b->S;
+  const SweepInfo geo = b->wide ? SweepInfo{} : sweep_info(b.get());  // (the wide-band path has no tiles)
 
   // int32 safety window: finite scores and the drift of "-infinity" cells must
   // stay within 2^28 of where they start (kernels rely on it, see THRESH).
@@ -636,7 +608,7 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
     d.n = n;
     d.m = m;
     d.NS = d.P = d.G = 0;
-    if (!b->wide) sweep_geometry(n, m, S, &d.NS, &d.P, &d.G);
+    if (!b->wide) sweep_geometry(geo, n, m, &d.NS, &d.P, &d.G);
     d.trace_cap = 2 * (n + m) + 2;
     d.seq_a = pr->off_a[p];
     d.seq_b = pr->off_b[p];
@@ -649,18 +621,18 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
     tot_a = std::max<int64_t>(tot_a, pr->off_a[p] + n);
     tot_b = std::max<int64_t>(tot_b, pr->off_b[p] + m);
     if (!b->wide) {
-      b->lds_bytes = std::max(b->lds_bytes, lds_need(S, b->NL, 1, sc->k1, sc->k2, n, m, b->dense, false, b->dense1));
-      b->lds_base = std::max(b->lds_base, lds_need(S, b->NL, 0, sc->k1, sc->k2, n, m, b->dense, false, b->dense1));
-      b->lds_diet8 = std::max(b->lds_diet8, lds_need(S, b->NL, 8, sc->k1, sc->k2, n, m, false, true));
-      b->lds_slim_codes = std::max(b->lds_slim_codes, lds_need_slim_codes(S, n, m));
+      b->lds_bytes = std::max(b->lds_bytes, lds_need(geo, 1, sc->k1, sc->k2, n, m, b->dense, false, b->dense1));
+      b->lds_base = std::max(b->lds_base, lds_need(geo, 0, sc->k1, sc->k2, n, m, b->dense, false, b->dense1));
+      b->lds_diet8 = std::max(b->lds_diet8, lds_need(geo, 8, sc->k1, sc->k2, n, m, false, true));
+      b->lds_slim_codes = std::max(b->lds_slim_codes, lds_need_slim_codes(geo, n, m));
     }
     b->lds_trace = std::max<size_t>(b->lds_trace, ((size_t)sc->k1 * sc->k1 + (size_t)sc->k2 * sc->k2) * 4 +
-                                                      (b->dense1 ? 1 : 2) * ((size_t)((n + 3) & ~3) + (size_t)((m + 3) & ~3)));
+                                                      (b->dense1 ? 1 : 2) * ((size_t)code_pad(n) + (size_t)code_pad(m)));
   }
   if (!b->wide)
-    b->lds_per_wave = lds_need(S, b->NL, 1, sc->k1, sc->k2, 1, 1, b->dense, false, b->dense1) -
-                      lds_need(S, b->NL, 0, sc->k1, sc->k2, 1, 1, b->dense, false, b->dense1);
-  if (!b->wide) b->lds_slim_base = lds_need_slim_base(S, sc->k1, sc->k2);
+    b->lds_per_wave = lds_need(geo, 1, sc->k1, sc->k2, 1, 1, b->dense, false, b->dense1) -
+                      lds_need(geo, 0, sc->k1, sc->k2, 1, 1, b->dense, false, b->dense1);
+  if (!b->wide) b->lds_slim_base = lds_need_slim_base(geo, sc->k1, sc->k2);
   if (std::max(b->lds_bytes, b->lds_trace) > 160 * 1024)
     return fail(BIALIGN_E_UNSUPPORTED, "molecules too long for the LDS staging (%zu bytes needed, 160 KiB per workgroup)",
                 std::max(b->lds_bytes, b->lds_trace));
@@ -703,13 +675,10 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
         pair_dwords[p] = b->lean ? 16 : wide_pair_dwords(d.n, d.m, S, b->NL);
         continue;
       }
-      int slp = (64 / W - 1) * W;  // Rec<S,NL>::SLP
-      if ((slp + 7) / 8 * 8 - slp <= BIALIGN_PADMAX) slp = (slp + 7) / 8 * 8;
-      const int64_t full_rec = (int64_t)((b->NL * W) / 4) * slp * 4 + 64 * ((b->NL * W) % 4);  // Rec<S,NL>::RECDW per step
-      const int64_t lean_dw = (int64_t)d.G * ((W * b->NL * W + 3) / 4 * 4);       // Rec<S,NL,true>::RECDW per step
-      const int64_t scratch_dw = (int64_t)(d.m + 2 * (64 / W - 1) + W) * full_rec;  // one strip: m + MAXOFF + 1 records
+      const int64_t lean_dw = (int64_t)d.G * geo.lean_recdw;
+      const int64_t scratch_dw = (int64_t)(d.m + geo.MAXOFF + 1) * geo.recdw;  // one strip's full records
       d.scratch_off = lean_dw;  // relative to layer_off until the chunk layout is fixed below
-      pair_dwords[p] = b->lean_trace ? lean_dw + b->resw_k * scratch_dw : (b->lean ? lean_dw : (int64_t)d.G * full_rec);
+      pair_dwords[p] = b->lean_trace ? lean_dw + b->resw_k * scratch_dw : (b->lean ? lean_dw : (int64_t)d.G * geo.recdw);
       if (b->pack && !b->lean)  // (a sweep that meets an unpackable value is repeated with full records: replan_full())
         pair_dwords[p] = pack_info(S).pair_dwords(d.G, d.P, d.m);
     }
@@ -751,11 +720,7 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
     pick_resw_k();
   }
   b->full_dwords.resize(pr->npairs);
-  for (int p = 0; p < pr->npairs; ++p) {
-    int slp = (64 / W - 1) * W;  // as in size_pairs
-    if ((slp + 7) / 8 * 8 - slp <= BIALIGN_PADMAX) slp = (slp + 7) / 8 * 8;
-    b->full_dwords[p] = b->wide ? pair_dwords[p] : (int64_t)b->pairs[p].G * ((int64_t)((b->NL * W) / 4) * slp * 4 + 64 * ((b->NL * W) % 4));
-  }
+  for (int p = 0; p < pr->npairs; ++p) b->full_dwords[p] = b->wide ? pair_dwords[p] : (int64_t)b->pairs[p].G * geo.recdw;
   b->packed_sizing = b->pack && !b->lean;
   if (int rc = plan_chunks(b.get(), pair_dwords, budget_dw)) return rc;
 

@@ -93,7 +93,7 @@ __global__ void __launch_bounds__(64 * TW) BIALIGN_WPE_ATTR fill_affine_kernel(c
   using G_ = Geo<S>;
   using R_ = Rec<S, 9, LEAN>;
   constexpr int W = G_::W, R = G_::R, RR = G_::RR, PADB = G_::PADB;
-  constexpr int XR = 12;  // exchange rows per point that go through LDS
+  constexpr int XR = XCH_ROWS;  // exchange rows per point that go through LDS
   constexpr int NV = XR * W, ND = R_::ND, NCH4 = R_::NCH4, TAIL = R_::TAIL, RECDW = R_::RECDW;
   extern __shared__ __align__(16) int32_t smem[];
 
@@ -138,16 +138,16 @@ __global__ void __launch_bounds__(64 * TW) BIALIGN_WPE_ATTR fill_affine_kernel(c
   int32_t* mu2ring = smem + TW * (GF::RING_DW + NV * NCOL) + wl * MF::RING_DW;  // dense-mu2 ring
   int32_t* mu1ring = smem + TW * (GF::RING_DW + NV * NCOL + MU2W) + wl * M1F::RING_DW;  // dense-mu1 ring
   volatile int32_t* prog_lds = smem + TW * PERW;                  // [16] (in-workgroup teams)
-  int32_t* s1 = smem + TW * PERW + 16;                            // [k1*k1]
+  int32_t* s1 = smem + TW * PERW + LDS_PROG_WORDS;                            // [k1*k1]
   int32_t* s2 = s1 + k1 * k1;                                   // [k2*k2]
-  const int npad = (n + 3) & ~3, mpad = (m + 2 * PADB + 3) & ~3;
+  const int npad = code_pad(n), mpad = code_pad(m, PADB);
   uint8_t* sa = reinterpret_cast<uint8_t*>(s2 + k2 * k2);  // seq A codes, [i-1]   (DIET: not staged)
   uint8_t* ca = sa + (DENSE1 ? 0 : npad);                   // cls A,       [k-1]   (DENSE1: no sequence codes)
   uint8_t* sb = DIET ? sa : ca + npad;                      // seq B codes, [j-1+PADB]
   uint8_t* cb = sb + (DENSE1 ? 0 : mpad);                   // cls B,       [l-1+PADB]
 
   for (int t = threadIdx.x; t < TW * PERW; t += 64 * TW) smem[t] = SENT;
-  if (threadIdx.x < 16) prog_lds[threadIdx.x] = 0;
+  if (threadIdx.x < LDS_PROG_WORDS) prog_lds[threadIdx.x] = 0;
   for (int t = threadIdx.x; t < k1 * k1; t += 64 * TW) s1[t] = A.s1[t];
   for (int t = threadIdx.x; t < k2 * k2; t += 64 * TW) s2[t] = A.s2[t];
   if (!DIET)

@@ -57,16 +57,16 @@ __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch 
   int32_t* mu2ring = smem + TW * (GF::RING_DW + NV * NCOL) + wl * MF::RING_DW;
   int32_t* mu1ring = smem + TW * (GF::RING_DW + NV * NCOL + MU2W) + wl * M1F::RING_DW;
   volatile int32_t* prog = smem + TW * PERW;  // [16] steps with acknowledged stores
-  int32_t* s1 = smem + TW * PERW + 16;
+  int32_t* s1 = smem + TW * PERW + LDS_PROG_WORDS;
   int32_t* s2 = s1 + k1 * k1;
-  const int npad = (n + 3) & ~3, mpad = (m + 2 * PADB + 3) & ~3;
+  const int npad = code_pad(n), mpad = code_pad(m, PADB);
   uint8_t* sa = reinterpret_cast<uint8_t*>(s2 + k2 * k2);
   uint8_t* ca = sa + (DENSE1 ? 0 : npad);  // (DENSE1: no sequence codes)
   uint8_t* sb = ca + npad;
   uint8_t* cb = sb + (DENSE1 ? 0 : mpad);
 
   for (int t = threadIdx.x; t < TW * PERW; t += 64 * TW) smem[t] = SENT;
-  if (threadIdx.x < 16) prog[threadIdx.x] = 0;
+  if (threadIdx.x < LDS_PROG_WORDS) prog[threadIdx.x] = 0;
   for (int t = threadIdx.x; t < k1 * k1; t += 64 * TW) s1[t] = A.s1[t];
   for (int t = threadIdx.x; t < k2 * k2; t += 64 * TW) s2[t] = A.s2[t];
   for (int t = threadIdx.x; t < n; t += 64 * TW) {

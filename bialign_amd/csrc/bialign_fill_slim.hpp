@@ -78,17 +78,17 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
   v4i* ring = reinterpret_cast<v4i*>(smem + wv * GF::RING_DW);        // ghost-row ring, two halves
   int32_t* sentblk = smem + NW * PERW;
   volatile int32_t* prog_lds = smem + NW * PERW + SENTBLK + pw * TW;  // [16]: this team's words
-  int32_t* s1 = smem + NW * PERW + SENTBLK + 16;                      // [k1*k1]
+  int32_t* s1 = smem + NW * PERW + SENTBLK + LDS_PROG_WORDS;                      // [k1*k1]
   int32_t* s2 = s1 + k1 * k1;                                         // [k2*k2]
   uint8_t* codes = reinterpret_cast<uint8_t*>(s2 + k2 * k2);          // per pair: seq A, cls A, seq B, cls B (A.slim_code_bytes each pair)
-  const int npad = (n + 3) & ~3, mpad = (m + 2 * PADB + 3) & ~3;
+  const int npad = code_pad(n), mpad = code_pad(m, PADB);
   uint8_t* sa = codes + (size_t)pw * A.slim_code_bytes;    // seq A codes, [i-1]
   uint8_t* ca = sa + npad;                                  // cls A,       [k-1]
   uint8_t* sb = ca + npad;                                  // seq B codes, [j-1+PADB]
   uint8_t* cb = sb + mpad;                                  // cls B,       [l-1+PADB]
 
   for (int t = threadIdx.x; t < NW * PERW + SENTBLK; t += 64 * NW) smem[t] = SENT;
-  if (threadIdx.x < 16) smem[NW * PERW + SENTBLK + threadIdx.x] = 0;
+  if (threadIdx.x < LDS_PROG_WORDS) smem[NW * PERW + SENTBLK + threadIdx.x] = 0;
   for (int t = threadIdx.x; t < k1 * k1; t += 64 * NW) s1[t] = A.s1[t];
   for (int t = threadIdx.x; t < k2 * k2; t += 64 * NW) s2[t] = A.s2[t];
   if (have_pair) {  // each team stages its pair's codes

@@ -1,8 +1,13 @@
 // bialign_host.hpp -- host-side internals shared by the translation units of libbialign_hip.so:
-// the batch / engine objects behind the C ABI and the kernel launchers.  The launchers are
-// templates on max_shift; each (max_shift, kind) is instantiated in its own translation unit
-// (bialign_inst.hip, compiled once per -DBIALIGN_TU_S / -DBIALIGN_TU_KIND) so that the kernels
-// build in parallel; bialign_capi.hip only dispatches.
+// the batch / engine objects behind the C ABI and the kernel launchers.
+//   Launching: launch() (LDS attribute, launch, error), launch_team() (the same with progress words in HBM and, for
+// cross-CU teams, one such launch at a time per device), xcu_resident() (occupancy of a cross-CU grid).
+//   Kernel variants are named by flag words (FillFlags, TraceFlags) through fill_affine_of / fill_linear_of /
+// traceback_*_of; which variants exist is stated once (fill_affine_exists, fill_linear_exists, fill_slim_exists,
+// traceback_exists), and one ladder per recurrence picks the launch for a team shape.
+//   The launchers are templates on max_shift; each (max_shift, kind) is instantiated in its own translation unit
+// (bialign_inst.hip, compiled once per -DBIALIGN_TU_S / -DBIALIGN_TU_KIND) so that the kernels build in parallel;
+// bialign_capi.hip only dispatches.
 #pragma once
 #include "bialign_kernels.hpp"
 
@@ -15,6 +20,7 @@
 #include <mutex>
 #include <numeric>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/bialign.h"
@@ -58,16 +64,6 @@ struct DevBuf {
     return hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, s);
   }
 };
-
-// GhostFeed<S,.>::BLK
-inline int ghost_blk(int S) {
-#ifdef BIALIGN_BLK_OVERRIDE
-  (void)S;
-  return BIALIGN_BLK_OVERRIDE;
-#else
-  return S <= 1 ? 8 : 4;
-#endif
-}
 
 }  // namespace bialign
 
@@ -224,35 +220,169 @@ int xcu_serial_end(bialign_engine* e);
 // engine's stream (bialign_mu2_build.hip).  The pairs' tab_off must be the device's.
 int launch_build_mu2(bialign_batch* b, int first, int count);
 
-template <int S, bool BETA_NONPOS, int TW, bool XCU, bool DENSE = false, bool LEAN = false, bool PACK = false,
-          bool DENSE1 = false>
+// ---- launching: every kernel of the library starts through launch() or launch_team()
+// Dynamic LDS beyond 64 KiB has to be allowed per kernel, ahead of a launch or an occupancy query.
+template <typename... P>
+hipError_t allow_lds(void (*kern)(P...), size_t lds) {
+  if (lds <= 64 * 1024) return hipSuccess;
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+template <typename... P, typename... A>
+hipError_t try_launch(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
+  if (hipError_t e = allow_lds(kern, lds)) return e;
+  hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+  return hipGetLastError();
+}
+template <typename... P, typename... A>
+int launch(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
+  HIP_TRY(try_launch(kern, grid, block, lds, st, args...));
+  return BIALIGN_OK;
+}
+
+// A launch whose workgroups hand over to each other through progress words in HBM (DeviceBatch::prog, PROG_WORDS per
+// pair, zeroed per launch).  serial: they sit on different CUs and wait for each other, so all of them must be resident
+// at once -- such launches run one at a time per device (xcu_serial_begin / _end) and mark the run for the fallback.
+template <typename... P, typename... X>
+int launch_team(bialign_batch* b, void (*kern)(P...), dim3 grid, dim3 block, size_t lds, DeviceBatch w, int count,
+                bool serial, const X&... extra) {
+  const size_t words = (size_t)count * PROG_WORDS;
+  if (b->d_prog.n < words) HIP_TRY(b->d_prog.alloc(words));
+  HIP_TRY(hipMemsetAsync(b->d_prog.p, 0, words * sizeof(int32_t), b->eng->stream));
+  w.prog = b->d_prog.p;
+  w.spin_limit = b->xcu_spin_limit;
+  if (!serial) return launch(kern, grid, block, lds, b->eng->stream, w, extra...);
+  b->used_xcu = true;
+  if (int rc = xcu_serial_begin(b->eng)) return rc;
+  const hipError_t launched = try_launch(kern, grid, block, lds, b->eng->stream, w, extra...);
+  const int rc = xcu_serial_end(b->eng);  // always: it releases the launch lock
+  if (launched == hipSuccess && rc) return rc;
+  HIP_TRY(launched);
+  return BIALIGN_OK;
+}
+
+// Workgroups of `block` threads with `lds` bytes of kernel `kern` the device can hold at once, from the runtime's
+// occupancy calculation for the actual code object (registers, LDS): the cap of a grid whose workgroups wait for each
+// other.  0 when the runtime cannot tell.
+template <typename... P>
+int xcu_resident(const bialign_batch* b, void (*kern)(P...), int block, size_t lds) {
+  int per_cu = 0;
+  if (allow_lds(kern, lds) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), block, lds) != hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  return per_cu * b->eng->num_cu;
+}
+// ... asked once per batch and cache slot (bialign_batch::xcu_resident; a batch is either DENSE or not); 0 once the
+// batch has fallen back from cross-CU teams
+template <typename... P>
+int xcu_resident_cached(bialign_batch* b, int slot, void (*kern)(P...), int block, size_t lds) {
+  if (b->no_xcu) return 0;
+  int& cached = b->xcu_resident[slot];
+  if (cached < 0) cached = xcu_resident(b, kern, block, lds);
+  return cached;
+}
+
+// A run-time flag word as a compile-time one: fn(std::integral_constant<unsigned, flags & MASK>{}), one bit at a time.
+template <unsigned MASK, unsigned F = 0, typename Fn>
+int with_flags(unsigned flags, Fn&& fn) {
+  if constexpr (MASK == 0) {
+    return fn(std::integral_constant<unsigned, F>{});
+  } else {
+    constexpr unsigned BIT = MASK & (~MASK + 1);
+    return (flags & BIT) ? with_flags<(MASK & ~BIT), (F | BIT)>(flags, fn) : with_flags<(MASK & ~BIT), F>(flags, fn);
+  }
+}
+
+// ---- the kernels' variants by name.  The kernel templates take rows of positional booleans; the host names a variant
+//      by a flag word and these functions are the only places that spell the rows out.
+enum FillFlags : unsigned {
+  F_XCU = 1,        // cross-CU team: gw workgroups per pair
+  F_DENSE = 2,      // mu2 from dense tables
+  F_LEAN = 4,       // LEAN records
+  F_RESW = 8,       // strip re-sweep of the lean traceback
+  F_PACK = 16,      // packed records (Pack<S>)
+  F_DENSE1 = 32,    // mu1 from dense tables
+  F_BETA_ANY = 64,  // affine: gap_opening_cost > 0, the general-beta algebra
+};
+enum TraceFlags : unsigned {
+  T_TRACE = 1,   // walk back and write the trace (else: the score only)
+  T_STRIP = 2,   // lean traceback: one strip's walk through the scratch records
+  T_WIDE = 4,    // wide-band layers (bialign_wide.hpp)
+  T_PACK = 8,    // packed records (affine)
+  T_DENSE1 = 16, // mu1 from dense tables
+};
+
+// The instantiation plan: which sweeps exist, as (max_shift, waves per workgroup, flags).
+constexpr bool fill_affine_exists(int S, int TW, unsigned F) {
+  const bool xcu = F & F_XCU, dense = F & (F_DENSE | F_DENSE1), pack = F & F_PACK;
+  // packed records: max_shift 1..BIALIGN_MAX_SHIFT_PACKED, full storage, not with dense mu1
+  if (pack && (S < 1 || S > BIALIGN_MAX_SHIFT_PACKED || (F & (F_LEAN | F_DENSE1)))) return false;
+  // re-sweeps and the (rare) general-beta algebra: one wave per pair, full (re-sweeps) or any (beta) records
+  if (F & (F_RESW | F_BETA_ANY)) return TW == 1 && !xcu && !pack && !((F & F_RESW) && (F & F_LEAN));
+  if (TW == 1) return !xcu || !dense || S <= 3;           // cross-CU teams of the dense forms: up to s=3
+  if (TW == 8) return !dense && (xcu ? S == 2 : S <= 2);  // LOOKUP only (s=2: the DIET layout, also as a cross-CU team)
+  return (TW == 4 || TW == 2) && !xcu && S <= 3;          // s >= 4 needs nearly all 512 registers of a SIMD lane: one wave per pair
+}
+constexpr bool fill_linear_exists(int TW, unsigned F) {
+  if (F & (F_PACK | F_BETA_ANY)) return false;
+  if (F & (F_RESW | F_XCU)) return TW == 1 && (F & (F_RESW | F_XCU)) != (F_RESW | F_XCU) && !((F & F_RESW) && (F & F_LEAN));
+  return TW == 1 || TW == 2 || (!(F & (F_DENSE | F_DENSE1)) && (TW == 4 || TW == 8));  // dense forms: up to two waves
+}
+// fill_affine_slim_kernel: max_shift 1, LOOKUP scores, LEAN or packed records, teams of 2, 3, 6 or 12 waves
+constexpr bool fill_slim_exists(int S, unsigned F) { return S == 1 && (F == F_LEAN || F == F_PACK); }
+constexpr bool traceback_exists(bool affine, int S, unsigned F) {
+  if ((F & T_PACK) && (!affine || S < 1 || S > BIALIGN_MAX_SHIFT_PACKED || (F & ~(T_PACK | T_TRACE)))) return false;
+  if (F & T_STRIP) return (F & T_TRACE) && !(F & T_WIDE);
+  return !(F & T_DENSE1) || (F & T_TRACE);  // (without the walk no score is read: the LOOKUP kernels serve)
+}
+
+template <int S, int TW, unsigned F>
+auto fill_affine_of() {
+  static_assert(fill_affine_exists(S, TW, F), "not in the instantiation plan");
+  return fill_affine_kernel<S, !(F & F_BETA_ANY), TW, (F & F_XCU) != 0, (F & F_DENSE) != 0, (F & F_LEAN) != 0, (F & F_RESW) != 0,
+                            (F & F_PACK) != 0, (F & F_DENSE1) != 0>;
+}
+template <int S, int TW, unsigned F>
+auto fill_linear_of() {
+  static_assert(fill_linear_exists(TW, F), "not in the instantiation plan");
+  return fill_linear_kernel<S, TW, (F & F_DENSE) != 0, (F & F_LEAN) != 0, (F & F_RESW) != 0, (F & F_XCU) != 0, (F & F_DENSE1) != 0>;
+}
+template <int S, unsigned F>
+auto traceback_affine_of() {
+  static_assert(traceback_exists(true, S, F), "not in the instantiation plan");
+  return traceback_affine_kernel<S, (F & T_TRACE) != 0, (F & T_STRIP) != 0, (F & T_WIDE) != 0, (F & T_PACK) != 0, (F & T_DENSE1) != 0>;
+}
+template <int S, unsigned F>
+auto traceback_linear_of() {
+  static_assert(traceback_exists(false, S, F), "not in the instantiation plan");
+  return traceback_linear_kernel<S, (F & T_TRACE) != 0, (F & T_STRIP) != 0, (F & T_WIDE) != 0, (F & T_DENSE1) != 0>;
+}
+
+// the flags a batch fixes for its sweeps
+inline unsigned fill_flags(const bialign_batch* b) {
+  return (b->dense ? F_DENSE : 0u) | (b->dense1 ? F_DENSE1 : 0u) | (b->lean ? F_LEAN : 0u) | (b->pack_now() ? F_PACK : 0u) |
+         (b->affine && b->prm.gap_opening_cost > 0 ? F_BETA_ANY : 0u);
+}
+// dynamic LDS of a TW-wave workgroup of the tiled sweeps
+template <int S, int TW>
+size_t fill_lds(const bialign_batch* b, bool affine) {
+  return (affine && S == 2 && TW == 8) ? b->lds_diet8 : b->lds_base + (size_t)TW * b->lds_per_wave;
+}
+
+// ---- affine sweeps
+template <int S, int TW, unsigned F>
 int launch_fill_affine_t(bialign_batch* b, const DeviceBatch& v, int first, int count, int gw) {
+  constexpr bool XCU = (F & F_XCU) != 0, PACK = (F & F_PACK) != 0;
   DeviceBatch w = v;
   w.order = v.order + first;
   w.team = gw;
   b->packed_layers = PACK;
   if (PACK) b->used_pack = true;
-  auto kern = fill_affine_kernel<S, BETA_NONPOS, TW, XCU, DENSE, LEAN, false, PACK, DENSE1>;
-  const size_t lds = (S == 2 && TW == 8) ? b->lds_diet8 : b->lds_base + (size_t)TW * b->lds_per_wave;
-  if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  if (XCU) {
-    if (b->d_prog.n < (size_t)count * PROG_WORDS) HIP_TRY(b->d_prog.alloc((size_t)count * PROG_WORDS));
-    HIP_TRY(hipMemsetAsync(b->d_prog.p, 0, (size_t)count * PROG_WORDS * sizeof(int32_t), b->eng->stream));
-    w.prog = b->d_prog.p;
-    w.spin_limit = b->xcu_spin_limit;
-    b->used_xcu = true;
-    if (int rc = xcu_serial_begin(b->eng)) return rc;
-  }
-  hipLaunchKernelGGL(kern, dim3(count * (XCU ? gw : 1)), dim3(64 * TW), lds, b->eng->stream, w);
-  const hipError_t launched = hipGetLastError();
-  if (XCU) {
-    const int rc = xcu_serial_end(b->eng);  // always: it releases the launch lock
-    if (launched == hipSuccess && rc) return rc;
-  }
-  HIP_TRY(launched);
-  return BIALIGN_OK;
+  b->last_team = XCU ? -TW * gw : TW;
+  const dim3 grid(count * (XCU ? gw : 1)), block(64 * TW);
+  if (XCU) return launch_team(b, fill_affine_of<S, TW, F>(), grid, block, fill_lds<S, TW>(b, true), w, count, true);
+  return launch(fill_affine_of<S, TW, F>(), grid, block, fill_lds<S, TW>(b, true), b->eng->stream, w);
 }
 
 template <int S, int TW, bool LEAN>
@@ -265,140 +395,71 @@ int launch_fill_affine_slim_t(bialign_batch* b, const DeviceBatch& v, int first,
   w.slim_code_bytes = (int32_t)b->lds_slim_codes;
   b->packed_layers = !LEAN;
   if (!LEAN) b->used_pack = true;
-  auto kern = fill_affine_slim_kernel<S, TW, PPW, LEAN>;
-  const size_t lds = b->lds_slim(TW);
-  if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((count + PPW - 1) / PPW), dim3(64 * 12), lds, b->eng->stream, w);
-  HIP_TRY(hipGetLastError());
-  return BIALIGN_OK;
+  b->last_team = TW;
+  return launch(fill_affine_slim_kernel<S, TW, PPW, LEAN>, dim3((count + PPW - 1) / PPW), dim3(64 * 12), b->lds_slim(TW),
+                b->eng->stream, w);
 }
 
 template <int S, bool LEAN>
 int launch_fill_affine_slim(bialign_batch* b, const DeviceBatch& v, int first, int count, int tw) {
-  if constexpr (S == 1) {
-    switch (tw) {
-      case 2: return launch_fill_affine_slim_t<S, 2, LEAN>(b, v, first, count);
-      case 3: return launch_fill_affine_slim_t<S, 3, LEAN>(b, v, first, count);
-      case 6: return launch_fill_affine_slim_t<S, 6, LEAN>(b, v, first, count);
-      case 12: return launch_fill_affine_slim_t<S, 12, LEAN>(b, v, first, count);
-    }
+  switch (tw) {
+    case 2: return launch_fill_affine_slim_t<S, 2, LEAN>(b, v, first, count);
+    case 3: return launch_fill_affine_slim_t<S, 3, LEAN>(b, v, first, count);
+    case 6: return launch_fill_affine_slim_t<S, 6, LEAN>(b, v, first, count);
+    case 12: return launch_fill_affine_slim_t<S, 12, LEAN>(b, v, first, count);
   }
   return fail(BIALIGN_E_UNSUPPORTED, "no three-waves-per-SIMD sweep for max_shift %d, team %d", S, tw);
 }
 
-// One-wave workgroups of the cross-CU kernel <S, LEAN> the device can hold at once, from the runtime's
-// occupancy calculation for the actual code object (registers, LDS): the cap of a cross-CU grid.
-template <int S, bool LEAN, int TW = 1, bool DENSE = false, bool DENSE1 = false>
-int xcu_resident_blocks(bialign_batch* b) {
-  int& cached = b->xcu_resident[(LEAN ? 1 : 0) + (TW == 8 ? 2 : 0)];  // (a batch is either DENSE or not)
-  if (cached >= 0) return cached;
-  cached = 0;
-  if constexpr ((DENSE || DENSE1 ? S <= 3 : true) && (TW == 1 || S == 2)) {
-    if (TW == 8 && !diet8_available(b)) return cached;
-    auto kern = fill_affine_kernel<S, true, TW, true, DENSE, LEAN, false, false, DENSE1>;
-    const size_t lds = TW == 8 ? b->lds_diet8 : b->lds_base + b->lds_per_wave;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      (void)hipGetLastError();
-      return cached;
-    }
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 64 * TW, lds) != hipSuccess) {
-      (void)hipGetLastError();
-      return cached;
-    }
-    cached = per_cu * b->eng->num_cu;
+// One-wave (TW = 8: eight-wave, the s=2 DIET layout) workgroups of the sweep's cross-CU kernel the device holds at
+// once; 0 where there is no such kernel.  Asked of the full-record kernel also when the sweep packs.
+template <int S, int TW, unsigned F>
+int xcu_resident_affine(bialign_batch* b) {
+  constexpr unsigned Q = (F & ~F_PACK) | F_XCU;
+  if constexpr (fill_affine_exists(S, TW, Q)) {
+    if (TW == 8 && !diet8_available(b)) return 0;
+    return xcu_resident_cached(b, ((F & F_LEAN) ? 1 : 0) + (TW == 8 ? 2 : 0), fill_affine_of<S, TW, Q>(), 64 * TW, fill_lds<S, TW>(b, true));
+  } else {
+    return 0;
   }
-  return cached;
 }
 
-// Dense-mu1 sweeps: the launch shapes of the dense-mu2 ones (one-wave cross-CU teams up to s=3, in-workgroup teams of
-// 4 and 2, one wave), full or LEAN records.
-template <int S, bool LEAN, bool DENSE>
-int launch_fill_affine_dense1(bialign_batch* b, const DeviceBatch& v, int first, int count) {
-  if (b->prm.gap_opening_cost > 0) {
-    b->last_team = 1;
-    return launch_fill_affine_t<S, false, 1, false, DENSE, LEAN, false, true>(b, v, first, count, 1);
+// One rung of the ladder: the TW-wave kernel (F_XCU in F: cross-CU teams of such workgroups), if it is in the
+// instantiation plan and the shape asks for at least that much.  True: launched, *rc is the outcome.
+template <int S, int TW, unsigned F>
+bool fill_affine_rung(bialign_batch* b, const DeviceBatch& v, int first, int count, const TeamShape& ts, int* rc) {
+  if constexpr (fill_affine_exists(S, TW, F)) {
+    constexpr bool XCU = (F & F_XCU) != 0;
+    if (XCU ? !(ts.gw > 1 && (TW == 1 || ts.tw == TW)) : ts.tw < TW) return false;
+    *rc = launch_fill_affine_t<S, TW, F>(b, v, first, count, XCU ? ts.gw : 1);
+    return true;
+  } else {
+    return false;
   }
-  const TeamShape ts = team_shape(b, first, count, !b->no_xcu ? xcu_resident_blocks<S, LEAN, 1, DENSE, true>(b) : 0, 0);
-  b->last_team = ts.waves() * (ts.gw > 1 ? -1 : 1);
-  if constexpr (S <= 3) {
-    if (ts.gw > 1) return launch_fill_affine_t<S, true, 1, true, DENSE, LEAN, false, true>(b, v, first, count, ts.gw);
-    b->last_team = std::min(ts.tw, 4);
-    if (ts.tw >= 4) return launch_fill_affine_t<S, true, 4, false, DENSE, LEAN, false, true>(b, v, first, count, 1);
-    if (ts.tw >= 2) return launch_fill_affine_t<S, true, 2, false, DENSE, LEAN, false, true>(b, v, first, count, 1);
-  }
-  b->last_team = 1;
-  return launch_fill_affine_t<S, true, 1, false, DENSE, LEAN, false, true>(b, v, first, count, 1);
 }
 
-template <int S, bool LEAN>
-int launch_fill_affine_l(bialign_batch* b, const DeviceBatch& v, int first, int count) {
-  if (b->dense1)  // dense mu1 (with or without dense mu2)
-    return b->dense ? launch_fill_affine_dense1<S, LEAN, true>(b, v, first, count)
-                    : launch_fill_affine_dense1<S, LEAN, false>(b, v, first, count);
-  if (b->prm.gap_opening_cost > 0) {  // rare: general-beta algebra, one wave per pair
-    b->last_team = 1;
-    return b->dense ? launch_fill_affine_t<S, false, 1, false, true, LEAN>(b, v, first, count, 1)
-                    : launch_fill_affine_t<S, false, 1, false, false, LEAN>(b, v, first, count, 1);
-  }
-  const bool xcu_ok = !b->no_xcu;
-  const TeamShape ts = b->dense ? team_shape(b, first, count, xcu_ok ? xcu_resident_blocks<S, LEAN, 1, true>(b) : 0, 0)
-                                : team_shape(b, first, count, xcu_ok ? xcu_resident_blocks<S, LEAN>(b) : 0,
-                                             xcu_ok ? xcu_resident_blocks<S, LEAN, 8>(b) : 0);
-  b->last_team = ts.waves() * (ts.gw > 1 ? -1 : 1);
-  if (ts.slim) return launch_fill_affine_slim<S, LEAN>(b, v, first, count, ts.tw);
-  if (b->dense) {  // dense-mu2 kernels: one-wave cross-CU teams, in-workgroup teams of 4 and 2, one wave
-    if constexpr (S >= 1 && S <= BIALIGN_MAX_SHIFT_PACKED && !LEAN) {
-      if (b->pack_now()) {
-        if (ts.gw > 1) return launch_fill_affine_t<S, true, 1, true, true, false, true>(b, v, first, count, ts.gw);
-        b->last_team = std::min(ts.tw, 4);
-        if (ts.tw >= 4) return launch_fill_affine_t<S, true, 4, false, true, false, true>(b, v, first, count, 1);
-        if (ts.tw >= 2) return launch_fill_affine_t<S, true, 2, false, true, false, true>(b, v, first, count, 1);
-        return launch_fill_affine_t<S, true, 1, false, true, false, true>(b, v, first, count, 1);
-      }
-    }
-    if constexpr (S <= 3) {
-      if (ts.gw > 1) return launch_fill_affine_t<S, true, 1, true, true, LEAN>(b, v, first, count, ts.gw);
-      b->last_team = std::min(ts.tw, 4);
-      if (ts.tw >= 4) return launch_fill_affine_t<S, true, 4, false, true, LEAN>(b, v, first, count, 1);
-      if (ts.tw >= 2) return launch_fill_affine_t<S, true, 2, false, true, LEAN>(b, v, first, count, 1);
-    }
-    b->last_team = 1;
-    return launch_fill_affine_t<S, true, 1, false, true, LEAN>(b, v, first, count, 1);
-  }
-  if constexpr (S >= 1 && S <= BIALIGN_MAX_SHIFT_PACKED && !LEAN) {
-    if (b->pack_now()) {  // same launch shapes, packed records
-      if constexpr (S == 2) {
-        if (ts.gw > 1 && ts.tw == 8) return launch_fill_affine_t<S, true, 8, true, false, false, true>(b, v, first, count, ts.gw);
-      }
-      if (ts.gw > 1) return launch_fill_affine_t<S, true, 1, true, false, false, true>(b, v, first, count, ts.gw);
-      if constexpr (S <= 2) {
-        if (ts.tw == 8) return launch_fill_affine_t<S, true, 8, false, false, false, true>(b, v, first, count, 1);
-      }
-      if (ts.tw >= 4) return launch_fill_affine_t<S, true, 4, false, false, false, true>(b, v, first, count, 1);
-      if (ts.tw >= 2) return launch_fill_affine_t<S, true, 2, false, false, false, true>(b, v, first, count, 1);
-      return launch_fill_affine_t<S, true, 1, false, false, false, true>(b, v, first, count, 1);
-    }
-  }
-  if constexpr (S == 2) {
-    if (ts.gw > 1 && ts.tw == 8) return launch_fill_affine_t<S, true, 8, true, false, LEAN>(b, v, first, count, ts.gw);
-  }
-  if (ts.gw > 1) return launch_fill_affine_t<S, true, 1, true, false, LEAN>(b, v, first, count, ts.gw);
-  if constexpr (S <= 2) {  // (s=2: the DIET layout)
-    if (ts.tw == 8) return launch_fill_affine_t<S, true, 8, false, false, LEAN>(b, v, first, count, 1);
-  }
-  if constexpr (S <= 3) {  // s >= 4 needs nearly all 512 registers of a SIMD lane: one wave per pair
-    if (ts.tw >= 4) return launch_fill_affine_t<S, true, 4, false, false, LEAN>(b, v, first, count, 1);
-    if (ts.tw >= 2) return launch_fill_affine_t<S, true, 2, false, false, LEAN>(b, v, first, count, 1);
-  }
-  return launch_fill_affine_t<S, true, 1, false, false, LEAN>(b, v, first, count, 1);
-}
-
+// The sweep of pairs order[first .. first+count): the team shape, then the first rung of "cross-CU eight-wave, cross-CU,
+// 8, 4, 2, 1" that exists for this (max_shift, form) and fits the shape.  bialign_batch::last_team is what was launched.
+// (team_shape() never returns more than exists: the dense forms, capped at four waves, report 1 at s >= 4 like the rest.)
 template <int S>
 int launch_fill_affine(bialign_batch* b, const DeviceBatch& v, int first, int count) {
-  return b->lean ? launch_fill_affine_l<S, true>(b, v, first, count) : launch_fill_affine_l<S, false>(b, v, first, count);
+  return with_flags<F_DENSE | F_LEAN | F_PACK | F_DENSE1 | F_BETA_ANY>(fill_flags(b), [&](auto flags) -> int {
+    constexpr unsigned F = decltype(flags)::value;
+    if constexpr (!fill_affine_exists(S, 1, F)) {
+      return fail(BIALIGN_E_UNSUPPORTED, "no affine sweep for max_shift %d in form %u", S, F);
+    } else {
+      TeamShape ts;  // general beta: one wave per pair
+      if constexpr (!(F & F_BETA_ANY)) ts = team_shape(b, first, count, xcu_resident_affine<S, 1, F>(b), xcu_resident_affine<S, 8, F>(b));
+      if constexpr (fill_slim_exists(S, F)) {
+        if (ts.slim) return launch_fill_affine_slim<S, (F & F_LEAN) != 0>(b, v, first, count, ts.tw);
+      }
+      int rc = BIALIGN_OK;
+      (void)(fill_affine_rung<S, 8, F | F_XCU>(b, v, first, count, ts, &rc) || fill_affine_rung<S, 1, F | F_XCU>(b, v, first, count, ts, &rc) ||
+             fill_affine_rung<S, 8, F>(b, v, first, count, ts, &rc) || fill_affine_rung<S, 4, F>(b, v, first, count, ts, &rc) ||
+             fill_affine_rung<S, 2, F>(b, v, first, count, ts, &rc) || fill_affine_rung<S, 1, F>(b, v, first, count, ts, &rc));
+      return rc;
+    }
+  });
 }
 
 // Lean traceback, one round: re-sweep the strip every unfinished pair's walk stands in ...
@@ -407,242 +468,109 @@ int launch_resweep_affine(bialign_batch* b, const DeviceBatch& v, int first, int
   DeviceBatch w = v;
   w.order = v.order + first;
   w.team = 1;
-  const size_t lds = b->lds_base + b->lds_per_wave;
-  auto go = [&](auto kern) -> int {
-    if (lds > 64 * 1024)
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(count * b->resw_k), dim3(64), lds, b->eng->stream, w);
-    HIP_TRY(hipGetLastError());
-    return BIALIGN_OK;
-  };
-  if (b->dense1) {
-    if (b->dense)
-      return b->prm.gap_opening_cost > 0 ? go(fill_affine_kernel<S, false, 1, false, true, false, true, false, true>)
-                                         : go(fill_affine_kernel<S, true, 1, false, true, false, true, false, true>);
-    return b->prm.gap_opening_cost > 0 ? go(fill_affine_kernel<S, false, 1, false, false, false, true, false, true>)
-                                       : go(fill_affine_kernel<S, true, 1, false, false, false, true, false, true>);
-  }
-  if (b->dense)
-    return b->prm.gap_opening_cost > 0 ? go(fill_affine_kernel<S, false, 1, false, true, false, true>)
-                                       : go(fill_affine_kernel<S, true, 1, false, true, false, true>);
-  return b->prm.gap_opening_cost > 0 ? go(fill_affine_kernel<S, false, 1, false, false, false, true>)
-                                     : go(fill_affine_kernel<S, true, 1, false, false, false, true>);
+  return with_flags<F_DENSE | F_DENSE1 | F_BETA_ANY>(fill_flags(b), [&](auto flags) -> int {
+    return launch(fill_affine_of<S, 1, decltype(flags)::value | F_RESW>(), dim3(count * b->resw_k), dim3(64), fill_lds<S, 1>(b, true),
+                  b->eng->stream, w);
+  });
 }
 
-// ... then walk through it.
+// ---- tracebacks: one wave per pair.  The kernel is named by what the batch holds; the score-only form stages nothing.
+inline unsigned trace_flags(const bialign_batch* b, bool do_trace) {
+  return (do_trace ? T_TRACE : 0u) | (b->dense1 && do_trace ? T_DENSE1 : 0u) | (b->packed_layers ? T_PACK : 0u);
+}
+template <typename... P>
+int launch_traceback_kernel(const bialign_batch* b, void (*kern)(P...), bool do_trace, const DeviceBatch& v, int first, int count) {
+  DeviceBatch w = v;
+  w.order = v.order + first;
+  return launch(kern, dim3(count), dim3(64), do_trace ? b->lds_trace : 0, b->eng->stream, w, count);
+}
+
+template <int S>
+int launch_traceback_affine(const bialign_batch* b, const DeviceBatch& v, int first, int count, bool do_trace) {
+  return with_flags<T_TRACE | T_PACK | T_DENSE1>(trace_flags(b, do_trace), [&](auto flags) -> int {
+    constexpr unsigned F = decltype(flags)::value;
+    if constexpr (traceback_exists(true, S, F)) return launch_traceback_kernel(b, traceback_affine_of<S, F>(), do_trace, v, first, count);
+    else return fail(BIALIGN_E_UNSUPPORTED, "no affine traceback for max_shift %d in form %u", S, F);
+  });
+}
+// ... the lean traceback's walk through the strip just re-swept
 template <int S>
 int launch_traceback_affine_strip(const bialign_batch* b, const DeviceBatch& v, int first, int count) {
-  DeviceBatch w = v;
-  w.order = v.order + first;
-  auto kern = b->dense1 ? traceback_affine_kernel<S, true, true, false, false, true> : traceback_affine_kernel<S, true, true>;
-  if (b->lds_trace > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_trace));
-  hipLaunchKernelGGL(kern, dim3(count), dim3(64), b->lds_trace, b->eng->stream, w, count);
-  HIP_TRY(hipGetLastError());
-  return BIALIGN_OK;
+  return b->dense1 ? launch_traceback_kernel(b, traceback_affine_of<S, T_TRACE | T_STRIP | T_DENSE1>(), true, v, first, count)
+                   : launch_traceback_kernel(b, traceback_affine_of<S, T_TRACE | T_STRIP>(), true, v, first, count);
 }
 
-template <int S>
-int launch_traceback_affine(const bialign_batch* b, const DeviceBatch& v, int first, int count,
-                            bool do_trace) {
-  DeviceBatch w = v;
-  w.order = v.order + first;
-  const int blocks = count;  // one wave per pair
-  if (b->dense1 && do_trace) {  // (the score-only form reads no scores: the LOOKUP kernel serves below)
-    auto kern = traceback_affine_kernel<S, true, false, false, false, true>;
-    if (b->lds_trace > 64 * 1024)
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)b->lds_trace));
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), b->lds_trace, b->eng->stream, w, count);
-    HIP_TRY(hipGetLastError());
-    return BIALIGN_OK;
-  }
-  if (b->lds_trace > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(traceback_affine_kernel<S, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_trace));
-  if constexpr (S >= 1 && S <= BIALIGN_MAX_SHIFT_PACKED) {
-    if (b->packed_layers) {
-      if (b->lds_trace > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(traceback_affine_kernel<S, true, false, false, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_trace));
-      if (do_trace)
-        hipLaunchKernelGGL((traceback_affine_kernel<S, true, false, false, true>), dim3(blocks), dim3(64), b->lds_trace,
-                           b->eng->stream, w, count);
-      else
-        hipLaunchKernelGGL((traceback_affine_kernel<S, false, false, false, true>), dim3(blocks), dim3(64), 0,
-                           b->eng->stream, w, count);
-      HIP_TRY(hipGetLastError());
-      return BIALIGN_OK;
-    }
-  }
-  if (do_trace)
-    hipLaunchKernelGGL((traceback_affine_kernel<S, true>), dim3(blocks), dim3(64), b->lds_trace, b->eng->stream, w, count);
-  else
-    hipLaunchKernelGGL((traceback_affine_kernel<S, false>), dim3(blocks), dim3(64), 0, b->eng->stream, w, count);
-  HIP_TRY(hipGetLastError());
-  return BIALIGN_OK;
-}
-
-template <int S, int TW, bool DENSE = false, bool LEAN = false, bool XCU = false, bool DENSE1 = false>
-int launch_fill_linear_t(bialign_batch* b, const DeviceBatch& v, int first, int count, int gw = 1) {
+// ---- one-layer sweeps
+template <int S, int TW, unsigned F>
+int launch_fill_linear_t(bialign_batch* b, const DeviceBatch& v, int first, int count, int gw) {
+  constexpr bool XCU = (F & F_XCU) != 0;
   DeviceBatch w = v;
   w.order = v.order + first;
   w.team = gw;
   b->packed_layers = false;
-  auto kern = fill_linear_kernel<S, TW, DENSE, LEAN, false, XCU, DENSE1>;
-  const size_t lds = b->lds_base + (size_t)TW * b->lds_per_wave;
-  if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  if (XCU) {  // as in launch_fill_affine_t
-    if (b->d_prog.n < (size_t)count * PROG_WORDS) HIP_TRY(b->d_prog.alloc((size_t)count * PROG_WORDS));
-    HIP_TRY(hipMemsetAsync(b->d_prog.p, 0, (size_t)count * PROG_WORDS * sizeof(int32_t), b->eng->stream));
-    w.prog = b->d_prog.p;
-    w.spin_limit = b->xcu_spin_limit;
-    b->used_xcu = true;
-    if (int rc = xcu_serial_begin(b->eng)) return rc;
-  }
-  hipLaunchKernelGGL(kern, dim3(count * (XCU ? gw : 1)), dim3(64 * TW), lds, b->eng->stream, w);
-  const hipError_t launched = hipGetLastError();
-  if (XCU) {
-    const int rc = xcu_serial_end(b->eng);
-    if (launched == hipSuccess && rc) return rc;
-  }
-  HIP_TRY(launched);
-  return BIALIGN_OK;
+  b->last_team = XCU ? -gw : TW;
+  const dim3 grid(count * (XCU ? gw : 1)), block(64 * TW);
+  if (XCU) return launch_team(b, fill_linear_of<S, TW, F>(), grid, block, fill_lds<S, TW>(b, false), w, count, true);
+  return launch(fill_linear_of<S, TW, F>(), grid, block, fill_lds<S, TW>(b, false), b->eng->stream, w);
 }
 
-// one-wave workgroups of the one-layer cross-CU kernel the device holds at once
-template <int S, bool LEAN, bool DENSE = false, bool DENSE1 = false>
-int xcu_resident_linear(bialign_batch* b) {
-  int& cached = b->xcu_resident[LEAN ? 1 : 0];
-  if (cached >= 0) return cached;
-  cached = 0;
-  auto kern = fill_linear_kernel<S, 1, DENSE, LEAN, false, true, DENSE1>;
-  const size_t lds = b->lds_base + b->lds_per_wave;
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-    (void)hipGetLastError();
-    return cached;
-  }
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 64, lds) != hipSuccess) {
-    (void)hipGetLastError();
-    return cached;
-  }
-  return cached = per_cu * b->eng->num_cu;
-}
-
-// dense mu1 (with or without dense mu2): one-wave cross-CU teams, in-workgroup teams of 2, one wave
-template <int S, bool LEAN, bool DENSE>
-int launch_fill_linear_dense1(bialign_batch* b, const DeviceBatch& v, int first, int count) {
-  const TeamShape ts = team_shape(b, first, count, !b->no_xcu ? xcu_resident_linear<S, LEAN, DENSE, true>(b) : 0);
-  b->last_team = ts.waves() * (ts.gw > 1 ? -1 : 1);
-  if (ts.gw > 1) return launch_fill_linear_t<S, 1, DENSE, LEAN, true, true>(b, v, first, count, ts.gw);
-  return ts.tw >= 2 ? launch_fill_linear_t<S, 2, DENSE, LEAN, false, true>(b, v, first, count)
-                    : launch_fill_linear_t<S, 1, DENSE, LEAN, false, true>(b, v, first, count);
-}
-
-template <int S, bool LEAN>
-int launch_fill_linear_l(bialign_batch* b, const DeviceBatch& v, int first, int count) {
-  if (b->dense1)
-    return b->dense ? launch_fill_linear_dense1<S, LEAN, true>(b, v, first, count)
-                    : launch_fill_linear_dense1<S, LEAN, false>(b, v, first, count);
-  const bool xcu_ok = !b->no_xcu;
-  const TeamShape ts = team_shape(b, first, count, !xcu_ok ? 0 : (b->dense ? xcu_resident_linear<S, LEAN, true>(b)
-                                                                             : xcu_resident_linear<S, LEAN>(b)));
-  b->last_team = ts.waves() * (ts.gw > 1 ? -1 : 1);
-  if (b->dense) {
-    if (ts.gw > 1) return launch_fill_linear_t<S, 1, true, LEAN, true>(b, v, first, count, ts.gw);
-    return ts.tw >= 2 ? launch_fill_linear_t<S, 2, true, LEAN>(b, v, first, count)
-                      : launch_fill_linear_t<S, 1, true, LEAN>(b, v, first, count);
-  }
-  if (ts.gw > 1) return launch_fill_linear_t<S, 1, false, LEAN, true>(b, v, first, count, ts.gw);
-  switch (ts.tw) {
-    case 8: return launch_fill_linear_t<S, 8, false, LEAN>(b, v, first, count);
-    case 4: return launch_fill_linear_t<S, 4, false, LEAN>(b, v, first, count);
-    case 2: return launch_fill_linear_t<S, 2, false, LEAN>(b, v, first, count);
-    default: return launch_fill_linear_t<S, 1, false, LEAN>(b, v, first, count);
+template <int S, int TW, unsigned F>
+bool fill_linear_rung(bialign_batch* b, const DeviceBatch& v, int first, int count, const TeamShape& ts, int* rc) {
+  if constexpr (fill_linear_exists(TW, F)) {
+    constexpr bool XCU = (F & F_XCU) != 0;
+    if (XCU ? ts.gw <= 1 : ts.tw < TW) return false;
+    *rc = launch_fill_linear_t<S, TW, F>(b, v, first, count, XCU ? ts.gw : 1);
+    return true;
+  } else {
+    return false;
   }
 }
 
+// as launch_fill_affine: cross-CU, 8, 4, 2, 1
 template <int S>
 int launch_fill_linear(bialign_batch* b, const DeviceBatch& v, int first, int count) {
-  return b->lean ? launch_fill_linear_l<S, true>(b, v, first, count) : launch_fill_linear_l<S, false>(b, v, first, count);
+  return with_flags<F_DENSE | F_LEAN | F_DENSE1>(fill_flags(b), [&](auto flags) -> int {
+    constexpr unsigned F = decltype(flags)::value;
+    const int resident = xcu_resident_cached(b, (F & F_LEAN) ? 1 : 0, fill_linear_of<S, 1, F | F_XCU>(), 64, fill_lds<S, 1>(b, false));
+    const TeamShape ts = team_shape(b, first, count, resident);
+    int rc = BIALIGN_OK;
+    (void)(fill_linear_rung<S, 1, F | F_XCU>(b, v, first, count, ts, &rc) || fill_linear_rung<S, 8, F>(b, v, first, count, ts, &rc) ||
+           fill_linear_rung<S, 4, F>(b, v, first, count, ts, &rc) || fill_linear_rung<S, 2, F>(b, v, first, count, ts, &rc) ||
+           fill_linear_rung<S, 1, F>(b, v, first, count, ts, &rc));
+    return rc;
+  });
 }
 
 template <int S>
 int launch_resweep_linear(bialign_batch* b, const DeviceBatch& v, int first, int count) {
   DeviceBatch w = v;
   w.order = v.order + first;
-  const size_t lds = b->lds_base + b->lds_per_wave;
-  auto go = [&](auto kern) -> int {
-    if (lds > 64 * 1024)
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(count * b->resw_k), dim3(64), lds, b->eng->stream, w);
-    HIP_TRY(hipGetLastError());
-    return BIALIGN_OK;
-  };
-  if (b->dense1)
-    return b->dense ? go(fill_linear_kernel<S, 1, true, false, true, false, true>)
-                    : go(fill_linear_kernel<S, 1, false, false, true, false, true>);
-  return b->dense ? go(fill_linear_kernel<S, 1, true, false, true>) : go(fill_linear_kernel<S, 1, false, false, true>);
+  return with_flags<F_DENSE | F_DENSE1>(fill_flags(b), [&](auto flags) -> int {
+    return launch(fill_linear_of<S, 1, decltype(flags)::value | F_RESW>(), dim3(count * b->resw_k), dim3(64), fill_lds<S, 1>(b, false),
+                  b->eng->stream, w);
+  });
 }
 
+template <int S>
+int launch_traceback_linear(const bialign_batch* b, const DeviceBatch& v, int first, int count, bool do_trace) {
+  return with_flags<T_TRACE | T_DENSE1>(trace_flags(b, do_trace), [&](auto flags) -> int {
+    constexpr unsigned F = decltype(flags)::value;
+    if constexpr (traceback_exists(false, S, F)) return launch_traceback_kernel(b, traceback_linear_of<S, F>(), do_trace, v, first, count);
+    else return fail(BIALIGN_E_UNSUPPORTED, "no one-layer traceback for max_shift %d in form %u", S, F);
+  });
+}
 template <int S>
 int launch_traceback_linear_strip(const bialign_batch* b, const DeviceBatch& v, int first, int count) {
-  DeviceBatch w = v;
-  w.order = v.order + first;
-  auto kern = b->dense1 ? traceback_linear_kernel<S, true, true, false, true> : traceback_linear_kernel<S, true, true>;
-  if (b->lds_trace > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_trace));
-  hipLaunchKernelGGL(kern, dim3(count), dim3(64), b->lds_trace, b->eng->stream, w, count);
-  HIP_TRY(hipGetLastError());
-  return BIALIGN_OK;
-}
-
-template <int S>
-int launch_traceback_linear(const bialign_batch* b, const DeviceBatch& v, int first, int count,
-                            bool do_trace) {
-  DeviceBatch w = v;
-  w.order = v.order + first;
-  const int blocks = count;  // one wave per pair
-  if (b->dense1 && do_trace) {  // (the score-only form reads no scores: the LOOKUP kernel serves below)
-    auto kern = traceback_linear_kernel<S, true, false, false, true>;
-    if (b->lds_trace > 64 * 1024)
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)b->lds_trace));
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), b->lds_trace, b->eng->stream, w, count);
-    HIP_TRY(hipGetLastError());
-    return BIALIGN_OK;
-  }
-  if (b->lds_trace > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(traceback_linear_kernel<S, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->lds_trace));
-  if (do_trace)
-    hipLaunchKernelGGL((traceback_linear_kernel<S, true>), dim3(blocks), dim3(64), b->lds_trace, b->eng->stream, w, count);
-  else
-    hipLaunchKernelGGL((traceback_linear_kernel<S, false>), dim3(blocks), dim3(64), 0, b->eng->stream, w, count);
-  HIP_TRY(hipGetLastError());
-  return BIALIGN_OK;
+  return b->dense1 ? launch_traceback_kernel(b, traceback_linear_of<S, T_TRACE | T_STRIP | T_DENSE1>(), true, v, first, count)
+                   : launch_traceback_kernel(b, traceback_linear_of<S, T_TRACE | T_STRIP>(), true, v, first, count);
 }
 
 template <int S, int NL>
 int launch_dump(const bialign_batch* b, const DeviceBatch& v, int pid, int32_t* d_out) {
   if constexpr (S >= 1 && S <= BIALIGN_MAX_SHIFT_PACKED && NL == 9) {
-    if (b->packed_layers) {
-      hipLaunchKernelGGL((dump_layers_kernel<S, NL, true>), dim3(256), dim3(256), 0, b->eng->stream, v, pid, d_out);
-      HIP_TRY(hipGetLastError());
-      return BIALIGN_OK;
-    }
+    if (b->packed_layers) return launch(dump_layers_kernel<S, NL, true>, dim3(256), dim3(256), 0, b->eng->stream, v, pid, d_out);
   }
-  hipLaunchKernelGGL((dump_layers_kernel<S, NL>), dim3(256), dim3(256), 0, b->eng->stream, v, pid, d_out);
-  HIP_TRY(hipGetLastError());
-  return BIALIGN_OK;
+  return launch(dump_layers_kernel<S, NL>, dim3(256), dim3(256), 0, b->eng->stream, v, pid, d_out);
 }
 
 // ---- wide-band path (max_shift above BIALIGN_MAX_SHIFT_TILED, bialign_wide.hpp): runtime band width,

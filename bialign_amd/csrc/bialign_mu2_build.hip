@@ -26,10 +26,8 @@ int launch_build_mu2(bialign_batch* b, int first, int count) {
     const int64_t tiles = (int64_t)((d.m + 63) / 64) * ((d.n + MU2_ROWS - 1) / MU2_ROWS);
     groups = std::max(groups, (tiles + MU2_WAVES - 1) / MU2_WAVES);
   }
-  hipLaunchKernelGGL(build_mu2_kernel, dim3(count, (unsigned)std::min<int64_t>(groups, MU2_MAX_GRID_Y)), dim3(64 * MU2_WAVES),
-                     0, b->eng->stream, a);
-  HIP_TRY(hipGetLastError());
-  return BIALIGN_OK;
+  return launch(build_mu2_kernel, dim3(count, (unsigned)std::min<int64_t>(groups, MU2_MAX_GRID_Y)), dim3(64 * MU2_WAVES), 0,
+                b->eng->stream, a);
 }
 
 }  // namespace bialign

@@ -31,9 +31,9 @@ __device__ __forceinline__ TraceInputs stage_trace_inputs(const DeviceBatch& A, 
   int32_t* s1 = smem;
   int32_t* s2 = s1 + k1 * k1;
   uint8_t* sa = reinterpret_cast<uint8_t*>(s2 + k2 * k2);
-  uint8_t* ca = sa + (D1 ? 0 : ((n + 3) & ~3));
-  uint8_t* sb = ca + ((n + 3) & ~3);
-  uint8_t* cb = sb + (D1 ? 0 : ((m + 3) & ~3));
+  uint8_t* ca = sa + (D1 ? 0 : code_pad(n));
+  uint8_t* sb = ca + code_pad(n);
+  uint8_t* cb = sb + (D1 ? 0 : code_pad(m));
   for (int t = threadIdx.x; t < k1 * k1; t += 64) s1[t] = A.s1[t];
   for (int t = threadIdx.x; t < k2 * k2; t += 64) s2[t] = A.s2[t];
   for (int t = threadIdx.x; t < n; t += 64) {

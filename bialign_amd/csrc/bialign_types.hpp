@@ -8,6 +8,10 @@ constexpr int32_t SENT = -(1 << 30) - (1 << 29);    // "guard failed" marker
 constexpr int32_t THRESH = -(1 << 30) - (1 << 28);  // below: no valid case
 constexpr int NCOL = 65;                            // 64 lanes + 1 sentinel column
 constexpr int PROG_WORDS = 256;                     // cross-CU teams: progress words per pair = largest team
+constexpr int LDS_PROG_WORDS = 16;                  // in-workgroup teams: progress words of a workgroup, in LDS
+constexpr int XCH_ROWS = 12;                        // affine sweeps: exchange rows per lattice point that go through LDS
+// Bytes one array of a molecule's codes takes in LDS: whole dwords, `guard` bytes around (B's codes in the sweeps: Geo<S>::PADB)
+__host__ __device__ constexpr int code_pad(int len, int guard = 0) { return (len + 2 * guard + 3) & ~3; }
 typedef int v4i __attribute__((ext_vector_type(4)));
 
 struct PairDesc {
