@@ -34,6 +34,7 @@ class Params(ctypes.Structure):
 
 BATCH_SCORE_ONLY = 1  # BIALIGN_BATCH_SCORE_ONLY
 BATCH_LEAN_TRACE = 2  # BIALIGN_BATCH_LEAN_TRACE
+BATCH_LEVEL_TRACE = 4  # BIALIGN_BATCH_LEVEL_TRACE
 
 
 class Scoring(ctypes.Structure):

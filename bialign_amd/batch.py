@@ -75,18 +75,27 @@ def encode_pairs(pairs, params):
 
 
 def make_batch(pairs, params, engine=None, hbm_budget_bytes=0, recurrence=0, mu2_dense=None,
-               score_only=False, lean_trace=False, mu1_dense=None):
-    """``mu1_dense`` / ``mu2_dense``: optional lists of one (len A, len B) int table per pair (engine.Batch)."""
+               score_only=False, lean_trace=False, mu1_dense=None, level_trace=False):
+    """``mu1_dense`` / ``mu2_dense``: optional lists of one (len A, len B) int table per pair (engine.Batch).
+    ``level_trace``: full results from checkpointed levels, for bands beyond the tiled kernels (engine.Batch)."""
+    _check_storage(score_only, lean_trace, level_trace)
     from .engine import Batch, default_engine  # loads the HIP library (no CPU fallback)
     model, fb = encode_flat(pairs, params)
     return Batch(engine or default_engine(), fb, None, model.s1, model.s2,
                  params["gap_opening_cost"], params["gap_cost"], params["shift_cost"],
                  params["max_shift"], hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence,
-                 mu2_dense=mu2_dense, score_only=score_only, lean_trace=lean_trace, mu1_dense=mu1_dense)
+                 mu2_dense=mu2_dense, score_only=score_only, lean_trace=lean_trace, mu1_dense=mu1_dense,
+                 level_trace=level_trace)
+
+
+def _check_storage(score_only, lean_trace, level_trace):
+    """The storage modes that exclude each other, refused before the library is loaded or called."""
+    if level_trace and (score_only or lean_trace):
+        raise ValueError("level_trace excludes score_only and lean_trace")
 
 
 def make_feature_batch(molecules, pair_index, params, engine=None, hbm_budget_bytes=0, recurrence=0,
-                       score_only=False, lean_trace=False, mu1_dense=None):
+                       score_only=False, lean_trace=False, mu1_dense=None, level_trace=False):
     """Batch with mu2 in FEATURE form (include/bialign.h, bialign_features): RNA molecules with real-valued
     structure features, e.g. from predicted base-pair probabilities.  ``molecules``: a list of
     ``(seq, (up, down, unp))``, three numbers per residue as ``scoring.rna_features`` makes them; ``pair_index``: a
@@ -96,6 +105,7 @@ def make_feature_batch(molecules, pair_index, params, engine=None, hbm_budget_by
     called: an index outside ``molecules``, ragged or mis-sized feature arrays, a NaN or infinite feature, and
     ValueError("math domain error") for a negative one."""
     from .scoring import check_features
+    _check_storage(score_only, lean_trace, level_trace)
     molecules = list(molecules)
     pair_index = [(int(ia), int(ib)) for ia, ib in pair_index]
     if not molecules or not pair_index:
@@ -120,7 +130,7 @@ def make_feature_batch(molecules, pair_index, params, engine=None, hbm_budget_by
     return Batch(engine or default_engine(), fb, None, model.s1, model.s2,
                  params["gap_opening_cost"], params["gap_cost"], params["shift_cost"],
                  params["max_shift"], hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence,
-                 score_only=score_only, lean_trace=lean_trace, mu1_dense=mu1_dense,
+                 score_only=score_only, lean_trace=lean_trace, mu1_dense=mu1_dense, level_trace=level_trace,
                  mu2_features=(int(params["structure_weight"]), flat, flat))
 
 

@@ -341,6 +341,22 @@ int lean_traceback_rounds(bialign_batch* b, const DeviceBatch& v, int first, int
   });
 }
 
+// Level-checkpointed traceback of one chunk (bialign_wide.hpp): as many (segment sweep, walk) rounds as its longest pair
+// has segments; every pair starts at its own top segment and drops out when its walk has ended.
+int level_traceback_rounds(bialign_batch* b, const DeviceBatch& v, int first, int count) {
+  HIP_TRY(hipMemsetAsync(b->d_tstate.p, 0, sizeof(TraceState) * b->npairs, b->eng->stream));
+  int rounds = 0;
+  for (int t = first; t < first + count; ++t) {
+    const PairDesc& d = b->pairs[b->order[t]];
+    rounds = std::max(rounds, wide_segments(d.n, d.m, b->wide_seg));
+  }
+  for (int r = 0; r < rounds; ++r) {
+    if (int rc = launch_segment_wide(b, v, first, count)) return rc;
+    if (int rc = launch_traceback_level(b, v, first, count)) return rc;
+  }
+  return BIALIGN_OK;
+}
+
 int launch_traceback(const bialign_batch* b, const DeviceBatch& v, int first, int count, bool do_trace) {
   if (b->wide) return launch_traceback_wide(b, v, first, count, do_trace);
   return with_shift(b, "traceback", [&](auto s) {
@@ -527,11 +543,18 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
   b->lean_trace = (prm->flags & BIALIGN_BATCH_LEAN_TRACE) != 0;
   b->lean = b->lean_trace || (prm->flags & BIALIGN_BATCH_SCORE_ONLY) != 0;
   b->wide = prm->max_shift > BIALIGN_MAX_SHIFT_TILED;  // bialign_wide.hpp: anti-diagonal path, all layers in HBM
+  if (prm->flags & BIALIGN_BATCH_LEVEL_TRACE) {
+    if (b->lean) return fail(BIALIGN_E_INVALID, "LEVEL_TRACE excludes SCORE_ONLY and LEAN_TRACE");
+    if (!b->wide)
+      return fail(BIALIGN_E_UNSUPPORTED, "LEVEL_TRACE exists for max_shift > %d only: use LEAN_TRACE for narrower bands",
+                  BIALIGN_MAX_SHIFT_TILED);
+  }
   // wide bands: score-only batches of the affine recurrence keep just the ring of derived values (bialign_wide.hpp);
   // the memory-lean traceback and the one-layer recurrence's score-only form exist for the tiled sweeps only
   if (b->wide && b->lean && (b->lean_trace || !b->affine))
     return fail(BIALIGN_E_UNSUPPORTED, "LEAN_TRACE, and SCORE_ONLY of the non-affine recurrence, exist for max_shift <= %d only",
                 BIALIGN_MAX_SHIFT_TILED);
+  if (prm->flags & BIALIGN_BATCH_LEVEL_TRACE) b->lean = b->level_trace = true;  // (no full layers: what `lean` says)
   if (b->dense && !b->feat && !pr->mu2_off) return fail(BIALIGN_E_INVALID, "mu2_dense given without mu2_off");
   if (!b->dense && (!pr->cls_a || !pr->cls_b)) return fail(BIALIGN_E_INVALID, "cls_a / cls_b are NULL (LOOKUP form)");
   if (b->dense1 && !pr->mu1_off) return fail(BIALIGN_E_INVALID, "mu1_dense given without mu1_off");
@@ -671,6 +694,11 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
   auto size_pairs = [&]() {
     for (int p = 0; p < pr->npairs; ++p) {
       PairDesc& d = b->pairs[p];
+      if (b->wide && b->level_trace) {  // checkpoints, one segment's scratch, the ring (bialign_wide.hpp)
+        d.scratch_off = wide_ckpt_dwords(d.n, d.m, S, b->wide_seg, b->NL);  // relative to layer_off until the chunk layout is fixed
+        pair_dwords[p] = wide_level_pair_dwords(d.n, d.m, S, b->wide_seg, b->NL);
+        continue;
+      }
       if (b->wide) {  // reference-order layers, every band slot of every (i, j); none at all for a score-only batch
         pair_dwords[p] = b->lean ? 16 : wide_pair_dwords(d.n, d.m, S, b->NL);
         continue;
@@ -701,7 +729,22 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
     for (size_pairs(); b->resw_k > 1 && max_need() > budget_dw; size_pairs())
       b->resw_k /= 2;
   };
+  // level-checkpointed traceback: the segment length C that makes the largest pair's region smallest -- (C + 5) levels
+  // of scratch and 5 per checkpoint, about 5 L / C of them: C ~ sqrt(5 L) -- one C for the whole batch
+  auto pick_wide_seg = [&]() {
+    int big = 0;
+    for (int p = 1; p < pr->npairs; ++p)
+      if (wide_pair_dwords(b->pairs[p].n, b->pairs[p].m, S, b->NL) > wide_pair_dwords(b->pairs[big].n, b->pairs[big].m, S, b->NL)) big = p;
+    const int n = b->pairs[big].n, m = b->pairs[big].m, L = 2 * (n + m);
+    int64_t best = INT64_MAX;
+    for (int C = WIDE_SEG_MIN; C <= std::max(WIDE_SEG_MIN, L); ++C) {
+      const int64_t levels = wide_scratch_levels(n, m, C) + (int64_t)WIDE_RING * (wide_segments(n, m, C) - 1);
+      if (levels < best) best = levels, b->wide_seg = C;
+    }
+    if (const char* e = getenv("BIALIGN_WIDE_SEG")) b->wide_seg = std::max(WIDE_SEG_MIN, atoi(e));  // tests
+  };
   if (b->lean_trace) pick_resw_k();
+  if (b->level_trace) pick_wide_seg();
   size_pairs();
   // A pair whose full layers exceed the budget is served from reduced storage instead of failing
   // (memory-lean traceback, ~1.3x the time).
@@ -718,6 +761,11 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
     b->lean = b->lean_trace = true;
     b->pack = false;
     pick_resw_k();
+  }
+  if (!b->lean && b->wide && max_need() > budget_dw) {  // ... wide bands: from checkpointed levels (bialign_wide.hpp)
+    b->lean = b->level_trace = true;
+    pick_wide_seg();
+    size_pairs();
   }
   b->full_dwords.resize(pr->npairs);
   for (int p = 0; p < pr->npairs; ++p) b->full_dwords[p] = b->wide ? pair_dwords[p] : (int64_t)b->pairs[p].G * geo.recdw;
@@ -828,7 +876,7 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
             layer_dw * 4.0 / (1 << 30), layer_dw * 4.0 / ms / 1e6);
   }
   HIP_TRY(b->d_scores.alloc(pr->npairs));
-  if (b->lean_trace) HIP_TRY(b->d_tstate.alloc(pr->npairs));
+  if (b->lean_trace || b->level_trace) HIP_TRY(b->d_tstate.alloc(pr->npairs));
   HIP_TRY(b->d_tlen.alloc(pr->npairs));
   HIP_TRY(b->d_complete.alloc(pr->npairs));
   HIP_TRY(b->d_err.alloc(1));
@@ -945,7 +993,7 @@ int bialign_batch_get_info(const bialign_batch* b, bialign_batch_info* info) {
   info->layer_bytes = b->cells * 4 * b->NL;
   info->hbm_layer_bytes = b->max_chunk_dwords * 4;
   info->trace_bytes = b->trace_bytes;
-  info->storage = b->lean_trace ? BIALIGN_BATCH_LEAN_TRACE : (b->lean ? BIALIGN_BATCH_SCORE_ONLY : 0);
+  info->storage = b->level_trace ? BIALIGN_BATCH_LEVEL_TRACE : (b->lean_trace ? BIALIGN_BATCH_LEAN_TRACE : (b->lean ? BIALIGN_BATCH_SCORE_ONLY : 0));
   info->reserved = 0;
   return BIALIGN_OK;
 }
@@ -953,7 +1001,7 @@ int bialign_batch_get_info(const bialign_batch* b, bialign_batch_info* info) {
 // Enqueue one run of the batch on the engine's stream (all chunks: fill, then traceback).
 static int enqueue_run(bialign_batch* b, uint32_t flags) {
   HIP_TRY(hipSetDevice(b->eng->device));
-  const bool do_trace = !(flags & BIALIGN_RUN_FILL_ONLY) && (!b->lean || b->lean_trace);
+  const bool do_trace = !(flags & BIALIGN_RUN_FILL_ONLY) && (!b->lean || b->lean_trace || b->level_trace);
   const DeviceBatch v = b->view();
   hipStream_t st = b->eng->stream;
   b->timing = bialign_timing{};
@@ -994,6 +1042,9 @@ static int enqueue_run(bialign_batch* b, uint32_t flags) {
       if (rc) return rc;
     } else if (b->lean_trace && do_trace) {
       rc = lean_traceback_rounds(b, v, first, count);
+      if (rc) return rc;
+    } else if (b->level_trace && do_trace) {
+      rc = level_traceback_rounds(b, v, first, count);
       if (rc) return rc;
     }
     HIP_TRY(hipEventRecord(b->evs[3 * c + 2], st));
@@ -1086,7 +1137,7 @@ int bialign_batch_get_traces(const bialign_batch* b, uint8_t* trace, int64_t* tr
                              int32_t* complete) {
   if (!b || !trace || !trace_off || !trace_len || !complete) return fail(BIALIGN_E_INVALID, "NULL argument");
   if (int rc = bialign_batch_wait(const_cast<bialign_batch*>(b))) return rc;
-  if (b->lean && !b->lean_trace)
+  if (b->lean && !b->lean_trace && !b->level_trace)
     return fail(BIALIGN_E_INVALID, "batch was created with BIALIGN_BATCH_SCORE_ONLY: it holds no layers to trace back");
   if (!b->ran || !b->ran_trace) return fail(BIALIGN_E_INVALID, "no traceback has been run on this batch");
   HIP_TRY(hipSetDevice(b->eng->device));
@@ -1101,7 +1152,7 @@ int bialign_batch_dump_layers(bialign_batch* b, int32_t pair, int32_t* out) {
   if (!b || !out) return fail(BIALIGN_E_INVALID, "NULL argument");
   if (pair < 0 || pair >= b->npairs) return fail(BIALIGN_E_INVALID, "pair %d out of range", pair);
   if (int rc = bialign_batch_wait(b)) return rc;
-  if (b->lean) return fail(BIALIGN_E_INVALID, "batch was created with reduced layer storage (SCORE_ONLY / LEAN_TRACE): it holds no full layers");
+  if (b->lean) return fail(BIALIGN_E_INVALID, "batch was created with reduced layer storage (SCORE_ONLY / LEAN_TRACE / LEVEL_TRACE): it holds no full layers");
   HIP_TRY(hipSetDevice(b->eng->device));
   hipStream_t st = b->eng->stream;
   // one-pair launch out of the regular launch order (team shape and layer offset are the pair's own)

@@ -148,6 +148,10 @@ struct bialign_batch {
   bool wide = false;        // max_shift above the tiled kernels: anti-diagonal path (bialign_wide.hpp), reference-order layers
   bool lean = false;        // LEAN records: the sweep keeps only the strip-bottom rows
   bool lean_trace = false;  // ... and tracebacks re-sweep one strip at a time into a scratch area
+  // Level-checkpointed traceback of the wide-band path (BIALIGN_BATCH_LEVEL_TRACE, bialign_wide.hpp): `lean` is set too
+  // (no full layers); a pair's region holds checkpoints, the scratch of one segment of wide_seg levels, and the ring.
+  bool level_trace = false;
+  int wide_seg = 0;
   DevBuf<TraceState> d_tstate;
   int resw_k = 1;           // strips re-swept and walked per round (more when the batch has few pairs)
   int k1 = 0, k2 = 0;
@@ -182,7 +186,7 @@ struct bialign_batch {
     v.dense_forms = (dense ? 1 : 0) | (dense1 ? 2 : 0);
     v.scratch = d_layers.p;  // a pair's scratch records follow its LEAN records in the same buffer
     v.tstate = d_tstate.p;
-    v.resw_k = resw_k;
+    v.resw_k = level_trace ? wide_seg : resw_k;
     v.wide_s = S;
     v.prio_mode = getenv("BIALIGN_PRIO") ? atoi(getenv("BIALIGN_PRIO")) : 1;
     v.spin_limit = 1 << 20;  // waves of one workgroup are co-resident by construction: a timeout there is a bug
@@ -311,6 +315,7 @@ enum TraceFlags : unsigned {
   T_WIDE = 4,    // wide-band layers (bialign_wide.hpp)
   T_PACK = 8,    // packed records (affine)
   T_DENSE1 = 16, // mu1 from dense tables
+  T_LEVEL = 32,  // level-checkpointed traceback: one segment's walk through the level-major scratch (bialign_wide.hpp)
 };
 
 // The instantiation plan: which sweeps exist, as (max_shift, waves per workgroup, flags).
@@ -333,6 +338,7 @@ constexpr bool fill_linear_exists(int TW, unsigned F) {
 constexpr bool fill_slim_exists(int S, unsigned F) { return S == 1 && (F == F_LEAN || F == F_PACK); }
 constexpr bool traceback_exists(bool affine, int S, unsigned F) {
   if ((F & T_PACK) && (!affine || S < 1 || S > BIALIGN_MAX_SHIFT_PACKED || (F & ~(T_PACK | T_TRACE)))) return false;
+  if (F & T_LEVEL) return S == 0 && (F & ~T_DENSE1) == (T_LEVEL | T_TRACE);
   if (F & T_STRIP) return (F & T_TRACE) && !(F & T_WIDE);
   return !(F & T_DENSE1) || (F & T_TRACE);  // (without the walk no score is read: the LOOKUP kernels serve)
 }
@@ -351,12 +357,13 @@ auto fill_linear_of() {
 template <int S, unsigned F>
 auto traceback_affine_of() {
   static_assert(traceback_exists(true, S, F), "not in the instantiation plan");
-  return traceback_affine_kernel<S, (F & T_TRACE) != 0, (F & T_STRIP) != 0, (F & T_WIDE) != 0, (F & T_PACK) != 0, (F & T_DENSE1) != 0>;
+  return traceback_affine_kernel<S, (F & T_TRACE) != 0, (F & T_STRIP) != 0, (F & T_WIDE) != 0, (F & T_PACK) != 0, (F & T_DENSE1) != 0,
+                                 (F & T_LEVEL) != 0>;
 }
 template <int S, unsigned F>
 auto traceback_linear_of() {
   static_assert(traceback_exists(false, S, F), "not in the instantiation plan");
-  return traceback_linear_kernel<S, (F & T_TRACE) != 0, (F & T_STRIP) != 0, (F & T_WIDE) != 0, (F & T_DENSE1) != 0>;
+  return traceback_linear_kernel<S, (F & T_TRACE) != 0, (F & T_STRIP) != 0, (F & T_WIDE) != 0, (F & T_DENSE1) != 0, (F & T_LEVEL) != 0>;
 }
 
 // the flags a batch fixes for its sweeps
@@ -577,6 +584,9 @@ int launch_dump(const bialign_batch* b, const DeviceBatch& v, int pid, int32_t* 
 //      one translation unit (bialign_wide.hip) for all of it
 int launch_fill_wide(bialign_batch* b, const DeviceBatch& v, int first, int count);
 int launch_traceback_wide(const bialign_batch* b, const DeviceBatch& v, int first, int count, bool do_trace);
+// level-checkpointed traceback, one round: sweep the segment every unfinished pair's walk stands in, then walk through it
+int launch_segment_wide(bialign_batch* b, const DeviceBatch& v, int first, int count);
+int launch_traceback_level(const bialign_batch* b, const DeviceBatch& v, int first, int count);
 int launch_dump_wide(const bialign_batch* b, const DeviceBatch& v, int pid, int32_t* d_out);
 
 // ---- instantiation plan: kind 0 = affine fill (the big kernels), kind 1 = everything else

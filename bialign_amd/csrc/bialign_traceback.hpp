@@ -65,11 +65,16 @@ __device__ __forceinline__ int wave_min16(int v) {  // min over lanes 0..15, val
 //   value A.wide_s and the layers lie in the reference's own order; S is then a dummy (0).
 //   PACK: the sweep stored packed records in interior steps (Pack<S>).
 //   D1: mu1 from the pair's dense table (DeviceBatch::dense_forms bit 1), mu2 dense if bit 0 is set.
-template <int S, bool DO_TRACE, bool STRIP = false, bool WIDE = false, bool PACK = false, bool D1 = false>
+//   LEVEL (level-checkpointed traceback of the wide-band path, bialign_wide.hpp): the walk continues from the
+//   pair's TraceState through ONE segment of levels -- the one fill_wide_*_kernel<.., WIDE_SEG> has just swept
+//   into the pair's scratch, addressed by level -- while every candidate of its point (1..4 levels down) lies
+//   there; the band half-width is A.wide_s and S a dummy (0), as for WIDE.
+template <int S, bool DO_TRACE, bool STRIP = false, bool WIDE = false, bool PACK = false, bool D1 = false, bool LEVEL = false>
 __global__ void __launch_bounds__(64) traceback_affine_kernel(const DeviceBatch A, int npairs) {
   static_assert(!WIDE || !STRIP, "no lean traceback on the wide-band path");
   static_assert(!PACK || (!WIDE && !STRIP), "packed records: full-storage tiled sweeps");
-  const int SR = WIDE ? A.wide_s : S;  // band half-width
+  static_assert(!LEVEL || (DO_TRACE && !WIDE && !STRIP && !PACK), "level traceback: a form of its own");
+  const int SR = (WIDE || LEVEL) ? A.wide_s : S;  // band half-width
   const int pid = A.order[blockIdx.x];
   const PairDesc pd = A.pairs[pid];
   const int n = pd.n, m = pd.m;
@@ -81,15 +86,21 @@ __global__ void __launch_bounds__(64) traceback_affine_kernel(const DeviceBatch 
   extern __shared__ __align__(16) int32_t smem[];
 
   TraceState ts{};
-  if (STRIP) {
+  if (STRIP || LEVEL) {
     ts = A.tstate[pid];
     if (ts.done) return;
   }
   const int Q = STRIP ? (ts.started ? ts.strip : pd.NS - 1) : 0;
   const int Qlo = STRIP ? max(Q - A.resw_k + 1, 0) : 0;  // strips Qlo..Q sit in the scratch slots Q-sp
   const int64_t sstride = (int64_t)(m + Geo<S>::MAXOFF + 1) * Rec<S, 9>::RECDW;
+  // LEVEL: the segment in the scratch and its lowest level
+  const int seg = LEVEL ? wide_segment_of(ts, n, m, A.resw_k) : 0, seg_base = LEVEL ? wide_seg_base(seg, A.resw_k) : 0;
   // layer value (state ss) of lattice point (pi, pj, a, b)
   auto cell = [&](int pi, int pj, int a, int b, int ss) -> int {
+    if (LEVEL) {  // [level - base][i][a][b/2][12]
+      const int WR = 2 * SR + 1, lev = 2 * (pi + pj) + a + b - 2 * SR;
+      return A.scratch[pd.scratch_off + ((lev - seg_base) * wide_level_points(n, SR) + (int64_t)(pi * WR + a) * ((WR + 1) / 2) + (b >> 1)) * 12 + ss];
+    }
     if (WIDE) return lay[pd.layer_off + wide_dword(m, 2 * SR + 1, 9, pi, pj, a, b, ss)];
     if (PACK) return packed_cell<S>(lay, pd, pi, pj, a, b, ss);
     if (!STRIP) return lay[cell_dword<S, 9>(pd, pi, pj, a, b, ss)];
@@ -103,7 +114,7 @@ __global__ void __launch_bounds__(64) traceback_affine_kernel(const DeviceBatch 
 
   int i = n, j = m, k = n, l = m, d0 = 0, d1 = 0, len = 0, complete = 0;
   int st = 0, cur = 0;
-  if (!STRIP || !ts.started) {
+  if (!(STRIP || LEVEL) || !ts.started) {
     // pyx:573-582: best end layer, first one with the least shift
     const int endv = c < 9 ? cell(n, m, SR, SR, c) : -BIG;
     const int best = __builtin_amdgcn_readfirstlane(-wave_min16(-endv));
@@ -127,6 +138,7 @@ __global__ void __launch_bounds__(64) traceback_affine_kernel(const DeviceBatch 
   while (true) {
     if (i == 0 && j == 0 && k == 0 && l == 0 && st == 8) { complete = 1; break; }
     if (STRIP && i < Qlo * RR) { finished = false; break; }  // above the re-swept strips: next round
+    if (LEVEL && seg > 0 && i + j + k + l < seg_base + WIDE_SEG_OVERLAP) { finished = false; break; }  // a candidate may lie below the scratch
     const int hU = st / 3, hV = st - 3 * hU;
     const int u0 = hU >= 1, u1 = hU != 1, v0 = hV >= 1, v1 = hV != 1;
     const int mu1 = (i >= 1 && j >= 1)
@@ -169,11 +181,11 @@ __global__ void __launch_bounds__(64) traceback_affine_kernel(const DeviceBatch 
     ++len;
     i -= q0; j -= q1; k -= q2; l -= q3;
   }
-  if (STRIP && !finished) {  // hand over to the next round
+  if ((STRIP || LEVEL) && !finished) {  // hand over to the next round
     if (c == 0) {
       TraceState nx;
       nx.i = i; nx.j = j; nx.k = k; nx.l = l; nx.st = st; nx.cur = cur; nx.d0 = d0; nx.d1 = d1;
-      nx.len = len; nx.strip = Qlo - 1; nx.started = 1; nx.done = 0;
+      nx.len = len; nx.strip = LEVEL ? seg - 1 : Qlo - 1; nx.started = 1; nx.done = 0;
       A.tstate[pid] = nx;
     }
     return;
@@ -189,7 +201,7 @@ __global__ void __launch_bounds__(64) traceback_affine_kernel(const DeviceBatch 
   if (c == 0) {
     A.trace_len[pid] = len;
     A.complete[pid] = complete;
-    if (STRIP) {
+    if (STRIP || LEVEL) {
       ts.done = 1;
       ts.started = 1;
       A.tstate[pid] = ts;
@@ -200,10 +212,12 @@ __global__ void __launch_bounds__(64) traceback_affine_kernel(const DeviceBatch 
 // Non-affine traceback (pyx:513-531): the first case, in generator order, that is
 // guard-valid and reproduces the cell; stops when none does (the origin).  One wave
 // per pair, lane c < 13 = case c; "first" = wave-min over the matching lane ids.
-template <int S, bool DO_TRACE, bool STRIP = false, bool WIDE = false, bool D1 = false>  // STRIP, WIDE, D1: see traceback_affine_kernel
+template <int S, bool DO_TRACE, bool STRIP = false, bool WIDE = false, bool D1 = false, bool LEVEL = false>  // STRIP, WIDE, D1, LEVEL: see traceback_affine_kernel
 __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch A, int npairs) {
   static_assert(!WIDE || !STRIP, "no lean traceback on the wide-band path");
-  const int SR = WIDE ? A.wide_s : S;
+  static_assert(!LEVEL || (DO_TRACE && !WIDE && !STRIP), "level traceback: a form of its own");
+  constexpr bool CONT = STRIP || LEVEL;  // the walk goes on from the pair's TraceState
+  const int SR = (WIDE || LEVEL) ? A.wide_s : S;
   const int pid = A.order[blockIdx.x];
   const PairDesc pd = A.pairs[pid];
   const int n = pd.n, m = pd.m;
@@ -214,14 +228,19 @@ __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch 
   constexpr int W = 2 * S + 1, RR = Geo<S>::RR;
   extern __shared__ __align__(16) int32_t smem[];
   TraceState ts{};
-  if (STRIP) {
+  if (CONT) {
     ts = A.tstate[pid];
     if (ts.done) return;
   }
   const int Q = STRIP ? (ts.started ? ts.strip : pd.NS - 1) : 0;
   const int Qlo = STRIP ? max(Q - A.resw_k + 1, 0) : 0;
   const int64_t sstride = (int64_t)(m + Geo<S>::MAXOFF + 1) * Rec<S, 1>::RECDW;
+  const int seg = LEVEL ? wide_segment_of(ts, n, m, A.resw_k) : 0, seg_base = LEVEL ? wide_seg_base(seg, A.resw_k) : 0;
   auto cell = [&](int pi, int pj, int a, int b) -> int {
+    if (LEVEL) {  // [level - base][i][a][b/2]
+      const int WR = 2 * SR + 1, lev = 2 * (pi + pj) + a + b - 2 * SR;
+      return A.scratch[pd.scratch_off + (lev - seg_base) * wide_level_points(n, SR) + (int64_t)(pi * WR + a) * ((WR + 1) / 2) + (b >> 1)];
+    }
     if (WIDE) return lay[pd.layer_off + wide_dword(m, 2 * SR + 1, 1, pi, pj, a, b, 0)];
     if (!STRIP) return lay[cell_dword<S, 1>(pd, pi, pj, a, b, 0)];
     const int sp = pi / RR, ilp = pi - sp * RR + 1;
@@ -229,8 +248,8 @@ __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch 
       return A.scratch[pd.scratch_off + (Q - sp) * sstride + Rec<S, 1>::dword(pj + 2 * ilp + a, (ilp - 1) * W + a, b)];
     return lay[pd.layer_off + Rec<S, 1, true>::dword((int64_t)sp * pd.P + pj + 2 * ilp + a, a, b)];
   };
-  int cur = (STRIP && ts.started) ? ts.cur : cell(n, m, SR, SR);
-  if (c == 0 && !(STRIP && ts.started)) A.scores[pid] = cur;  // pyx:471
+  int cur = (CONT && ts.started) ? ts.cur : cell(n, m, SR, SR);
+  if (c == 0 && !(CONT && ts.started)) A.scores[pid] = cur;  // pyx:471
   if (!DO_TRACE) return;
   const TraceInputs in = stage_trace_inputs<D1>(A, pd, smem);
   const uint8_t *sa = in.sa, *ca = in.ca, *sb = in.sb, *cb = in.cb;
@@ -250,10 +269,11 @@ __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch 
 
   uint8_t* out = A.trace + pd.trace_off;
   int i = n, j = m, k = n, l = m, len = 0;
-  if (STRIP && ts.started) { i = ts.i; j = ts.j; k = ts.k; l = ts.l; len = ts.len; }
+  if (CONT && ts.started) { i = ts.i; j = ts.j; k = ts.k; l = ts.l; len = ts.len; }
   bool finished = true;
   while (true) {
     if (STRIP && i < Qlo * RR) { finished = false; break; }
+    if (LEVEL && seg > 0 && i + j + k + l < seg_base + WIDE_SEG_OVERLAP) { finished = false; break; }
     const int mu1 = (i >= 1 && j >= 1)
                         ? (D1 ? mu1tab[(int64_t)(i - 1) * m + (j - 1)] : in.s1[sa[i - 1] * A.k1 + sb[j - 1]])
                         : 0;
@@ -275,11 +295,11 @@ __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch 
     ++len;
     i -= (code >> 3) & 1; j -= (code >> 2) & 1; k -= (code >> 1) & 1; l -= code & 1;
   }
-  if (STRIP && !finished) {
+  if (CONT && !finished) {
     if (c == 0) {
       TraceState nx{};
       nx.i = i; nx.j = j; nx.k = k; nx.l = l; nx.cur = cur; nx.len = len;
-      nx.strip = Qlo - 1; nx.started = 1; nx.done = 0;
+      nx.strip = LEVEL ? seg - 1 : Qlo - 1; nx.started = 1; nx.done = 0;
       A.tstate[pid] = nx;
     }
     return;
@@ -295,7 +315,7 @@ __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch 
   if (c == 0) {
     A.trace_len[pid] = len;
     A.complete[pid] = 1;
-    if (STRIP) {
+    if (CONT) {
       ts.done = 1;
       ts.started = 1;
       A.tstate[pid] = ts;

@@ -23,6 +23,7 @@ struct PairDesc {
   int64_t trace_off;      // byte offset in the trace buffer
   int64_t tab_off;        // dense forms: start of this pair's tables in DeviceBatch::dense_tab (n x m each, mu2's first)
   int64_t scratch_off;    // lean traceback: dword offset of this pair's one-strip scratch records
+                          // (level traceback, bialign_wide.hpp: of its segment scratch; the ring follows it)
 };
 
 // Lean traceback: where a pair's walk stands between two strips.
@@ -31,7 +32,7 @@ struct TraceState {
   int32_t st, cur;        // its state and layer value
   int32_t d0, d1;         // running shifts (pyx:541-545)
   int32_t len;            // columns emitted so far (end -> start order)
-  int32_t strip;          // strip the current point lies in
+  int32_t strip;          // strip the current point lies in (level traceback, bialign_wide.hpp: the segment to sweep next)
   int32_t started, done;  // 0/1
 };
 
@@ -54,6 +55,7 @@ struct DeviceBatch {
   int32_t* scratch;     // lean traceback: full records of resw_k strips per pair
   TraceState* tstate;   // lean traceback: [npairs]
   int32_t resw_k;       // lean traceback: strips re-swept (in parallel) and walked per round
+                        // (level traceback, bialign_wide.hpp: levels per segment, C)
   int32_t wide_s;       // wide-band path (max_shift beyond the tiled kernels): the band half-width
   int32_t prio_mode;    // 1 = rotate wave priorities by workgroup age (fill_affine_kernel); BIALIGN_PRIO=0 switches it off
   int32_t spin_limit;   // team hand-off: polls of the partner's progress word before a wave gives up (error flag)

@@ -4,14 +4,16 @@
 
 namespace bialign {
 
-// The sweep kernel of a batch, handed to fn: affine or one-layer, mu1 as LOOKUP or dense tables.
-template <typename Fn>
+// The sweep kernel of a batch, handed to fn: affine or one-layer, mu1 as LOOKUP or dense tables; MODE: all layers
+// (or, affine, none: score only), or a pass of the level-checkpointed traceback.
+template <int MODE, typename Fn>
 int with_wide_fill_kernel(const bialign_batch* b, Fn&& fn) {
-  if (b->affine) return b->dense1 ? fn(fill_wide_affine_kernel<1>) : fn(fill_wide_affine_kernel<0>);
-  return b->dense1 ? fn(fill_wide_linear_kernel<1>) : fn(fill_wide_linear_kernel<0>);
+  if (b->affine) return b->dense1 ? fn(fill_wide_affine_kernel<1, MODE>) : fn(fill_wide_affine_kernel<0, MODE>);
+  return b->dense1 ? fn(fill_wide_linear_kernel<1, MODE>) : fn(fill_wide_linear_kernel<0, MODE>);
 }
 
-int launch_fill_wide(bialign_batch* b, const DeviceBatch& v, int first, int count) {
+template <int MODE>
+static int launch_fill_wide_mode(bialign_batch* b, const DeviceBatch& v, int first, int count) {
   DeviceBatch w = v;
   w.order = v.order + first;
   b->packed_layers = false;
@@ -19,7 +21,7 @@ int launch_fill_wide(bialign_batch* b, const DeviceBatch& v, int first, int coun
   // counter after every level), no more than a level has work for; one after a lost-co-residency recovery.
   int parts = 1;
   if (!b->no_xcu) {
-    const int resident = with_wide_fill_kernel(b, [&](auto kern) { return xcu_resident(b, kern, WIDE_THREADS, 0); });
+    const int resident = with_wide_fill_kernel<MODE>(b, [&](auto kern) { return xcu_resident(b, kern, WIDE_THREADS, 0); });
     int busiest = 1;  // points of the largest level, over the pairs of this launch: ~ min(n, m) rows x W x (W+1)/2
     for (int t = first; t < first + count; ++t) {
       const PairDesc& d = b->pairs[b->order[t]];
@@ -30,7 +32,7 @@ int launch_fill_wide(bialign_batch* b, const DeviceBatch& v, int first, int coun
     if (const char* e = getenv("BIALIGN_WIDE_PARTS")) parts = std::max(1, std::min(atoi(e), parts));  // tests
   }
   w.team = parts;
-  if (b->affine) {  // ring of derived values (bialign_wide.hpp): WIDE_RING levels per pair of this launch
+  if (MODE == WIDE_FULL && b->affine) {  // ring of derived values (bialign_wide.hpp): WIDE_RING levels per pair of this launch
     std::vector<int64_t> off(count);
     int64_t total = 0;
     for (int t = 0; t < count; ++t) {
@@ -46,9 +48,26 @@ int launch_fill_wide(bialign_batch* b, const DeviceBatch& v, int first, int coun
     w.wide_score_only = b->lean ? 1 : 0;
   }
   b->last_team = parts * (WIDE_THREADS / 64) * (parts > 1 ? -1 : 1);
-  return with_wide_fill_kernel(b, [&](auto kern) {
+  return with_wide_fill_kernel<MODE>(b, [&](auto kern) {
     return launch_team(b, kern, dim3(count * parts), dim3(WIDE_THREADS), 0, w, count, parts > 1, b->S);
   });
+}
+
+int launch_fill_wide(bialign_batch* b, const DeviceBatch& v, int first, int count) {
+  return b->level_trace ? launch_fill_wide_mode<WIDE_CKPT>(b, v, first, count) : launch_fill_wide_mode<WIDE_FULL>(b, v, first, count);
+}
+
+int launch_segment_wide(bialign_batch* b, const DeviceBatch& v, int first, int count) {
+  return launch_fill_wide_mode<WIDE_SEG>(b, v, first, count);
+}
+
+int launch_traceback_level(const bialign_batch* b, const DeviceBatch& v, int first, int count) {
+  constexpr unsigned F = T_TRACE | T_LEVEL;
+  if (b->affine)
+    return b->dense1 ? launch_traceback_kernel(b, traceback_affine_of<0, F | T_DENSE1>(), true, v, first, count)
+                     : launch_traceback_kernel(b, traceback_affine_of<0, F>(), true, v, first, count);
+  return b->dense1 ? launch_traceback_kernel(b, traceback_linear_of<0, F | T_DENSE1>(), true, v, first, count)
+                   : launch_traceback_kernel(b, traceback_linear_of<0, F>(), true, v, first, count);
 }
 
 int launch_traceback_wide(const bialign_batch* b, const DeviceBatch& v, int first, int count, bool do_trace) {

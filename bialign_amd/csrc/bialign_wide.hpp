@@ -167,9 +167,110 @@ __device__ __forceinline__ int wfY(int y, int x, int m, int beta) { return max(y
 __device__ __forceinline__ int wfX(int y, int x, int m, int beta) { return max(x, beta + max(y, m)); }
 __device__ __forceinline__ int wfM(int y, int x, int m) { return max(max(y, x), m); }
 
+// ---------------------------------------------------------------------------
+// Level-checkpointed traceback (BIALIGN_BATCH_LEVEL_TRACE): full results without the pair's layers in HBM.
+// A traceback walks strictly downward in D (every predecessor lowers it by 1..4), and the sweep's whole state
+// is the last WIDE_RING levels, so the lattice is cut by LEVEL into segments of C levels:
+//   pass 1 (WIDE_CKPT)  the ring sweep without layers; every point of a level in [kC-4, kC], 1 <= k < K, also
+//                       stores its own layer values into checkpoint k (the ring's derived values are functions
+//                       of them); the last level writes the score.
+//   pass 2 (WIDE_SEG)   rounds, top segment first: segment k rebuilds the ring from checkpoint k (k > 0), sweeps
+//                       levels kC+1 .. min((k+1)C+4, L) (segment 0: from level 0) and stores their layers into the
+//                       pair's scratch [D - base][i][a][b/2][pitch]; the LEVEL form of the traceback kernels then
+//                       walks from the pair's TraceState while all candidates of its point (levels D-1 .. D-4)
+//                       lie in the scratch, i.e. down to a point of level <= kC+4 -- which is the top level of
+//                       segment k-1: consecutive segments overlap by WIDE_SEG_OVERLAP = 4 levels.
+// L = 2(n+m), K = max(1, ceil(L / C)) segments, K-1 checkpoints.  A pair's region of the chunk buffer:
+// checkpoints (at PairDesc::layer_off), scratch (scratch_off), ring.  Which segment a pair is at travels in its
+// TraceState (strip), so one launch serves pairs at different segments and finished pairs drop out.
+// ---------------------------------------------------------------------------
+enum WideMode { WIDE_FULL = 0, WIDE_CKPT = 1, WIDE_SEG = 2 };
+constexpr int WIDE_SEG_OVERLAP = 4;  // levels below a walk's point that hold its candidates
+constexpr int WIDE_SEG_MIN = 8;      // smallest C: the checkpoint windows [kC-4, kC] must not touch
+static_assert(WIDE_SEG_OVERLAP == WIDE_RING - 1 && WIDE_SEG_MIN > WIDE_RING, "segments are cut for predecessors 1..4 levels down");
+__host__ __device__ inline int64_t wide_level_points(int n, int S) {  // LV: (i, a, b/2) slots of one level
+  const int64_t W = 2 * S + 1;
+  return (int64_t)(n + 1) * W * ((W + 1) / 2);
+}
+__host__ __device__ inline int wide_segments(int n, int m, int C) {
+  const int L = 2 * (n + m), K = (L + C - 1) / C;
+  return K > 1 ? K : 1;
+}
+// levels of segment k in the scratch: base .. top (the sweep of k > 0 starts right above checkpoint k)
+__host__ __device__ inline int wide_seg_base(int k, int C) { return k > 0 ? k * C + 1 : 0; }
+__host__ __device__ inline int wide_seg_top(int k, int C, int n, int m) {
+  const int L = 2 * (n + m), t = (k + 1) * C + WIDE_SEG_OVERLAP;
+  return t < L ? t : L;
+}
+__host__ __device__ inline int wide_scratch_levels(int n, int m, int C) {  // segment 0 holds one level more than the rest
+  const int L = 2 * (n + m);
+  return C + WIDE_SEG_OVERLAP + 1 < L + 1 ? C + WIDE_SEG_OVERLAP + 1 : L + 1;
+}
+__host__ __device__ inline int64_t wide_ckpt_dwords(int n, int m, int S, int C, int NL) {
+  return (int64_t)(wide_segments(n, m, C) - 1) * WIDE_RING * wide_level_points(n, S) * wide_pitch(NL);
+}
+__host__ __device__ inline int64_t wide_scratch_dwords(int n, int m, int S, int C, int NL) {
+  return (int64_t)wide_scratch_levels(n, m, C) * wide_level_points(n, S) * wide_pitch(NL);
+}
+// the ring of the LEVEL forms: the affine sweep's 27 derived values per point, the one-layer sweep's own value
+__host__ __device__ inline int64_t wide_level_ring_dwords(int n, int S, int NL) {
+  return (int64_t)WIDE_RING * wide_level_points(n, S) * (NL == 9 ? WIDE_SLOT : 1);
+}
+__host__ __device__ inline int64_t wide_level_pair_dwords(int n, int m, int S, int C, int NL) {
+  const int64_t d = wide_ckpt_dwords(n, m, S, C, NL) + wide_scratch_dwords(n, m, S, C, NL) + wide_level_ring_dwords(n, S, NL);
+  return (d + 3) / 4 * 4;  // the next pair's cells stay 16-byte aligned
+}
+// The segment pair pid is at: K-1 before its walk has started, else what the walk left in its TraceState.
+__device__ __forceinline__ int wide_segment_of(const TraceState& ts, int n, int m, int C) {
+  return ts.started ? ts.strip : wide_segments(n, m, C) - 1;
+}
+
+// The 27 derived values of a point with layer values M, written through into the ring (component 0 at r).
+__device__ __forceinline__ void wide_store_derived(const int (&M)[9], int32_t* r, int64_t LV, int beta) {
+  int H2[3][3], H3[3][3], G[3][3];
+#pragma unroll
+  for (int u = 0; u < 3; ++u) {
+    H2[u][0] = wfY(M[3 * u], M[3 * u + 1], M[3 * u + 2], beta);
+    H2[u][1] = wfX(M[3 * u], M[3 * u + 1], M[3 * u + 2], beta);
+    H2[u][2] = wfM(M[3 * u], M[3 * u + 1], M[3 * u + 2]);
+  }
+#pragma unroll
+  for (int v = 0; v < 3; ++v) {
+    H3[0][v] = wfY(M[v], M[3 + v], M[6 + v], beta);
+    H3[1][v] = wfX(M[v], M[3 + v], M[6 + v], beta);
+    H3[2][v] = wfM(M[v], M[3 + v], M[6 + v]);
+    G[0][v] = wfY(H2[0][v], H2[1][v], H2[2][v], beta);
+    G[1][v] = wfX(H2[0][v], H2[1][v], H2[2][v], beta);
+    G[2][v] = wfM(H2[0][v], H2[1][v], H2[2][v]);
+  }
+#pragma unroll
+  for (int u = 0; u < 3; ++u) {
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+      wide_store(r + (3 * u + v) * LV, G[u][v]);
+      wide_store(r + (9 + 3 * v + u) * LV, H2[u][v]);  // H2 at 9 + 3V + U
+      wide_store(r + (18 + 3 * u + v) * LV, H3[u][v]);
+    }
+  }
+}
+// A point's nine layer values in a 12-dword, 16-byte-aligned cell that only a later kernel reads: plain 16-byte accesses.
+__device__ __forceinline__ void wide_store_cell(int32_t* p, const int (&M)[9]) {
+  v4i* out = reinterpret_cast<v4i*>(p);
+  out[0] = v4i{M[0], M[1], M[2], M[3]};
+  out[1] = v4i{M[4], M[5], M[6], M[7]};
+  out[2] = v4i{M[8], 0, 0, 0};
+}
+__device__ __forceinline__ void wide_load_cell(const int32_t* p, int (&M)[9]) {
+  const v4i* in = reinterpret_cast<const v4i*>(p);
+  const v4i x = in[0], y = in[1], z = in[2];
+  M[0] = x[0]; M[1] = x[1]; M[2] = x[2]; M[3] = x[3];
+  M[4] = y[0]; M[5] = y[1]; M[6] = y[2]; M[7] = y[3];
+  M[8] = z[0];
+}
+
 // D1 = 1: mu1 from the pair's dense table (DeviceBatch::dense_forms bit 1).  (A template also so that only
-// bialign_wide.hip instantiates it.)
-template <int D1 = 0>
+// bialign_wide.hip instantiates it.)  MODE: WIDE_FULL, or a pass of the level-checkpointed traceback (above).
+template <int D1 = 0, int MODE = WIDE_FULL>
 __global__ void __launch_bounds__(WIDE_THREADS) fill_wide_affine_kernel(const DeviceBatch A, int S) {
   const int parts = A.team, slot = blockIdx.x / parts, part = blockIdx.x - slot * parts;
   const int pid = A.order[slot];
@@ -185,11 +286,20 @@ __global__ void __launch_bounds__(WIDE_THREADS) fill_wide_affine_kernel(const De
   const int n = c.n, m = c.m, W = c.W, HW = (W + 1) / 2;
   const int beta = c.beta, gamma = c.gamma, delta = c.delta;
   int32_t* const flags = A.prog + (int64_t)slot * PROG_WORDS;  // [parts] levels closed, zeroed per launch
-  int32_t* const ring = A.wide_ring + A.wide_ring_off[slot];
+  // LEVEL forms: the pair's segment (every part reads the same state, left by an earlier kernel), scratch and ring
+  const int C = A.resw_k;
+  int seg = 0;
+  if constexpr (MODE == WIDE_SEG) {
+    const TraceState ts = A.tstate[pid];
+    if (ts.done) return;
+    seg = wide_segment_of(ts, c.n, c.m, C);
+  }
+  int32_t* const scratch = MODE == WIDE_FULL ? nullptr : A.scratch + pd.scratch_off;
+  int32_t* const ring = MODE == WIDE_FULL ? A.wide_ring + A.wide_ring_off[slot] : scratch + wide_scratch_dwords(c.n, c.m, S, C, 9);
   __shared__ WideStage stage;
   wide_stage(c, stage);
   const int64_t LV = (int64_t)(n + 1) * W * HW, lvl = wide_ring_level_dwords(n, S);  // points per level, dwords per level (27 LV)
-  const bool keep_layers = !A.wide_score_only;
+  const bool keep_layers = MODE == WIDE_FULL && !A.wide_score_only;
   bool failed = false;  // (a level barrier timed out for this thread: no further waits)
 
   // component 0 of lattice point (i, a, b) in the ring level at `base`; component v lies v * LV dwords further
@@ -200,10 +310,36 @@ __global__ void __launch_bounds__(WIDE_THREADS) fill_wide_affine_kernel(const De
   long long tph[5] = {0, 0, 0, 0, 0}, tlast = __builtin_amdgcn_s_memtime();
   auto stamp = [&](int ph) { const long long t = __builtin_amdgcn_s_memtime(); tph[ph] += t - tlast; tlast = t; };
 #endif
-  for (int D = 0; D <= 2 * (n + m); ++D) {
+  // levels of this launch, and the number of the first one's barrier (barrier 0 of a segment closes the rebuilt ring)
+  const int Dlo = MODE == WIDE_SEG ? wide_seg_base(seg, C) : 0, Dhi = MODE == WIDE_SEG ? wide_seg_top(seg, C, n, m) : 2 * (n + m);
+  const int sync0 = MODE == WIDE_SEG ? 1 - Dlo : 0;
+  if constexpr (MODE == WIDE_SEG) {
+    if (seg > 0) {  // the ring as pass 1 left it after level seg*C: derived values of checkpoint seg's five levels
+      for (int t = 0; t < WIDE_RING; ++t) {
+        const int D = seg * C - WIDE_SEG_OVERLAP + t;
+        const int32_t* ck = c.lay + ((int64_t)(seg - 1) * WIDE_RING + t) * LV * 12;
+        int32_t* rl = ring + (D % WIDE_RING) * lvl;
+        wide_for_level(c, D, part, parts, [&](int i, int, int, int, int aa, int bb) {
+          int M[9];
+          wide_load_cell(ck + ((int64_t)(i * W + aa) * HW + (bb >> 1)) * 12, M);
+          wide_store_derived(M, rpoint(rl, i, aa, bb), LV, beta);
+        });
+      }
+    }
+    wide_level_sync(A, flags, 0, part, parts, failed);
+  }
+  for (int D = Dlo; D <= Dhi; ++D) {
     int32_t* rb[WIDE_RING];  // ring levels of D, D-1, .. D-4
 #pragma unroll
     for (int d = 0; d < WIDE_RING; ++d) rb[d] = ring + ((D - d + WIDE_RING) % WIDE_RING) * lvl;
+    // LEVEL forms: where this level's cells go -- a checkpoint's level (pass 1), the segment scratch -- or nullptr
+    int32_t* cells = nullptr;
+    if constexpr (MODE == WIDE_CKPT) {
+      const int kc = (D + WIDE_SEG_OVERLAP) / C;  // the only k whose window [kC-4, kC] can hold D
+      if (kc >= 1 && kc < wide_segments(n, m, C) && D <= kc * C)
+        cells = c.lay + ((int64_t)(kc - 1) * WIDE_RING + (D - (kc * C - WIDE_SEG_OVERLAP))) * LV * 12;
+    }
+    if constexpr (MODE == WIDE_SEG) cells = scratch + (int64_t)(D - Dlo) * LV * 12;
     wide_for_level(c, D, part, parts, [&](int i, int j, int k, int l, int aa, int bb) {
       int M[9];
       if (D == 0) {  // pyx:483-485
@@ -258,34 +394,16 @@ __global__ void __launch_bounds__(WIDE_THREADS) fill_wide_affine_kernel(const De
           }
         }
       }
-      // derived values for the successors
-      int H2[3][3], H3[3][3], G[3][3];
+      wide_store_derived(M, rpoint(rb[0], i, aa, bb), LV, beta);  // derived values for the successors
+      if constexpr (MODE != WIDE_FULL) {
+        if (cells) wide_store_cell(cells + ((int64_t)(i * W + aa) * HW + (bb >> 1)) * 12, M);
+        if (MODE == WIDE_CKPT && D == 2 * (n + m)) {  // the end cell (n,m,n,m): the score (pyx:509)
+          int best = M[0];
 #pragma unroll
-      for (int u = 0; u < 3; ++u) {
-        H2[u][0] = wfY(M[3 * u], M[3 * u + 1], M[3 * u + 2], beta);
-        H2[u][1] = wfX(M[3 * u], M[3 * u + 1], M[3 * u + 2], beta);
-        H2[u][2] = wfM(M[3 * u], M[3 * u + 1], M[3 * u + 2]);
-      }
-#pragma unroll
-      for (int v = 0; v < 3; ++v) {
-        H3[0][v] = wfY(M[v], M[3 + v], M[6 + v], beta);
-        H3[1][v] = wfX(M[v], M[3 + v], M[6 + v], beta);
-        H3[2][v] = wfM(M[v], M[3 + v], M[6 + v]);
-        G[0][v] = wfY(H2[0][v], H2[1][v], H2[2][v], beta);
-        G[1][v] = wfX(H2[0][v], H2[1][v], H2[2][v], beta);
-        G[2][v] = wfM(H2[0][v], H2[1][v], H2[2][v]);
-      }
-      int32_t* r = rpoint(rb[0], i, aa, bb);
-#pragma unroll
-      for (int u = 0; u < 3; ++u) {
-#pragma unroll
-        for (int v = 0; v < 3; ++v) {
-          wide_store(r + (3 * u + v) * LV, G[u][v]);
-          wide_store(r + (9 + 3 * v + u) * LV, H2[u][v]);  // H2 at 9 + 3V + U
-          wide_store(r + (18 + 3 * u + v) * LV, H3[u][v]);
+          for (int q = 1; q < 9; ++q) best = max(best, M[q]);
+          A.scores[pid] = best;
         }
-      }
-      if (keep_layers) {
+      } else if (keep_layers) {
         // the sweep itself never reads a layer back (its state is the ring): plain write-back stores, 16-byte aligned
         v4i* out = reinterpret_cast<v4i*>(c.lay + wide_dword(m, W, 9, i, j, aa, bb, 0));
         out[0] = v4i{M[0], M[1], M[2], M[3]};
@@ -303,7 +421,7 @@ __global__ void __launch_bounds__(WIDE_THREADS) fill_wide_affine_kernel(const De
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     stamp(3);  // stores acknowledged
 #endif
-    wide_level_sync(A, flags, D, part, parts, failed);
+    wide_level_sync(A, flags, D + sync0, part, parts, failed);
 #if BIALIGN_EXP == 8
     stamp(4);  // barrier
 #endif
@@ -323,7 +441,11 @@ __global__ void __launch_bounds__(WIDE_THREADS) fill_wide_affine_kernel(const De
 // ---------------------------------------------------------------------------
 // Non-affine fill (pyx:443-471): thirteen cases (pyx:233-248), one layer.
 // ---------------------------------------------------------------------------
-template <int D1 = 0>  // see fill_wide_affine_kernel
+// MODE WIDE_FULL reads its predecessors from the layers themselves.  The LEVEL forms (WIDE_CKPT, WIDE_SEG: see
+// fill_wide_affine_kernel) keep the point's one value in a ring of the last WIDE_RING levels instead,
+// [D mod WIDE_RING][i][a][b/2] like a component of the affine ring: thirteen loads from it per point; a checkpoint
+// is those five levels, the segment scratch has pitch 1.
+template <int D1 = 0, int MODE = WIDE_FULL>  // see fill_wide_affine_kernel
 __global__ void __launch_bounds__(WIDE_THREADS) fill_wide_linear_kernel(const DeviceBatch A, int S) {
   const int parts = A.team, slot = blockIdx.x / parts, part = blockIdx.x - slot * parts;
   const int pid = A.order[slot];
@@ -341,13 +463,56 @@ __global__ void __launch_bounds__(WIDE_THREADS) fill_wide_linear_kernel(const De
   constexpr int OFF[13] = {15, 10, 5, 12, 3, 8, 4, 2, 1, 11, 7, 14, 13};  // o0*8+o1*4+o2*2+o3, generator order
   int32_t* const flags = A.prog + (int64_t)slot * PROG_WORDS;
   bool failed = false;  // (a level barrier timed out for this thread: no further waits)
+  // LEVEL forms: the pair's segment, scratch and ring (as in fill_wide_affine_kernel)
+  const int C = A.resw_k, HW = (W + 1) / 2;
+  const int64_t LV = wide_level_points(n, S);
+  int seg = 0;
+  if constexpr (MODE == WIDE_SEG) {
+    const TraceState ts = A.tstate[pid];
+    if (ts.done) return;
+    seg = wide_segment_of(ts, n, m, C);
+  }
+  int32_t* const scratch = MODE == WIDE_FULL ? nullptr : A.scratch + pd.scratch_off;
+  int32_t* const ring = MODE == WIDE_FULL ? nullptr : scratch + wide_scratch_dwords(n, m, S, C, 1);
   __shared__ WideStage stage;
   wide_stage(c, stage);
 
-  for (int D = 0; D <= 2 * (n + m); ++D) {
+  const int Dlo = MODE == WIDE_SEG ? wide_seg_base(seg, C) : 0, Dhi = MODE == WIDE_SEG ? wide_seg_top(seg, C, n, m) : 2 * (n + m);
+  const int sync0 = MODE == WIDE_SEG ? 1 - Dlo : 0;
+  if constexpr (MODE == WIDE_SEG) {
+    if (seg > 0) {  // the ring as pass 1 left it after level seg*C: checkpoint seg's five levels
+      for (int t = 0; t < WIDE_RING; ++t) {
+        const int D = seg * C - WIDE_SEG_OVERLAP + t;
+        const int32_t* ck = c.lay + ((int64_t)(seg - 1) * WIDE_RING + t) * LV;
+        int32_t* rl = ring + (D % WIDE_RING) * LV;
+        wide_for_level(c, D, part, parts, [&](int i, int, int, int, int aa, int bb) {
+          const int64_t x = (int64_t)(i * W + aa) * HW + (bb >> 1);
+          wide_store(rl + x, ck[x]);
+        });
+      }
+    }
+    wide_level_sync(A, flags, 0, part, parts, failed);
+  }
+  for (int D = Dlo; D <= Dhi; ++D) {
+    int32_t* cells = nullptr;  // LEVEL forms: where this level's values go besides the ring, or nullptr
+    if constexpr (MODE == WIDE_CKPT) {
+      const int kc = (D + WIDE_SEG_OVERLAP) / C;  // the only k whose window [kC-4, kC] can hold D
+      if (kc >= 1 && kc < wide_segments(n, m, C) && D <= kc * C)
+        cells = c.lay + ((int64_t)(kc - 1) * WIDE_RING + (D - (kc * C - WIDE_SEG_OVERLAP))) * LV;
+    }
+    if constexpr (MODE == WIDE_SEG) cells = scratch + (int64_t)(D - Dlo) * LV;
     wide_for_level(c, D, part, parts, [&](int i, int j, int k, int l, int aa, int bb) {
-      int32_t* out = c.lay + wide_dword(m, W, 1, i, j, aa, bb, 0);
-      if (D == 0) { wide_store(out, 0); return; }  // zero-initialised storage (pyx:452)
+      // a point's slot within a level of the ring / a checkpoint / the scratch
+      auto lslot = [&](int pi, int pa, int pb) { return (int64_t)(pi * W + pa) * HW + (pb >> 1); };
+      // where the point's value goes: its layer cell, or (LEVEL forms) its ring slot
+      int32_t* out = MODE == WIDE_FULL ? c.lay + wide_dword(m, W, 1, i, j, aa, bb, 0) : ring + (D % WIDE_RING) * LV + lslot(i, aa, bb);
+      auto also = [&](int v) {  // LEVEL forms: the copy a later kernel reads (plain store), the score
+        if constexpr (MODE != WIDE_FULL) {
+          if (cells) cells[lslot(i, aa, bb)] = v;
+          if (MODE == WIDE_CKPT && D == 2 * (n + m)) A.scores[pid] = v;  // pyx:471
+        }
+      };
+      if (D == 0) { wide_store(out, 0); also(0); return; }  // zero-initialised storage (pyx:452)
       int pv[13];
       bool ok[13];
 #pragma unroll
@@ -355,7 +520,9 @@ __global__ void __launch_bounds__(WIDE_THREADS) fill_wide_linear_kernel(const De
         const int o0 = (OFF[t] >> 3) & 1, o1 = (OFF[t] >> 2) & 1, o2 = (OFF[t] >> 1) & 1, o3 = OFF[t] & 1;
         const int pi = i - o0, pj = j - o1, pk = k - o2, pl = l - o3;
         ok[t] = c.valid(pi, pj, pk, pl);
-        const int32_t* src = ok[t] ? c.lay + wide_dword(m, W, 1, pi, pj, pk - pi + S, pl - pj + S, 0) : out;
+        const int32_t* src = !ok[t] ? out
+                             : MODE == WIDE_FULL ? c.lay + wide_dword(m, W, 1, pi, pj, pk - pi + S, pl - pj + S, 0)
+                                                 : ring + ((D - (o0 + o1 + o2 + o3)) % WIDE_RING) * LV + lslot(pi, pk - pi + S, pl - pj + S);
         pv[t] = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       const int mu1 = c.template mu1<D1 != 0>(i, j), mu2 = c.mu2(k, l);
@@ -371,8 +538,9 @@ __global__ void __launch_bounds__(WIDE_THREADS) fill_wide_linear_kernel(const De
         any = true;
       }
       wide_store(out, best);
+      also(best);
     });
-    wide_level_sync(A, flags, D, part, parts, failed);
+    wide_level_sync(A, flags, D + sync0, part, parts, failed);
   }
 }
 

@@ -80,6 +80,10 @@ class Batch:
     only the rows the next strip needs; ``traces()`` / ``dump_layers()`` raise.
     ``lean_trace``: scores AND traces from that reduced storage (BIALIGN_BATCH_LEAN_TRACE): the
     traceback re-sweeps one strip at a time; for pairs whose full layers would not fit in HBM.
+    ``level_trace``: the same for bands beyond ``_lib.MAX_SHIFT_TILED`` (BIALIGN_BATCH_LEVEL_TRACE): the sweep
+    leaves checkpoints of five anti-diagonal levels, the traceback re-sweeps one segment of levels at a time.
+    Excludes ``score_only`` and ``lean_trace``; the engine takes it by itself when a wide-band pair's layers
+    exceed the HBM budget (``info["storage"] == _lib.BATCH_LEVEL_TRACE``).
     ``mu2_features``: ``(structure_weight, feats_a, feats_b)``, mu2 in FEATURE form (include/bialign.h,
     bialign_features): the RNA structure score of real-valued per-residue features (predicted structures), whose
     n x m tables the GPU builds itself, chunk by chunk.  With molecule lists ``feats_a[p]`` / ``feats_b[p]`` is
@@ -90,9 +94,11 @@ class Batch:
 
     def __init__(self, engine, mols_a, mols_b, s1, s2, gap_opening_cost, gap_cost, shift_cost,
                  max_shift, hbm_budget_bytes=0, recurrence=0, mu2_dense=None, score_only=False,
-                 lean_trace=False, mu1_dense=None, mu2_features=None):
+                 lean_trace=False, mu1_dense=None, mu2_features=None, level_trace=False):
         if mu2_features is not None and mu2_dense is not None:
             raise ValueError("mu2_features and mu2_dense exclude each other")
+        if level_trace and (score_only or lean_trace):
+            raise ValueError("level_trace excludes score_only and lean_trace")
         flat = mols_b is None and hasattr(mols_a, "seq_a")
         if mols_b is None and hasattr(mols_a, "seq_a"):  # a batch.FlatBatch: the arrays are the ABI's already
             fb = mols_a
@@ -134,7 +140,8 @@ class Batch:
             mu1_ptr, mu1_off_ptr = _ptr(mu1_flat, ctypes.c_int32), _ptr(mu1_off, ctypes.c_int64)
         prm = _lib.Params(int(gap_opening_cost), int(gap_cost), int(shift_cost), int(max_shift),
                           int(recurrence), (_lib.BATCH_SCORE_ONLY if score_only else 0) |
-                          (_lib.BATCH_LEAN_TRACE if lean_trace else 0))
+                          (_lib.BATCH_LEAN_TRACE if lean_trace else 0) |
+                          (_lib.BATCH_LEVEL_TRACE if level_trace else 0))
         sc = _lib.Scoring(s1.shape[0], _ptr(s1, ctypes.c_int32), s2.shape[0], _ptr(s2, ctypes.c_int32))
         pr = _lib.Pairs(self.npairs, _ptr(self.len_a, ctypes.c_int32), _ptr(self.len_b, ctypes.c_int32),
                         _ptr(off_a, ctypes.c_int64), _ptr(off_b, ctypes.c_int64),

@@ -37,15 +37,16 @@ extern "C" {
 
 #define BIALIGN_OK 0
 #define BIALIGN_E_INVALID (-1)     /* bad argument (message says which) */
-#define BIALIGN_E_UNSUPPORTED (-2) /* e.g. reduced storage at max_shift above BIALIGN_MAX_SHIFT_TILED */
+#define BIALIGN_E_UNSUPPORTED (-2) /* e.g. LEAN_TRACE at max_shift above BIALIGN_MAX_SHIFT_TILED, LEVEL_TRACE at or below it */
 #define BIALIGN_E_DEVICE (-3)      /* HIP runtime error */
 #define BIALIGN_E_NOMEM (-4)       /* a single pair does not fit the HBM budget */
 #define BIALIGN_E_RANGE (-5)       /* scores could leave the int32 safety window */
 
 /* max_shift: any band width the reference takes (pyx:25-35; bialign.py:83 has no upper bound).  Bands up to
  * BIALIGN_MAX_SHIFT_TILED run the tiled register/LDS sweep (the fast path, all storage modes); wider bands
- * run a plain anti-diagonal kernel over layers kept in the reference's own array order (one workgroup per
- * pair, full storage only).  BIALIGN_MAX_SHIFT merely bounds the index arithmetic. */
+ * run a plain anti-diagonal kernel over layers kept in the reference's own array order (full storage, affine
+ * SCORE_ONLY, or -- the reduced mode with full results there -- BIALIGN_BATCH_LEVEL_TRACE).  BIALIGN_MAX_SHIFT merely
+ * bounds the index arithmetic. */
 #define BIALIGN_MAX_SHIFT_TILED 5
 #define BIALIGN_MAX_SHIFT 1024
 /* Molecule length: the tiled sweep stages both molecules' codes (2 bytes per residue and molecule) next to
@@ -76,6 +77,17 @@ extern "C" {
  * decides) for ~1.1-1.3x the time: for pairs whose layers would not fit otherwise.  max_shift <=
  * BIALIGN_MAX_SHIFT_TILED only (BIALIGN_E_UNSUPPORTED beyond). */
 #define BIALIGN_BATCH_LEAN_TRACE 2u
+/* LEVEL_TRACE: the same for bands beyond BIALIGN_MAX_SHIFT_TILED: full results (scores and traces) without the
+ * pair's layers in HBM.  The anti-diagonal sweep keeps its state in a ring of the last five levels and leaves a
+ * checkpoint of five levels every C levels; the traceback then sweeps one segment of C + 4 levels at a time, top
+ * segment first, into a per-pair scratch addressed by level and walks through it (a traceback only ever steps 1..4
+ * levels down).  Per pair (C + 4 + 5 L / C) levels instead of all L = 2(n+m), C ~ sqrt(5 L) chosen by the engine: a
+ * quarter of the default mode's HBM at 300 x 300, a tenth at 3000 x 3000, for about twice the sweep time (every
+ * level is swept twice).  Both recurrences, every form of mu1 / mu2.  max_shift > BIALIGN_MAX_SHIFT_TILED only
+ * (BIALIGN_E_UNSUPPORTED below: LEAN_TRACE is the mode there); with SCORE_ONLY or LEAN_TRACE: BIALIGN_E_INVALID.
+ * bialign_batch_dump_layers fails with BIALIGN_E_INVALID.  The engine takes this mode by itself when a wide-band
+ * pair's full layers exceed the HBM budget (bialign_batch_info.storage says so). */
+#define BIALIGN_BATCH_LEVEL_TRACE 4u
 
 typedef struct bialign_engine bialign_engine; /* one per (process, device) */
 typedef struct bialign_batch bialign_batch;   /* inputs resident in HBM */
@@ -166,8 +178,8 @@ typedef struct bialign_batch_info {
   int64_t layer_bytes;    /* algorithmic bytes: 36 B (affine) or 4 B per cell */
   int64_t hbm_layer_bytes;/* allocated size of the largest chunk's layer buffer */
   int64_t trace_bytes;    /* capacity of the trace buffer, sum of 2(n+m)+2 */
-  int32_t storage;        /* 0 = all layers, BIALIGN_BATCH_SCORE_ONLY, or BIALIGN_BATCH_LEAN_TRACE (asked for, or
-                             chosen by the engine because a pair's full layers exceed the HBM budget) */
+  int32_t storage;        /* 0 = all layers, BIALIGN_BATCH_SCORE_ONLY, or BIALIGN_BATCH_LEAN_TRACE / BIALIGN_BATCH_LEVEL_TRACE
+                             (asked for, or chosen by the engine because a pair's full layers exceed the HBM budget) */
   int32_t reserved;
 } bialign_batch_info;
 
