@@ -62,6 +62,21 @@ class FeatureInfo(ctypes.Structure):
 
 MU2_LOOKUP, MU2_DENSE, MU2_FEATURE = 0, 1, 2  # bialign_feature_info.form
 
+class NullSpec(ctypes.Structure):
+    """bialign_null_spec: a null batch's replicas per pair and seed."""
+    _fields_ = [("replicas", ctypes.c_int32), ("seed", ctypes.c_uint32)]
+
+
+class NullStats(ctypes.Structure):
+    """bialign_null_stats: one pair's replica scores reduced to exact integers."""
+    _fields_ = [("sum", ctypes.c_int64), ("sumsq", ctypes.c_int64), ("min", ctypes.c_int32),
+                ("max", ctypes.c_int32), ("n_ge", ctypes.c_int32), ("replicas", ctypes.c_int32)]
+
+
+class NullInfo(ctypes.Structure):
+    _fields_ = [("shuffle_ms", ctypes.c_double), ("stats_ms", ctypes.c_double),
+                ("replica_bytes", ctypes.c_int64)]
+
 
 class BatchInfo(ctypes.Structure):
     _fields_ = [("npairs", ctypes.c_int32), ("nchunks", ctypes.c_int32),
@@ -104,6 +119,13 @@ SYMBOLS = [
     ("bialign_batch_get_scores", ctypes.c_int, [ctypes.c_void_p, c_i32p]),
     ("bialign_batch_get_traces", ctypes.c_int, [ctypes.c_void_p, c_u8p, c_i64p, c_i32p, c_i32p]),
     ("bialign_batch_dump_layers", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_i32p]),
+    ("bialign_batch_create_null", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.POINTER(Params), ctypes.POINTER(Scoring), ctypes.POINTER(Pairs),
+      ctypes.POINTER(NullSpec), ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p)]),
+    ("bialign_batch_get_null_scores", ctypes.c_int, [ctypes.c_void_p, c_i32p]),
+    ("bialign_batch_get_null_stats", ctypes.c_int, [ctypes.c_void_p, c_i32p, ctypes.POINTER(NullStats)]),
+    ("bialign_batch_get_null_info", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(NullInfo)]),
+    ("bialign_batch_dump_null_codes", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, c_u8p, c_u8p]),
 ]
 
 #: Declared in include/bialign.h as well, but kept apart from SYMBOLS: tests/test_capi_symbols.py collects the header's

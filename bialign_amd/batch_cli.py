@@ -9,6 +9,10 @@ pair.  For each pair the output is the reference CLI's block (``Input:`` echo, `
 decoded alignment in the chosen ``--outmode``) behind a ``>pair`` header line.  Under
 ``torchrun`` (one process per GPU) the pairs are sharded over the ranks; every rank prints its
 own pairs, rank 0 additionally a ``#scores`` line with all gathered scores.
+
+``--zscore R`` adds one line behind each pair's block: where the score lies among the scores of A against R shuffles
+of B (``bialign_amd.significance``; the shuffles are made and scored on the GPU),
+``ZSCORE: <z> (mean <mean>, sd <sd>, <n_ge>/<R> shuffles >= score)``.  Without the option the output is unchanged.
 """
 import argparse
 import sys
@@ -44,7 +48,19 @@ def build_parser():
     p.add_argument("--score_only", action="store_true",
                    help="Print one 'pair nameA nameB score' line per pair and skip the alignments "
                         "(the GPU then keeps a fraction of the DP layers: faster, far less memory).")
+    p.add_argument("--zscore", type=int, default=0, metavar="R",
+                   help="Also print each pair's z-score against R shuffles of molecule B (1..65535), as a "
+                        "'ZSCORE:' line behind the pair's block.")
+    p.add_argument("--zscore_seed", type=int, default=0, metavar="N",
+                   help="Seed of the shuffles (default 0); shuffle r of a pair is a function of the seed, r and the "
+                        "pair's position among the pairs its process aligns.")
     return p
+
+
+def zscore_line(z, t):
+    """The ZSCORE line of pair t from ``significance.zscores`` results."""
+    return (f"ZSCORE: {z['z'][t]:.2f} (mean {z['mean'][t]:.1f}, sd {z['std'][t]:.1f}, "
+            f"{int(z['n_ge'][t])}/{int(z['replicas'][t])} shuffles >= score)")
 
 
 def pair_block(idx, rec, params, score, trace, complete, verbose):
@@ -79,7 +95,10 @@ def main(argv=None):
 
 def _main(argv=None):
     args = build_parser().parse_args(argv)
-    params = {k: v for k, v in vars(args).items() if k not in ("pairs", "verbose", "score_only")}
+    params = {k: v for k, v in vars(args).items() if k not in ("pairs", "verbose", "score_only", "zscore", "zscore_seed")}
+    if args.zscore:
+        from .significance import check_null
+        check_null((args.zscore, args.zscore_seed))
     records = read_pairs(args.pairs)
     from .batch import make_batch, pair_cost, shard
     from .distributed import gather_scores, init_from_env
@@ -93,15 +112,24 @@ def _main(argv=None):
                            engine=default_engine(local_rank), score_only=args.score_only)
         batch.run()
         scores = batch.scores()
+        z = None
+        if args.zscore:
+            from .significance import zscores
+            z = zscores([(r[1], r[4], r[2], r[5]) for r in (records[p] for p in mine)], params, replicas=args.zscore,
+                        seed=args.zscore_seed, observed=scores, engine=default_engine(local_rank))
         if args.score_only:
             for t, p in enumerate(mine):
                 print(f"pair {p}\t{records[p][0]}\t{records[p][3]}\t{int(scores[t])}")
+                if z:
+                    print(zscore_line(z, t))
         else:
             traces, complete = batch.traces()
             for t, p in enumerate(mine):
                 trace = trace_codes_to_columns(traces[t], as_tuples=not batch.affine)
                 for line in pair_block(p, records[p], params, int(scores[t]), trace, bool(complete[t]), args.verbose):
                     print(line)
+                if z:
+                    print(zscore_line(z, t))
         batch.close()
     if world > 1:
         allscores = gather_scores(scores, len(records), costs)

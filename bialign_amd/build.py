@@ -2,7 +2,8 @@
 
 The kernels are templates on max_shift; each (max_shift, kind) slice is its own translation unit
 (csrc/bialign_inst.hip with -DBIALIGN_TU_S / -DBIALIGN_TU_KIND), compiled in parallel, then linked
-with the wide-band unit, the mu2 table builder (csrc/bialign_mu2_build.hip) and the C-ABI unit
+with the wide-band unit, the mu2 table builder (csrc/bialign_mu2_build.hip), the shuffled-null kernels
+(csrc/bialign_null.hip) and the C-ABI unit
 (csrc/bialign_capi.hip) into one shared library.
 """
 import concurrent.futures
@@ -37,6 +38,7 @@ def units():
     out.append(("wide.o", "bialign_wide.hip", []))
     # the FEATURE form's table builder reproduces the reference's doubles operation by operation: nothing contracted
     out.append(("mu2_build.o", "bialign_mu2_build.hip", ["-ffp-contract=off"]))
+    out.append(("null.o", "bialign_null.hip", []))
     out.append(("capi.o", "bialign_capi.hip", []))
     return out
 

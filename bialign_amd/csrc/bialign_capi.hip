@@ -391,6 +391,9 @@ int plan_chunks(bialign_batch* b, const std::vector<int64_t>& pair_dwords, int64
   b->max_chunk_tab_dwords = 0;
   int64_t total_dw = 0;
   for (int p = 0; p < npairs; ++p) {
+    if (pair_dwords[p] + tab_of(p) > budget_dw && b->null_R)
+      return fail(BIALIGN_E_NOMEM, "pair %d: one replica needs %lld bytes of layers, budget is %lld", p / b->null_R,
+                  (long long)pair_dwords[p] * 4, (long long)budget_dw * 4);
     if (pair_dwords[p] + tab_of(p) > budget_dw)
       return feat ? fail(BIALIGN_E_NOMEM, "pair %d needs %lld bytes of layers and %lld of mu2 table, budget is %lld", p,
                          (long long)pair_dwords[p] * 4, (long long)tab_of(p) * 4, (long long)budget_dw * 4)
@@ -511,9 +514,21 @@ void bialign_engine_destroy(bialign_engine* e) {
   delete e;
 }
 
-// bialign_batch_create (ft == nullptr) and bialign_batch_create_features
+// What bialign_batch_create_null adds to the virtual pairs it hands to create_batch: the real pairs' B molecules.
+struct NullPlan {
+  int32_t replicas;
+  uint32_t seed;
+  int32_t npairs;                // real pairs
+  const int64_t* off_b;          // [npairs] start of real pair p's B in seq_b / cls_b
+  const uint8_t *seq_b, *cls_b;  // the B codes as the caller gave them
+  int64_t tot_b;                 // their extent
+};
+
+// bialign_batch_create (ft == nullptr), bialign_batch_create_features, and bialign_batch_create_null (nul != nullptr: pr
+// describes the virtual pairs, whose off_b point into replica buffers that are allocated here and filled on the device)
 static int create_batch(bialign_engine* eng, const bialign_params* prm, const bialign_scoring* sc,
-                        const bialign_pairs* pr, const bialign_features* ft, int64_t hbm_budget, bialign_batch** out) {
+                        const bialign_pairs* pr, const bialign_features* ft, int64_t hbm_budget, bialign_batch** out,
+                        const NullPlan* nul = nullptr) {
   if (!eng || !prm || !sc || !pr || !out) return fail(BIALIGN_E_INVALID, "NULL argument");
   *out = nullptr;
   if (pr->npairs < 1) return fail(BIALIGN_E_INVALID, "npairs must be >= 1");
@@ -540,6 +555,8 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
   b->dense = b->feat || pr->mu2_dense != nullptr;  // (the FEATURE form's tables feed the DENSE consumers)
   if (b->feat) b->feat_sw = ft->structure_weight;
   b->dense1 = pr->mu1_dense != nullptr;
+  if (nul) b->null_R = nul->replicas, b->null_npairs = nul->npairs, b->null_seed = nul->seed;
+  const auto shown = [&](int p) { return nul ? p / nul->replicas : p; };  // the pair an error message names: the real one
   b->lean_trace = (prm->flags & BIALIGN_BATCH_LEAN_TRACE) != 0;
   b->lean = b->lean_trace || (prm->flags & BIALIGN_BATCH_SCORE_ONLY) != 0;
   b->wide = prm->max_shift > BIALIGN_MAX_SHIFT_TILED;  // bialign_wide.hpp: anti-diagonal path, all layers in HBM
@@ -623,10 +640,16 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
   for (int p = 0; p < pr->npairs; ++p) {
     const int n = pr->len_a[p], m = pr->len_b[p];
     if (n < 1 || m < 1)  // the reference raises IndexError on empty molecules (pyx:407)
-      return fail(BIALIGN_E_INVALID, "pair %d: empty molecule (n=%d, m=%d)", p, n, m);
+      return fail(BIALIGN_E_INVALID, "pair %d: empty molecule (n=%d, m=%d)", shown(p), n, m);
     if ((2 * ((int64_t)n + m) + 8) * colmax >= (1 << 28))
-      return fail(BIALIGN_E_RANGE, "pair %d: scores may leave the int32 safety window (n+m=%d, column bound %lld)", p,
+      return fail(BIALIGN_E_RANGE, "pair %d: scores may leave the int32 safety window (n+m=%d, column bound %lld)", shown(p),
                   n + m, (long long)colmax);
+    if (nul) {  // the reduction's int64 sum of squares: replicas * bound^2 with the window's bound on |score| (< 2^28)
+      const int64_t bound = (2 * ((int64_t)n + m) + 8) * colmax;
+      if (bound > 0 && bound * bound > INT64_MAX / nul->replicas)
+        return fail(BIALIGN_E_RANGE, "pair %d: %d replica scores of magnitude up to %lld could overflow the int64 sum of squares",
+                    shown(p), nul->replicas, (long long)bound);
+    }
     PairDesc& d = b->pairs[p];
     d.n = n;
     d.m = m;
@@ -680,6 +703,13 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
       ok = interior >= 1 && (force || packed_dw * 5 <= full_dw * 4);
     }
     b->pack = ok;
+  }
+
+  // Null batch: the replicas' codes are input data like the uploaded codes -- outside the budget.  Allocated ahead of the
+  // budget's look at the free memory, which so has their size subtracted.
+  if (nul) {
+    HIP_TRY(b->d_seq_b.alloc((size_t)tot_b));
+    HIP_TRY(b->d_cls_b.alloc((size_t)tot_b));
   }
 
   // ---- chunking under the HBM budget; inside a chunk longest sweeps first
@@ -828,8 +858,16 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
   if (b->dense || b->dense1) zeros.assign((size_t)std::max(tot_a, tot_b), 0);  // codes a dense form replaces are unused
   HIP_TRY(b->d_seq_a.upload(b->dense1 ? zeros.data() : pr->seq_a, tot_a, st));
   HIP_TRY(b->d_cls_a.upload(b->dense ? zeros.data() : pr->cls_a, tot_a, st));
-  HIP_TRY(b->d_seq_b.upload(b->dense1 ? zeros.data() : pr->seq_b, tot_b, st));
-  HIP_TRY(b->d_cls_b.upload(b->dense ? zeros.data() : pr->cls_b, tot_b, st));
+  if (nul) {  // B once, as the caller gave it: the shuffle kernel writes d_seq_b / d_cls_b from it ahead of every run's sweeps
+    HIP_TRY(b->d_null_seq.upload(nul->seq_b, (size_t)nul->tot_b, st));
+    HIP_TRY(b->d_null_cls.upload(nul->cls_b, (size_t)nul->tot_b, st));
+    HIP_TRY(b->d_null_off.upload(nul->off_b, (size_t)nul->npairs, st));
+    HIP_TRY(b->d_null_stats.alloc((size_t)nul->npairs));
+    for (hipEvent_t& e : b->null_evs) HIP_TRY(hipEventCreate(&e));
+  } else {
+    HIP_TRY(b->d_seq_b.upload(b->dense1 ? zeros.data() : pr->seq_b, tot_b, st));
+    HIP_TRY(b->d_cls_b.upload(b->dense ? zeros.data() : pr->cls_b, tot_b, st));
+  }
   std::vector<int32_t> tabs;
   std::vector<int64_t> mu1_offs;
   if (b->feat) {  // the molecules' features, three planes per side; a dense mu1's tables resident, pair after pair
@@ -906,6 +944,56 @@ int bialign_batch_create_features(bialign_engine* eng, const bialign_params* prm
   if (!ft->up_a || !ft->down_a || !ft->unp_a || !ft->up_b || !ft->down_b || !ft->unp_b)
     return fail(BIALIGN_E_INVALID, "a feature array is NULL");
   return create_batch(eng, prm, sc, pr, ft, hbm_budget, out);
+}
+
+int bialign_batch_create_null(bialign_engine* eng, const bialign_params* prm, const bialign_scoring* sc,
+                              const bialign_pairs* pr, const bialign_null_spec* spec, int64_t hbm_budget, bialign_batch** out) {
+  if (out) *out = nullptr;
+  if (!eng || !prm || !sc || !pr || !out) return fail(BIALIGN_E_INVALID, "NULL argument");
+  if (!spec) return fail(BIALIGN_E_INVALID, "spec is NULL");
+  if (spec->replicas < 1 || spec->replicas > 65535)
+    return fail(BIALIGN_E_INVALID, "replicas must be 1..65535, got %d", spec->replicas);
+  if (pr->npairs < 1) return fail(BIALIGN_E_INVALID, "npairs must be >= 1");
+  if ((int64_t)pr->npairs * spec->replicas > INT32_MAX)
+    return fail(BIALIGN_E_INVALID, "npairs * replicas = %lld exceeds INT32_MAX", (long long)pr->npairs * spec->replicas);
+  if (prm->flags & (BIALIGN_BATCH_LEAN_TRACE | BIALIGN_BATCH_LEVEL_TRACE))
+    return fail(BIALIGN_E_INVALID, "a null batch is SCORE_ONLY: LEAN_TRACE / LEVEL_TRACE do not apply");
+  if (pr->mu1_dense || pr->mu2_dense)
+    return fail(BIALIGN_E_UNSUPPORTED, "null batches take the LOOKUP form only (a dense table's columns would have to be permuted per replica)");
+  if (!pr->len_a || !pr->len_b || !pr->off_a || !pr->off_b) return fail(BIALIGN_E_INVALID, "len_a / len_b / off_a / off_b are NULL");
+  if (!pr->seq_a || !pr->seq_b) return fail(BIALIGN_E_INVALID, "seq_a / seq_b are NULL (LOOKUP form)");
+  if (!pr->cls_a || !pr->cls_b) return fail(BIALIGN_E_INVALID, "cls_a / cls_b are NULL (LOOKUP form)");
+  const int R = spec->replicas;
+  const size_t nv = (size_t)pr->npairs * R;
+  // the virtual pairs, pair-major: v = p * R + r is real pair p against replica r, whose codes start at
+  // R * (sum of len_b before p) + r * len_b[p] of the replica buffers
+  std::vector<int32_t> len_a(nv), len_b(nv);
+  std::vector<int64_t> off_a(nv), off_b(nv);
+  NullPlan plan{R, spec->seed, pr->npairs, pr->off_b, pr->seq_b, pr->cls_b, 0};
+  int64_t before = 0;
+  for (int p = 0; p < pr->npairs; ++p) {
+    const int n = pr->len_a[p], m = pr->len_b[p];
+    if (n < 1 || m < 1) return fail(BIALIGN_E_INVALID, "pair %d: empty molecule (n=%d, m=%d)", p, n, m);
+    if (pr->off_b[p] < 0) return fail(BIALIGN_E_INVALID, "pair %d: negative off_b", p);
+    for (int r = 0; r < R; ++r) {
+      const size_t v = (size_t)p * R + r;
+      len_a[v] = n;
+      len_b[v] = m;
+      off_a[v] = pr->off_a[p];
+      off_b[v] = before * R + (int64_t)r * m;
+    }
+    before += m;
+    plan.tot_b = std::max<int64_t>(plan.tot_b, pr->off_b[p] + m);
+  }
+  bialign_pairs vp = *pr;
+  vp.npairs = (int32_t)nv;
+  vp.len_a = len_a.data();
+  vp.len_b = len_b.data();
+  vp.off_a = off_a.data();
+  vp.off_b = off_b.data();
+  bialign_params vprm = *prm;
+  vprm.flags = BIALIGN_BATCH_SCORE_ONLY;
+  return create_batch(eng, &vprm, sc, &vp, nullptr, hbm_budget, out, &plan);
 }
 
 void bialign_batch_destroy(bialign_batch* b) {
@@ -985,7 +1073,7 @@ int bialign_engine_trim(bialign_engine* e) {
 
 int bialign_batch_get_info(const bialign_batch* b, bialign_batch_info* info) {
   if (!b || !info) return fail(BIALIGN_E_INVALID, "NULL argument");
-  info->npairs = b->npairs;
+  info->npairs = b->null_R ? b->null_npairs : b->npairs;
   info->nchunks = (int)b->chunk_begin.size() - 1;
   info->affine = b->affine;
   info->max_shift = b->S;
@@ -1022,6 +1110,11 @@ static int enqueue_run(bialign_batch* b, uint32_t flags) {
   b->build_launches = 0;
   HIP_TRY(hipStreamWaitEvent(st, b->uploaded, 0));
   HIP_TRY(hipMemsetAsync(b->d_err.p, 0, sizeof(int32_t), st));  // the flag is per run
+  if (b->null_R) {  // null batch: the replicas' B codes, all of them ahead of the first sweep (timed on its own, outside fill_ms)
+    HIP_TRY(hipEventRecord(b->null_evs[0], st));
+    if (int rc = launch_shuffle_null(b, 0, b->npairs)) return rc;
+    HIP_TRY(hipEventRecord(b->null_evs[1], st));
+  }
   for (int c = 0; c < nchunks; ++c) {  // stream order keeps chunk c's traceback ahead of chunk c+1's sweep
     const int first = b->chunk_begin[c], count = b->chunk_begin[c + 1] - first;
     if (b->feat) {
@@ -1078,6 +1171,11 @@ int bialign_batch_wait(bialign_batch* b) {
         b->build_ms += f;
       }
     }
+    if (b->null_R) {
+      float f = 0;
+      HIP_TRY(hipEventElapsedTime(&f, b->null_evs[0], b->null_evs[1]));
+      b->shuffle_ms = f;
+    }
     int32_t err = 0;
     HIP_TRY(hipMemcpy(&err, b->d_err.p, sizeof err, hipMemcpyDeviceToHost));
     if (!err) break;
@@ -1126,6 +1224,7 @@ int bialign_batch_get_timing(const bialign_batch* b, bialign_timing* t) {
 
 int bialign_batch_get_scores(const bialign_batch* b, int32_t* scores) {
   if (!b || !scores) return fail(BIALIGN_E_INVALID, "NULL argument");
+  if (b->null_R) return fail(BIALIGN_E_INVALID, "a null batch has no observed scores: use bialign_batch_get_null_scores / _get_null_stats");
   if (int rc = bialign_batch_wait(const_cast<bialign_batch*>(b))) return rc;
   if (!b->ran) return fail(BIALIGN_E_INVALID, "bialign_batch_run has not been called");
   HIP_TRY(hipSetDevice(b->eng->device));
@@ -1225,6 +1324,64 @@ int bialign_batch_get_feature_info(const bialign_batch* b, bialign_feature_info*
     for (const PairDesc& d : b->pairs) dense_dw += (int64_t)d.n * d.m;
   info->table_bytes = 4 * (b->feat ? b->max_chunk_tab_dwords : dense_dw);
   info->build_ms = b->build_ms;
+  return BIALIGN_OK;
+}
+
+int bialign_batch_get_null_scores(const bialign_batch* b, int32_t* out) {
+  if (!b || !out) return fail(BIALIGN_E_INVALID, "NULL argument");
+  if (!b->null_R) return fail(BIALIGN_E_INVALID, "not a null batch (bialign_batch_create_null)");
+  if (int rc = bialign_batch_wait(const_cast<bialign_batch*>(b))) return rc;
+  if (!b->ran) return fail(BIALIGN_E_INVALID, "bialign_batch_run has not been called");
+  HIP_TRY(hipSetDevice(b->eng->device));
+  HIP_TRY(hipMemcpy(out, b->d_scores.p, sizeof(int32_t) * b->npairs, hipMemcpyDeviceToHost));
+  return BIALIGN_OK;
+}
+
+int bialign_batch_get_null_stats(const bialign_batch* cb, const int32_t* observed, bialign_null_stats* out) {
+  if (!cb || !out) return fail(BIALIGN_E_INVALID, "NULL argument");
+  if (!cb->null_R) return fail(BIALIGN_E_INVALID, "not a null batch (bialign_batch_create_null)");
+  bialign_batch* b = const_cast<bialign_batch*>(cb);  // (the reduction's buffers and times are the batch's)
+  if (int rc = bialign_batch_wait(b)) return rc;
+  if (!b->ran) return fail(BIALIGN_E_INVALID, "bialign_batch_run has not been called");
+  HIP_TRY(hipSetDevice(b->eng->device));
+  hipStream_t st = b->eng->stream;
+  if (observed) HIP_TRY(b->d_null_obs.upload(observed, (size_t)b->null_npairs, st));
+  HIP_TRY(hipEventRecord(b->null_evs[2], st));
+  if (int rc = launch_null_stats(b, observed ? b->d_null_obs.p : nullptr)) return rc;
+  HIP_TRY(hipEventRecord(b->null_evs[3], st));
+  HIP_TRY(hipMemcpyAsync(out, b->d_null_stats.p, sizeof(bialign_null_stats) * b->null_npairs, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  float f = 0;
+  HIP_TRY(hipEventElapsedTime(&f, b->null_evs[2], b->null_evs[3]));
+  b->stats_ms = f;
+  return BIALIGN_OK;
+}
+
+int bialign_batch_get_null_info(const bialign_batch* b, bialign_null_info* info) {
+  if (!b || !info) return fail(BIALIGN_E_INVALID, "NULL argument");
+  if (!b->null_R) return fail(BIALIGN_E_INVALID, "not a null batch (bialign_batch_create_null)");
+  if (int rc = bialign_batch_wait(const_cast<bialign_batch*>(b))) return rc;
+  info->shuffle_ms = b->shuffle_ms;
+  info->stats_ms = b->stats_ms;
+  info->replica_bytes = (int64_t)(b->d_seq_b.n + b->d_cls_b.n);
+  return BIALIGN_OK;
+}
+
+int bialign_batch_dump_null_codes(bialign_batch* b, int32_t pair, int32_t replica, uint8_t* seq, uint8_t* cls) {
+  if (!b || !seq || !cls) return fail(BIALIGN_E_INVALID, "NULL argument");
+  if (!b->null_R) return fail(BIALIGN_E_INVALID, "not a null batch (bialign_batch_create_null)");
+  if (pair < 0 || pair >= b->null_npairs) return fail(BIALIGN_E_INVALID, "pair %d out of range", pair);
+  if (replica < 0 || replica >= b->null_R) return fail(BIALIGN_E_INVALID, "replica %d out of range", replica);
+  if (int rc = bialign_batch_wait(b)) return rc;
+  HIP_TRY(hipSetDevice(b->eng->device));
+  hipStream_t st = b->eng->stream;
+  HIP_TRY(hipStreamWaitEvent(st, b->uploaded, 0));
+  const int v = pair * b->null_R + replica;
+  if (int rc = launch_shuffle_null(b, v, 1)) return rc;
+  const PairDesc& d = b->pairs[v];
+  HIP_TRY(hipMemcpyAsync(seq, b->d_seq_b.p + d.seq_b, (size_t)d.m, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(cls, b->d_cls_b.p + d.seq_b, (size_t)d.m, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   return BIALIGN_OK;
 }
 

@@ -144,6 +144,17 @@ struct bialign_batch {
   std::vector<hipEvent_t> build_evs;   // two per chunk, around the builder's launch
   double build_ms = 0;                 // HIP-event time of the builder launches of the last run (not part of fill_ms)
   int build_launches = 0;
+  // Null batch (bialign_batch_create_null, bialign_null.hpp): npairs above counts the VIRTUAL pairs, null_npairs real pairs x
+  // null_R replicas, pair-major; d_seq_b / d_cls_b are the replica buffers the shuffle kernel fills ahead of a run's sweeps
+  // from the uploaded B codes kept in d_null_seq / d_null_cls (real pair p's at d_null_off[p]).
+  int null_R = 0, null_npairs = 0;  // null_R == 0: not a null batch
+  uint32_t null_seed = 0;
+  DevBuf<uint8_t> d_null_seq, d_null_cls;
+  DevBuf<int64_t> d_null_off;
+  DevBuf<int32_t> d_null_obs;               // observed scores of the last bialign_batch_get_null_stats
+  DevBuf<bialign_null_stats> d_null_stats;  // ... and its result
+  hipEvent_t null_evs[4] = {nullptr, nullptr, nullptr, nullptr};  // around the shuffle launch of a run, around the reduction
+  double shuffle_ms = 0, stats_ms = 0;      // HIP-event times (not part of fill_ms)
   bool dense1 = false;      // mu1 in DENSE form (kernels with DENSE1 / D1 set; no packed records, no slim or diet sweeps)
   bool wide = false;        // max_shift above the tiled kernels: anti-diagonal path (bialign_wide.hpp), reference-order layers
   bool lean = false;        // LEAN records: the sweep keeps only the strip-bottom rows
@@ -164,6 +175,8 @@ struct bialign_batch {
     for (hipEvent_t e : evs)
       if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : build_evs)
+      if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : null_evs)
       if (e) (void)hipEventDestroy(e);
     if (uploaded) (void)hipEventDestroy(uploaded);
   }
@@ -223,6 +236,11 @@ int xcu_serial_end(bialign_engine* e);
 // FEATURE form of mu2: build the tables of pairs order[first .. first+count) into the chunk's table buffer, on the
 // engine's stream (bialign_mu2_build.hip).  The pairs' tab_off must be the device's.
 int launch_build_mu2(bialign_batch* b, int first, int count);
+
+// Null batch (bialign_null.hip): write the replicas of virtual pairs first .. first + count into the replica buffers, and
+// reduce every real pair's replica scores (d_scores) into d_null_stats; both on the engine's stream.
+int launch_shuffle_null(bialign_batch* b, int first, int count);
+int launch_null_stats(bialign_batch* b, const int32_t* d_observed);
 
 // ---- launching: every kernel of the library starts through launch() or launch_team()
 // Dynamic LDS beyond 64 KiB has to be allowed per kernel, ahead of a launch or an occupancy query.

@@ -1,0 +1,126 @@
+// bialign_null.hpp -- shuffled-null significance: the replicas' B codes and the per-pair reduction of their scores.
+//
+// A null batch (bialign_batch_create_null) is a SCORE_ONLY batch of npairs * R *virtual* pairs, virtual pair
+// v = p * R + r being real pair p against replica r of its B molecule.  The sweeps run on it exactly as on any batch:
+// a virtual pair's PairDesc::seq_a is the real pair's, its seq_b points into the replica buffers, which
+// shuffle_codes_kernel fills from the one uploaded copy of B.  null_stats_kernel then reduces every real pair's R
+// scores to exact integers; no floating point on the device.
+//
+// The permutation is the one include/bialign.h states (normative there; bialign_amd/significance.py mirrors it).
+//
+// Mapping of the shuffle: one thread per virtual pair.  It copies B into its own slice of the replica buffers and
+// runs the Fisher-Yates swaps there in place (swapping the values is the same as gathering through the permuted
+// index array: seq'[x] = seq_b[perm[x]]).  The chain of swaps is sequential per replica by definition, the replicas
+// are independent: npairs * R threads, each O(m) dependent byte accesses that stay in L2 -- against O(m^2) lattice
+// cells per replica in the sweep.  Vector loads and stores, 64-bit offsets, no atomics, no LDS.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/bialign.h"
+#include "bialign_types.hpp"
+
+namespace bialign {
+
+__host__ __device__ inline uint32_t null_mix(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7FEB352Du;
+  x ^= x >> 15;
+  x *= 0x846CA68Bu;
+  x ^= x >> 16;
+  return x;
+}
+__host__ __device__ inline uint32_t null_hash(uint32_t seed, uint32_t p, uint32_t r) {
+  return null_mix(null_mix(null_mix(seed ^ 0x9E3779B9u) + p) + r);
+}
+// in [0, t]
+__host__ __device__ inline uint32_t null_draw(uint32_t h, uint32_t t) {
+  return (uint32_t)(((uint64_t)null_mix(h + t) * (uint64_t)(t + 1)) >> 32);
+}
+
+struct ShuffleArgs {
+  const PairDesc* pairs;    // the VIRTUAL pairs: m, and seq_b = start of the replica's slice in dst_seq / dst_cls
+  const int64_t* src_off;   // [real pairs] start of pair p's B in src_seq / src_cls
+  const uint8_t *src_seq, *src_cls;  // the uploaded B codes
+  uint8_t *dst_seq, *dst_cls;        // the replica buffers
+  int32_t first, count;     // virtual pairs first .. first + count
+  int32_t replicas;
+  uint32_t seed;
+};
+
+constexpr int NULL_BLOCK = 256;
+
+__global__ __launch_bounds__(NULL_BLOCK) void shuffle_codes_kernel(ShuffleArgs A) {
+  const int64_t t0 = (int64_t)blockIdx.x * NULL_BLOCK + threadIdx.x;
+  if (t0 >= A.count) return;
+  const int32_t v = A.first + (int32_t)t0;
+  const int32_t p = v / A.replicas, r = v - p * A.replicas;
+  const PairDesc& pd = A.pairs[v];
+  const int32_t m = pd.m;
+  const uint8_t* const ss = A.src_seq + A.src_off[p];
+  const uint8_t* const sc = A.src_cls + A.src_off[p];
+  uint8_t* const ds = A.dst_seq + pd.seq_b;
+  uint8_t* const dc = A.dst_cls + pd.seq_b;
+  for (int32_t x = 0; x < m; ++x) {
+    ds[x] = ss[x];
+    dc[x] = sc[x];
+  }
+  const uint32_t h = null_hash(A.seed, (uint32_t)p, (uint32_t)r);
+  for (int32_t t = m - 1; t >= 1; --t) {
+    const uint32_t j = null_draw(h, (uint32_t)t);  // <= t < m: inside the slice
+    const uint8_t st = ds[t], ct = dc[t], sj = ds[j], cj = dc[j];
+    ds[j] = st;
+    dc[j] = ct;
+    ds[t] = sj;
+    dc[t] = cj;
+  }
+}
+
+struct NullStatsArgs {
+  const int32_t* scores;    // [npairs * replicas], pair-major
+  const int32_t* observed;  // [npairs] or nullptr
+  bialign_null_stats* out;  // [npairs]
+  int32_t npairs, replicas;
+};
+
+// One wave per real pair: lanes stride over its R scores, then a butterfly over the wave.  |score| < 2^28 and
+// R * bound^2 < 2^63 are the host's checks (bialign_batch_create_null), so neither sum can overflow.
+__global__ __launch_bounds__(NULL_BLOCK) void null_stats_kernel(NullStatsArgs A) {
+  const int lane = threadIdx.x & 63;
+  const int32_t p = (int32_t)blockIdx.x * (NULL_BLOCK / 64) + (int32_t)(threadIdx.x >> 6);
+  if (p >= A.npairs) return;  // (whole waves leave: p is wave-uniform)
+  const int32_t R = A.replicas;
+  const int32_t* const sc = A.scores + (int64_t)p * R;
+  const bool have_obs = A.observed != nullptr;
+  const int32_t obs = have_obs ? A.observed[p] : 0;
+  int64_t sum = 0, sumsq = 0;
+  int32_t mn = INT32_MAX, mx = INT32_MIN, nge = 0;
+  for (int32_t r = lane; r < R; r += 64) {
+    const int32_t x = sc[r];
+    sum += x;
+    sumsq += (int64_t)x * x;
+    mn = x < mn ? x : mn;
+    mx = x > mx ? x : mx;
+    nge += (have_obs && x >= obs) ? 1 : 0;
+  }
+  for (int d = 32; d >= 1; d >>= 1) {
+    sum += __shfl_xor(sum, d, 64);
+    sumsq += __shfl_xor(sumsq, d, 64);
+    const int32_t omn = __shfl_xor(mn, d, 64), omx = __shfl_xor(mx, d, 64);
+    mn = omn < mn ? omn : mn;
+    mx = omx > mx ? omx : mx;
+    nge += __shfl_xor(nge, d, 64);
+  }
+  if (lane == 0) {
+    bialign_null_stats s;
+    s.sum = sum;
+    s.sumsq = sumsq;
+    s.min = mn;
+    s.max = mx;
+    s.n_ge = nge;
+    s.replicas = R;
+    A.out[p] = s;
+  }
+}
+
+}  // namespace bialign

@@ -10,6 +10,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import lib, check
+from .significance import check_null
 
 STATES = [(0, 1, 0, 1), (0, 1, 1, 0), (0, 1, 1, 1), (1, 0, 0, 1), (1, 0, 1, 0),
           (1, 0, 1, 1), (1, 1, 0, 1), (1, 1, 1, 0), (1, 1, 1, 1)]  # pyx:61-65
@@ -90,11 +91,20 @@ class Batch:
     pair p's ``(up, down, unp)`` (``scoring.rna_features``); with a ``batch.FlatBatch`` they are triples of flat
     float64 arrays indexed like ``seq_a`` / ``seq_b``, so that pairs may share molecules
     (``batch.make_feature_batch``).  Replaces the class codes / ``s2``; excludes ``mu2_dense``.
+    ``null``: ``(replicas, seed)``, a null batch (bialign_batch_create_null; ``significance.null_batch``): every pair
+    against ``replicas`` shuffles of its B molecule, made on the GPU from the one uploaded copy of B, as one score-only
+    batch.  Results come from ``null_scores()`` / ``null_stats()``; ``scores()`` raises.  LOOKUP form only.
     """
 
     def __init__(self, engine, mols_a, mols_b, s1, s2, gap_opening_cost, gap_cost, shift_cost,
                  max_shift, hbm_budget_bytes=0, recurrence=0, mu2_dense=None, score_only=False,
-                 lean_trace=False, mu1_dense=None, mu2_features=None, level_trace=False):
+                 lean_trace=False, mu1_dense=None, mu2_features=None, level_trace=False, null=None):
+        if null is not None:
+            replicas, seed = check_null(null)
+            if mu2_features is not None or mu2_dense is not None or mu1_dense is not None:
+                raise ValueError("a null batch takes the LOOKUP form only (no mu1_dense / mu2_dense / mu2_features)")
+            if lean_trace or level_trace:
+                raise ValueError("a null batch is score-only: lean_trace / level_trace do not apply")
         if mu2_features is not None and mu2_dense is not None:
             raise ValueError("mu2_features and mu2_dense exclude each other")
         if level_trace and (score_only or lean_trace):
@@ -149,7 +159,15 @@ class Batch:
                         _ptr(seq_b, ctypes.c_uint8), _ptr(cls_b, ctypes.c_uint8), mu2_ptr, mu2_off_ptr,
                         mu1_ptr, mu1_off_ptr)
         self._h = ctypes.c_void_p()
-        if feat is None:
+        self.replicas = None
+        if null is not None:
+            if self.npairs * replicas > 2 ** 31 - 1:
+                raise ValueError("npairs * replicas exceeds INT32_MAX")
+            self.replicas = replicas
+            spec = _lib.NullSpec(replicas, seed)
+            check(lib.bialign_batch_create_null(engine._h, ctypes.byref(prm), ctypes.byref(sc), ctypes.byref(pr),
+                                                ctypes.byref(spec), int(hbm_budget_bytes), ctypes.byref(self._h)))
+        elif feat is None:
             check(lib.bialign_batch_create(engine._h, ctypes.byref(prm), ctypes.byref(sc), ctypes.byref(pr),
                                            int(hbm_budget_bytes), ctypes.byref(self._h)))
         else:
@@ -212,6 +230,51 @@ class Batch:
         check(lib.bialign_batch_get_feature_info(self._h, ctypes.byref(fi)))
         return dict(form=("lookup", "dense", "feature")[fi.form], table_bytes=fi.table_bytes,
                     build_ms=fi.build_ms, build_launches=fi.build_launches)
+
+    def null_scores(self):
+        """Null batch: the replica scores of the last run, int32 of shape (npairs, replicas)."""
+        self._need_null()
+        out = np.empty((self.npairs, self.replicas), dtype=np.int32)
+        check(lib.bialign_batch_get_null_scores(self._h, _ptr(out, ctypes.c_int32)))
+        return out
+
+    def null_stats(self, observed=None):
+        """Null batch: every pair's replica scores reduced on the GPU to exact integers -- a dict of arrays ``sum``,
+        ``sumsq`` (int64), ``min``, ``max``, ``n_ge``, ``replicas`` (int32).  ``observed``: the real pairs' scores, for
+        ``n_ge`` = replicas scoring at least that much (0 everywhere when None)."""
+        self._need_null()
+        obs_ptr = None
+        if observed is not None:
+            observed = np.ascontiguousarray(observed, dtype=np.int32)
+            if observed.shape != (self.npairs,):
+                raise ValueError("observed needs one score per pair")
+            obs_ptr = _ptr(observed, ctypes.c_int32)
+        out = (_lib.NullStats * self.npairs)()
+        check(lib.bialign_batch_get_null_stats(self._h, obs_ptr, out))
+        arr = np.frombuffer(out, dtype=np.dtype([("sum", "<i8"), ("sumsq", "<i8"), ("min", "<i4"), ("max", "<i4"),
+                                                  ("n_ge", "<i4"), ("replicas", "<i4")]))
+        return {k: arr[k].copy() for k in arr.dtype.names}
+
+    def null_info(self):
+        """Null batch: kernel times of the shuffle (last run) and of the last ``null_stats`` reduction, and the bytes of
+        the replicas' codes in HBM."""
+        self._need_null()
+        ni = _lib.NullInfo()
+        check(lib.bialign_batch_get_null_info(self._h, ctypes.byref(ni)))
+        return dict(shuffle_ms=ni.shuffle_ms, stats_ms=ni.stats_ms, replica_bytes=ni.replica_bytes)
+
+    def dump_null_codes(self, pair, replica):
+        """Null batch, test hook: (sequence codes, class codes) of one replica of one pair's B as the sweep reads them."""
+        self._need_null()
+        m = int(self.len_b[pair])
+        seq, cls = np.empty(m, dtype=np.uint8), np.empty(m, dtype=np.uint8)
+        check(lib.bialign_batch_dump_null_codes(self._h, int(pair), int(replica), _ptr(seq, ctypes.c_uint8),
+                                                _ptr(cls, ctypes.c_uint8)))
+        return seq, cls
+
+    def _need_null(self):
+        if self.replicas is None:
+            raise ValueError("not a null batch (create it with null=(replicas, seed))")
 
     def dump_mu2(self, pair):
         """The (len A, len B) int32 mu2 table of one pair as the sweep reads it (DENSE or FEATURE form)."""

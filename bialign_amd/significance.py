@@ -1,0 +1,142 @@
+"""Shuffled-null significance: z-scores of optimal scores against shuffles of molecule B made on the GPU.
+
+A raw bi-alignment score grows with both lengths and with composition, so the scores of a long and a short pair do not
+compare.  The standard remedy for pairwise aligners is a shuffled null: align A against R random shuffles of B and
+report where the real score lies in that distribution.  A *null batch* (include/bialign.h, bialign_batch_create_null)
+runs those npairs x R alignments as one score-only batch; B is uploaded once, the GPU writes the shuffles and reduces
+every pair's R scores to exact integer sums, and ``zscores`` forms mean, standard deviation and z from them here.
+
+``permutation`` and ``shuffle_b`` restate the header's permutation in plain Python: the documented way to reproduce
+any replica on the host.  Nothing in this module loads the HIP library before its arguments are checked.
+"""
+import numpy as np
+
+MAX_REPLICAS = 65535  # bialign_null_spec.replicas: 1..65535
+_M32 = 0xFFFFFFFF
+
+
+def _mix(x):
+    x ^= x >> 16
+    x = (x * 0x7FEB352D) & _M32
+    x ^= x >> 15
+    x = (x * 0x846CA68B) & _M32
+    x ^= x >> 16
+    return x
+
+
+def permutation(seed, pair, replica, m):
+    """The permutation of 0..m-1 that replica ``replica`` of pair ``pair`` (its index in the batch) applies to a B
+    molecule of length m under ``seed``: ``shuffled[x] = original[perm[x]]`` (include/bialign.h, THE PERMUTATION)."""
+    seed, pair, replica, m = int(seed), int(pair), int(replica), int(m)
+    if not 0 <= seed <= _M32:
+        raise ValueError("seed must be in 0..2**32-1")
+    if pair < 0 or replica < 0 or m < 1:
+        raise ValueError("pair and replica must be >= 0, m >= 1")
+    h = _mix((_mix((_mix(seed ^ 0x9E3779B9) + pair) & _M32) + replica) & _M32)
+    perm = list(range(m))
+    for t in range(m - 1, 0, -1):
+        j = (_mix((h + t) & _M32) * (t + 1)) >> 32
+        perm[t], perm[j] = perm[j], perm[t]
+    return np.array(perm, dtype=np.int64)
+
+
+#: RNA: the letter a position's structure class is written with in a shuffled molecule (scoring.RNA_UNP, _DOWN, _UP)
+_RNA_CLASS_LETTERS = ".()"
+
+
+def shuffle_b(pair_tuple, seed, pair, replica, rna=False):
+    """``(seqA, seqB, strA, strB)`` -> the same with molecule B as replica ``replica`` of pair ``pair`` has it: the
+    residues of B permuted, each with its structure annotation.  Proteins: the structure letter moves with the residue.
+    ``rna=True``: what moves is the position's structure *class* (unpaired, pairs to the right, pairs to the left --
+    ``scoring.rna_classes``), written ``.``, ``(``, ``)``; such a string lists classes per position and is in general
+    no balanced dot-bracket structure."""
+    seq_a, seq_b, str_a, str_b = pair_tuple
+    if len(seq_b) != len(str_b):
+        raise ValueError("Provided structure and sequence must have the same length.")
+    perm = permutation(seed, pair, replica, len(seq_b)).tolist()
+    if rna:
+        from .scoring import rna_classes
+        str_b = "".join(_RNA_CLASS_LETTERS[c] for c in rna_classes(str_b).tolist())
+    return seq_a, "".join(seq_b[x] for x in perm), str_a, "".join(str_b[x] for x in perm)
+
+
+def check_null(null):
+    """``(replicas, seed)`` of a null batch -> two ints, refused as the C ABI refuses them (before it is called)."""
+    try:
+        replicas, seed = null
+    except (TypeError, ValueError):
+        raise ValueError("null must be (replicas, seed)") from None
+    if isinstance(replicas, bool) or int(replicas) != replicas or not 1 <= int(replicas) <= MAX_REPLICAS:
+        raise ValueError(f"replicas must be an integer in 1..{MAX_REPLICAS}, got {replicas!r}")
+    if int(seed) != seed or not 0 <= int(seed) <= _M32:
+        raise ValueError(f"seed must be an integer in 0..2**32-1, got {seed!r}")
+    return int(replicas), int(seed)
+
+
+def _check_pairs(pairs, replicas, seed):
+    pairs = pairs if isinstance(pairs, list) else list(pairs)
+    replicas, seed = check_null((replicas, seed))
+    if not pairs:
+        raise ValueError("need at least one pair")
+    if len(pairs) * replicas > 2 ** 31 - 1:
+        raise ValueError("npairs * replicas exceeds INT32_MAX")
+    return pairs, replicas, seed
+
+
+def null_batch(pairs, params, replicas, seed=0, engine=None, hbm_budget_bytes=0, recurrence=0):
+    """A null batch of ``pairs`` (``(seqA, seqB, strA, strB)`` each, as ``batch.make_batch`` takes them): every pair
+    against ``replicas`` shuffles of its B.  -> ``engine.Batch``; ``run()`` it, then ``null_scores()`` /
+    ``null_stats()``."""
+    pairs, replicas, seed = _check_pairs(pairs, replicas, seed)
+    from .batch import encode_flat
+    from .engine import Batch, default_engine  # loads the HIP library (no CPU fallback)
+    model, fb = encode_flat(pairs, params)
+    return Batch(engine or default_engine(), fb, None, model.s1, model.s2,
+                 params["gap_opening_cost"], params["gap_cost"], params["shift_cost"], params["max_shift"],
+                 hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence, null=(replicas, seed))
+
+
+def zscores_from_stats(score, stats):
+    """Observed scores and the exact integer reductions of ``Batch.null_stats`` -> dict of arrays ``score``, ``mean``,
+    ``std`` (sample standard deviation, ddof = 1), ``z`` (nan where std is 0 or R is 1), ``p_emp`` =
+    (n_ge + 1) / (R + 1), ``n_ge``, ``replicas``.  The variance's numerator R * sumsq - sum^2 is formed in Python
+    integers, so the same integers always give the same doubles."""
+    score = np.asarray(score, dtype=np.int64)
+    n = len(score)
+    mean, std, z = np.empty(n), np.empty(n), np.empty(n)
+    for p in range(n):
+        R, s1, s2 = int(stats["replicas"][p]), int(stats["sum"][p]), int(stats["sumsq"][p])
+        mean[p] = s1 / R
+        num = R * s2 - s1 * s1  # = R * (R - 1) * variance, exact
+        if num < 0:
+            raise ValueError(f"pair {p}: sums are inconsistent (R * sumsq < sum^2)")
+        std[p] = (num / (R * (R - 1))) ** 0.5 if R > 1 else float("nan")
+        z[p] = (int(score[p]) - mean[p]) / std[p] if R > 1 and num > 0 else float("nan")
+    n_ge = np.asarray(stats["n_ge"], dtype=np.int64)
+    reps = np.asarray(stats["replicas"], dtype=np.int64)
+    return dict(score=score, mean=mean, std=std, z=z, p_emp=(n_ge + 1) / (reps + 1), n_ge=n_ge, replicas=reps)
+
+
+def zscores(pairs, params, replicas=100, seed=0, observed=None, engine=None, hbm_budget_bytes=0, recurrence=0):
+    """z-scores of the pairs' optimal scores against ``replicas`` shuffles of each pair's B (``zscores_from_stats``).
+    ``observed``: the pairs' real scores if the caller has them; else a score-only batch computes them first."""
+    pairs, replicas, seed = _check_pairs(pairs, replicas, seed)
+    if observed is not None:
+        observed = np.ascontiguousarray(observed, dtype=np.int32)
+        if observed.shape != (len(pairs),):
+            raise ValueError("observed needs one score per pair")
+    from .batch import make_batch
+    if observed is None:
+        b = make_batch(pairs, params, engine=engine, hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence, score_only=True)
+        try:
+            b.run()
+            observed = b.scores().copy()
+        finally:
+            b.close()
+    nb = null_batch(pairs, params, replicas, seed=seed, engine=engine, hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence)
+    try:
+        nb.run()
+        stats = nb.null_stats(observed)
+    finally:
+        nb.close()
+    return zscores_from_stats(observed, stats)

@@ -21,6 +21,8 @@
  * (bialign_pairs.mu1_dense / mu2_dense), for scores that depend on position,
  * or, mu2 only, in FEATURE form (bialign_features, bialign_batch_create_features):
  * three doubles per residue from which the GPU builds each pair's table itself.
+ * A *null batch* (bialign_null_spec, bialign_batch_create_null) scores every pair against shuffles of its B
+ * molecule that the GPU makes itself, for z-scores of the optimal scores.
  *
  * The engine is GPU only.  There is no CPU fallback behind this ABI.
  */
@@ -169,6 +171,44 @@ typedef struct bialign_feature_info {
   double build_ms;        /* HIP-event time of the builder launches of the last run; not part of fill_ms */
 } bialign_feature_info;
 
+/* ---- Shuffled-null significance (new in ABI 10 as added symbols: no existing struct or function changes).
+ * A raw bi-alignment score grows with both lengths and with composition; where it lies among the scores of A against
+ * R random shuffles of B is comparable between pairs.  A null batch runs those npairs * R alignments as one SCORE_ONLY
+ * batch: B is uploaded once, the GPU writes the R shuffled copies of every pair's B itself and reduces every pair's R
+ * scores to exact integers (bialign_null_stats); z = (score - mean) / sd is formed by the caller from those.
+ *
+ * THE PERMUTATION (normative; all arithmetic uint32 unless said otherwise):
+ *     mix(x):  x ^= x >> 16;  x *= 0x7FEB352D;  x ^= x >> 15;  x *= 0x846CA68B;  x ^= x >> 16
+ *     h(seed, p, r) = mix(mix(mix(seed ^ 0x9E3779B9) + p) + r)       p = pair index in the batch, r = replica
+ *     draw(t)       = (uint64(mix(h + t)) * (t + 1)) >> 32           in [0, t]
+ *     perm = identity on 0..m-1;  for t = m-1 down to 1: swap(perm[t], perm[draw(t)])
+ *     replica r of pair p's B:  seq'[x] = seq_b[perm[x]],  cls'[x] = cls_b[perm[x]]
+ * (a residue's letter and its structure class move together).  A is never shuffled; m = 1 gives the identity.  The
+ * result depends on (seed, p, r, m) only -- not on chunking, team size, launch order or device; pairs that share a B
+ * molecule through off_b get different shuffles because p differs.  bialign_amd/significance.py restates it in Python.
+ *
+ * LOOKUP form only: with mu1_dense or mu2_dense set bialign_batch_create_null fails with BIALIGN_E_UNSUPPORTED (a
+ * table's columns would have to be permuted per replica), and there is no FEATURE-form null batch. */
+typedef struct bialign_null_spec {
+  int32_t replicas; /* R, 1..65535 */
+  uint32_t seed;
+} bialign_null_spec;
+
+/* Pair p's R replica scores, reduced on the GPU in integer arithmetic (bit for bit reproducible):
+ * mean = sum / R, sample variance = (sumsq - sum * sum / R) / (R - 1). */
+typedef struct bialign_null_stats {
+  int64_t sum, sumsq; /* of the replica scores and of their squares */
+  int32_t min, max;
+  int32_t n_ge;       /* replicas with score >= the observed score (0 when none was given) */
+  int32_t replicas;
+} bialign_null_stats;
+
+typedef struct bialign_null_info {
+  double shuffle_ms;     /* HIP-event time of the shuffle kernel of the last run; not part of fill_ms */
+  double stats_ms;       /* ... of the last bialign_batch_get_null_stats reduction */
+  int64_t replica_bytes; /* the replicas' B codes in HBM, both kinds: 2 * R * (sum of len_b); outside hbm_budget_bytes */
+} bialign_null_info;
+
 typedef struct bialign_batch_info {
   int32_t npairs;
   int32_t nchunks;        /* HBM-budgeted chunks the batch is processed in */
@@ -277,6 +317,30 @@ int bialign_batch_dump_layers(bialign_batch* b, int32_t pair, int32_t* out);
 /* dump_mu2: pair's mu2 table as the sweep reads it, out[(k-1)*m + (l-1)], n*m int32.  FEATURE form: the table is built
  * anew for this pair; DENSE form: the uploaded table; LOOKUP form: BIALIGN_E_INVALID. */
 int bialign_batch_dump_mu2(bialign_batch* b, int32_t pair, int32_t* out);
+
+/* A null batch: every pair of `pairs` against `spec->replicas` shuffles of its B molecule (THE PERMUTATION above), as a
+ * SCORE_ONLY batch of npairs * replicas alignments (the flag is forced; LEAN_TRACE or LEVEL_TRACE in params->flags:
+ * BIALIGN_E_INVALID).  Every max_shift and both recurrences as for SCORE_ONLY (the one-layer recurrence beyond
+ * BIALIGN_MAX_SHIFT_TILED: BIALIGN_E_UNSUPPORTED).  spec NULL, replicas outside 1..65535 or npairs * replicas above
+ * INT32_MAX: BIALIGN_E_INVALID; mu1_dense / mu2_dense set: BIALIGN_E_UNSUPPORTED; a pair whose replica scores could
+ * overflow the int64 sum of squares (replicas * bound^2, bound from the int32 safety window's column bound):
+ * BIALIGN_E_RANGE.  The replicas' codes are input data like the uploaded codes: outside hbm_budget_bytes (and
+ * subtracted from the free memory a budget of 0 is taken from).  run / wait / get_timing / get_info work as for any
+ * batch: bialign_batch_info.npairs is the number of real pairs, cells counts all replicas; bialign_batch_get_scores
+ * fails with BIALIGN_E_INVALID (a null batch has no observed score), get_traces / dump_layers as for SCORE_ONLY. */
+int bialign_batch_create_null(bialign_engine* eng, const bialign_params* params, const bialign_scoring* scoring,
+                              const bialign_pairs* pairs, const bialign_null_spec* spec, int64_t hbm_budget_bytes,
+                              bialign_batch** out);
+/* The replica scores of the last run, pair-major: out[p * replicas + r]. */
+int bialign_batch_get_null_scores(const bialign_batch* b, int32_t* out /* [npairs * replicas] */);
+/* One wave per pair reduces its replica scores on the GPU.  observed: the real pairs' scores (e.g. of a SCORE_ONLY
+ * batch of the same pairs) for n_ge, or NULL (n_ge = 0). */
+int bialign_batch_get_null_stats(const bialign_batch* b, const int32_t* observed /* [npairs] or NULL */,
+                                 bialign_null_stats* out /* [npairs] */);
+int bialign_batch_get_null_info(const bialign_batch* b, bialign_null_info* info);
+/* Test hook: the codes of one replica of one pair's B as the sweep reads them (len_b bytes each; the shuffle kernel is
+ * run for that replica). */
+int bialign_batch_dump_null_codes(bialign_batch* b, int32_t pair, int32_t replica, uint8_t* seq, uint8_t* cls);
 
 #ifdef __cplusplus
 }
