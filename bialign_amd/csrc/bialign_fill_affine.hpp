@@ -296,6 +296,8 @@ __global__ void __launch_bounds__(64 * TW) BIALIGN_WPE_ATTR fill_affine_kernel(c
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   int vm_younger = 0;  // store instructions issued since the last block's DMAs (wave-uniform)
   int pk_all = 0;      // packed records: OR of every offset this lane has stored since the last range check
+  static_assert(!PACK || PK_::check_in_every_gap(GF::BLK),
+                "range check: a test must fall into every non-interior stretch between two strips (pk_all is cleared, not kept, once a row leaves the lattice)");
 
   // Exchange inputs of rows i-1 (what lanes L-W, L-W+1 published for each band column).  They are loop-carried:
   // row r is fetched from the exchange array at the END of a step, as soon as its last consumer of that step is
@@ -369,7 +371,7 @@ __global__ void __launch_bounds__(64 * TW) BIALIGN_WPE_ATTR fill_affine_kernel(c
       // the DMAs just retired were issued at step g - BLK ahead of that step's stores, and vmcnt retires in
       // order: the stores of all steps before g - BLK are acknowledged
       if ((XCU || TW > 1) && L == 0) prog_put(g - GF::BLK);
-      if (PACK && (g & 15) == 0) {  // every 16 steps: an offset since then that does not fit 16 bits (or collides with the -2^30 mark): the host falls back
+      if (PACK && (g & (PK_::CHECK - 1)) == 0) {  // every 16 steps: an offset since then that does not fit 16 bits (or collides with the -2^30 mark): the host falls back
         const bool bad = live && !ghost && (unsigned)pk_all > 0xffffu;
         if (__builtin_amdgcn_ballot_w64(bad) != 0 && L == 0) atomicOr(A.errflag, 2);
         pk_all = 0;

@@ -190,6 +190,8 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   int vm_younger = 0;
   int pk_all = 0;  // OR of every offset this lane has stored since the last range check
+  static_assert(LEAN || PK_::check_in_every_gap(GF::BLK),
+                "range check: a test must fall into every non-interior stretch between two strips (pk_all is cleared, not kept, once a row leaves the lattice)");
 
   // delay-line stage, opaque to the compiler (see fill_affine_kernel)
   auto dmov = [](int& dst, int src) __attribute__((always_inline)) { asm("v_mov_b32 %0, %1" : "=v"(dst) : "v"(src)); };
@@ -218,7 +220,7 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
     if (gt == 0) {
       GF::wait_block(vm_younger);
       if (TW > 1 && L == 0) prog_lds[w] = g - GF::BLK;
-      if (!LEAN && (g & 15) == 0) {  // every 16 steps: an offset since then that does not fit 16 bits (or collides with the -2^30 mark): the host falls back
+      if (!LEAN && (g & (PK_::CHECK - 1)) == 0) {  // every 16 steps: an offset since then that does not fit 16 bits (or collides with the -2^30 mark): the host falls back
         const bool bad = live && !ghost && (unsigned)pk_all > 0xffffu;  // (lanes that hold lattice points in interior steps)
         if (__builtin_amdgcn_ballot_w64(bad) != 0 && L == 0) atomicOr(A.errflag, 2);
         pk_all = 0;

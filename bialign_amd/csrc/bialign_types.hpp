@@ -171,6 +171,17 @@ struct Pack {
   __host__ __device__ static inline int hi(int m) { return m - S; }  // last phase whose points all lie inside the molecule
   __host__ __device__ static inline bool interior(int qs, int c, int m) { return qs >= Q0 && c >= LO && c <= m - S; }
   __host__ __device__ static inline int nbs(int P, int m) { return P - (m - S - LO + 1); }  // full records per strip >= Q0
+  // The sweeps' range check (fill_affine_kernel, fill_affine_slim_kernel): a lane ORs what it stores in interior steps
+  // into an accumulator that is tested at the head of every step that is a multiple of CHECK and of the ghost block, and
+  // after the last step.  A lane whose row leaves the lattice at a strip change CLEARS the accumulator in its next interior
+  // step, so a test has to fall between the last interior step of a strip and the update of the first interior step of the
+  // next.  A wave walks through nbs(P, m) non-interior steps there (phases m - S + 1 .. P - 1, then 0 .. LO - 1; every lane
+  // changes its row among them, at lane 0's phase 2 il + a <= MAXOFF < LO), at least CHECK_GAP since P >= m + 2.
+  static constexpr int CHECK = 16;
+  static constexpr int CHECK_GAP = LO + S + 1;
+  __host__ __device__ static constexpr bool check_in_every_gap(int blk) {
+    return (blk & (blk - 1)) == 0 && (CHECK & (CHECK - 1)) == 0 && (blk > CHECK ? blk : CHECK) <= CHECK_GAP;
+  }
   // index of the full record of a non-interior step among the pair's full records
   __host__ __device__ static inline int64_t bidx(int qs, int c, int P, int m) {
     if (qs < Q0) return (int64_t)qs * P + c;
