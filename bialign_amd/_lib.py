@@ -126,6 +126,11 @@ SYMBOLS = [
     ("bialign_batch_get_null_stats", ctypes.c_int, [ctypes.c_void_p, c_i32p, ctypes.POINTER(NullStats)]),
     ("bialign_batch_get_null_info", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(NullInfo)]),
     ("bialign_batch_dump_null_codes", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, c_u8p, c_u8p]),
+    ("bialign_batch_create_null_features", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.POINTER(Params), ctypes.POINTER(Scoring), ctypes.POINTER(Pairs),
+      ctypes.POINTER(Features), ctypes.POINTER(NullSpec), ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p)]),
+    ("bialign_batch_dump_null_features", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, c_f64p, c_f64p, c_f64p]),
 ]
 
 #: Declared in include/bialign.h as well, but kept apart from SYMBOLS: tests/test_capi_symbols.py collects the header's

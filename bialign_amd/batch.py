@@ -95,7 +95,7 @@ def _check_storage(score_only, lean_trace, level_trace):
 
 
 def make_feature_batch(molecules, pair_index, params, engine=None, hbm_budget_bytes=0, recurrence=0,
-                       score_only=False, lean_trace=False, mu1_dense=None, level_trace=False):
+                       score_only=False, lean_trace=False, mu1_dense=None, level_trace=False, null=None):
     """Batch with mu2 in FEATURE form (include/bialign.h, bialign_features): RNA molecules with real-valued
     structure features, e.g. from predicted base-pair probabilities.  ``molecules``: a list of
     ``(seq, (up, down, unp))``, three numbers per residue as ``scoring.rna_features`` makes them; ``pair_index``: a
@@ -103,9 +103,17 @@ def make_feature_batch(molecules, pair_index, params, engine=None, hbm_budget_by
     so an all-against-all batch costs O(sum of lengths) on the host; the GPU builds each chunk's score tables.
     The structure weight is ``params["structure_weight"]``.  Bad arguments raise ValueError before the library is
     called: an index outside ``molecules``, ragged or mis-sized feature arrays, a NaN or infinite feature, and
-    ValueError("math domain error") for a negative one."""
+    ValueError("math domain error") for a negative one.
+    ``null``: ``(replicas, seed)``, a FEATURE-form null batch (``significance.null_feature_batch``): every pair against
+    ``replicas`` shuffles of its B molecule, a residue's three numbers moving with its letter; score-only, mu1 in
+    LOOKUP form."""
     from .scoring import check_features
     _check_storage(score_only, lean_trace, level_trace)
+    if null is not None:
+        from .significance import check_null
+        null = check_null(null)
+        if lean_trace or level_trace or mu1_dense is not None:
+            raise ValueError("a null batch is score-only and takes mu1 in LOOKUP form: no lean_trace / level_trace / mu1_dense")
     molecules = list(molecules)
     pair_index = [(int(ia), int(ib)) for ia, ib in pair_index]
     if not molecules or not pair_index:
@@ -131,7 +139,7 @@ def make_feature_batch(molecules, pair_index, params, engine=None, hbm_budget_by
                  params["gap_opening_cost"], params["gap_cost"], params["shift_cost"],
                  params["max_shift"], hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence,
                  score_only=score_only, lean_trace=lean_trace, mu1_dense=mu1_dense, level_trace=level_trace,
-                 mu2_features=(int(params["structure_weight"]), flat, flat))
+                 mu2_features=(int(params["structure_weight"]), flat, flat), null=null)
 
 
 def shard(npairs, rank, world_size, costs=None):

@@ -391,6 +391,9 @@ int plan_chunks(bialign_batch* b, const std::vector<int64_t>& pair_dwords, int64
   b->max_chunk_tab_dwords = 0;
   int64_t total_dw = 0;
   for (int p = 0; p < npairs; ++p) {
+    if (pair_dwords[p] + tab_of(p) > budget_dw && b->null_R && feat)
+      return fail(BIALIGN_E_NOMEM, "pair %d: one replica needs %lld bytes of layers and %lld of mu2 table, budget is %lld",
+                  p / b->null_R, (long long)pair_dwords[p] * 4, (long long)tab_of(p) * 4, (long long)budget_dw * 4);
     if (pair_dwords[p] + tab_of(p) > budget_dw && b->null_R)
       return fail(BIALIGN_E_NOMEM, "pair %d: one replica needs %lld bytes of layers, budget is %lld", p / b->null_R,
                   (long long)pair_dwords[p] * 4, (long long)budget_dw * 4);
@@ -520,12 +523,16 @@ struct NullPlan {
   uint32_t seed;
   int32_t npairs;                // real pairs
   const int64_t* off_b;          // [npairs] start of real pair p's B in seq_b / cls_b
-  const uint8_t *seq_b, *cls_b;  // the B codes as the caller gave them
+  const uint8_t *seq_b, *cls_b;  // the B codes as the caller gave them (cls_b: nullptr in FEATURE form)
   int64_t tot_b;                 // their extent
+  int32_t max_m;                 // the longest B
+  // FEATURE form: ft->up_b / down_b / unp_b are the real pairs' planes, indexed by off_b above like seq_b
 };
 
 // bialign_batch_create (ft == nullptr), bialign_batch_create_features, and bialign_batch_create_null (nul != nullptr: pr
-// describes the virtual pairs, whose off_b point into replica buffers that are allocated here and filled on the device)
+// describes the virtual pairs, whose off_b point into replica buffers that are allocated here and filled on the device);
+// bialign_batch_create_null_features gives both: ft's B planes are then the real pairs' (NullPlan::off_b), the replica
+// planes are allocated here
 static int create_batch(bialign_engine* eng, const bialign_params* prm, const bialign_scoring* sc,
                         const bialign_pairs* pr, const bialign_features* ft, int64_t hbm_budget, bialign_batch** out,
                         const NullPlan* nul = nullptr) {
@@ -619,10 +626,15 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
       return BIALIGN_OK;
     };
     bmax = 0;
-    for (int p = 0; p < pr->npairs; ++p) {
+    // null batch: the real pairs, once each -- a shuffle moves B's numbers and leaves their maxima, so the real pair's
+    // bound serves all its replicas (virtual pair p * R is real pair p's first; its B is at the plan's off_b)
+    const int nreal = nul ? nul->npairs : pr->npairs;
+    for (int p = 0; p < nreal; ++p) {
       const MolMax *ma = nullptr, *mb = nullptr;
-      if (int rc = check(0, p, pr->off_a[p], std::max(pr->len_a[p], 0), ft->up_a, ft->down_a, ft->unp_a, &ma)) return rc;
-      if (int rc = check(1, p, pr->off_b[p], std::max(pr->len_b[p], 0), ft->up_b, ft->down_b, ft->unp_b, &mb)) return rc;
+      const size_t v = nul ? (size_t)p * nul->replicas : (size_t)p;
+      const int64_t off_b = nul ? nul->off_b[p] : pr->off_b[p];
+      if (int rc = check(0, p, pr->off_a[v], std::max(pr->len_a[v], 0), ft->up_a, ft->down_a, ft->unp_a, &ma)) return rc;
+      if (int rc = check(1, p, off_b, std::max(pr->len_b[v], 0), ft->up_b, ft->down_b, ft->unp_b, &mb)) return rc;
       const double bound = std::fabs((double)ft->structure_weight) *
                            (std::sqrt(ma->up * mb->up) + std::sqrt(ma->down * mb->down) + std::sqrt(ma->unp * mb->unp));
       if (!(bound < 1073741824.0))  // 2^30: outside any window, and an int64 could not hold much more
@@ -710,6 +722,8 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
   if (nul) {
     HIP_TRY(b->d_seq_b.alloc((size_t)tot_b));
     HIP_TRY(b->d_cls_b.alloc((size_t)tot_b));
+    if (b->feat) HIP_TRY(b->d_feat_b.alloc(3 * (size_t)tot_b));  // ... and so the replicas' three planes of features
+    b->null_max_m = nul->max_m;
   }
 
   // ---- chunking under the HBM budget; inside a chunk longest sweeps first
@@ -855,12 +869,15 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
   HIP_TRY(b->d_s1.upload(sc->s1, (size_t)sc->k1 * sc->k1, st));
   HIP_TRY(b->d_s2.upload(sc->s2, (size_t)sc->k2 * sc->k2, st));
   std::vector<uint8_t> zeros;
-  if (b->dense || b->dense1) zeros.assign((size_t)std::max(tot_a, tot_b), 0);  // codes a dense form replaces are unused
+  if (b->dense || b->dense1) zeros.assign((size_t)(nul ? tot_a : std::max(tot_a, tot_b)), 0);  // codes a dense form replaces are unused
   HIP_TRY(b->d_seq_a.upload(b->dense1 ? zeros.data() : pr->seq_a, tot_a, st));
   HIP_TRY(b->d_cls_a.upload(b->dense ? zeros.data() : pr->cls_a, tot_a, st));
   if (nul) {  // B once, as the caller gave it: the shuffle kernel writes d_seq_b / d_cls_b from it ahead of every run's sweeps
     HIP_TRY(b->d_null_seq.upload(nul->seq_b, (size_t)nul->tot_b, st));
-    HIP_TRY(b->d_null_cls.upload(nul->cls_b, (size_t)nul->tot_b, st));
+    if (b->feat)  // FEATURE form: no classes; the replicas' (unused) class codes are zero like those of any FEATURE batch
+      HIP_TRY(hipMemsetAsync(b->d_cls_b.p, 0, std::max<size_t>((size_t)tot_b, 1), st));
+    else
+      HIP_TRY(b->d_null_cls.upload(nul->cls_b, (size_t)nul->tot_b, st));
     HIP_TRY(b->d_null_off.upload(nul->off_b, (size_t)nul->npairs, st));
     HIP_TRY(b->d_null_stats.alloc((size_t)nul->npairs));
     for (hipEvent_t& e : b->null_evs) HIP_TRY(hipEventCreate(&e));
@@ -876,10 +893,13 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
     const double* src_a[3] = {ft->up_a, ft->down_a, ft->unp_a};
     const double* src_b[3] = {ft->up_b, ft->down_b, ft->unp_b};
     HIP_TRY(b->d_feat_a.alloc(3 * (size_t)tot_a));
-    HIP_TRY(b->d_feat_b.alloc(3 * (size_t)tot_b));
+    // null batch: d_feat_b is the replica planes (allocated above, filled by the shuffle kernel); B's own go beside d_null_seq
+    DevBuf<double>& up_b = nul ? b->d_null_feat : b->d_feat_b;
+    const int64_t src_tot_b = nul ? nul->tot_b : tot_b;
+    HIP_TRY(up_b.alloc(3 * (size_t)src_tot_b));
     for (int f = 0; f < 3; ++f) {
       HIP_TRY(hipMemcpyAsync(b->d_feat_a.p + (size_t)f * tot_a, src_a[f], (size_t)tot_a * sizeof(double), hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(b->d_feat_b.p + (size_t)f * tot_b, src_b[f], (size_t)tot_b * sizeof(double), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(up_b.p + (size_t)f * src_tot_b, src_b[f], (size_t)src_tot_b * sizeof(double), hipMemcpyHostToDevice, st));
     }
     if (b->dense1) {
       mu1_offs.resize(pr->npairs);
@@ -946,8 +966,9 @@ int bialign_batch_create_features(bialign_engine* eng, const bialign_params* prm
   return create_batch(eng, prm, sc, pr, ft, hbm_budget, out);
 }
 
-int bialign_batch_create_null(bialign_engine* eng, const bialign_params* prm, const bialign_scoring* sc,
-                              const bialign_pairs* pr, const bialign_null_spec* spec, int64_t hbm_budget, bialign_batch** out) {
+// bialign_batch_create_null (ft == nullptr) and bialign_batch_create_null_features
+static int create_null(bialign_engine* eng, const bialign_params* prm, const bialign_scoring* sc, const bialign_pairs* pr,
+                       const bialign_features* ft, const bialign_null_spec* spec, int64_t hbm_budget, bialign_batch** out) {
   if (out) *out = nullptr;
   if (!eng || !prm || !sc || !pr || !out) return fail(BIALIGN_E_INVALID, "NULL argument");
   if (!spec) return fail(BIALIGN_E_INVALID, "spec is NULL");
@@ -958,23 +979,28 @@ int bialign_batch_create_null(bialign_engine* eng, const bialign_params* prm, co
     return fail(BIALIGN_E_INVALID, "npairs * replicas = %lld exceeds INT32_MAX", (long long)pr->npairs * spec->replicas);
   if (prm->flags & (BIALIGN_BATCH_LEAN_TRACE | BIALIGN_BATCH_LEVEL_TRACE))
     return fail(BIALIGN_E_INVALID, "a null batch is SCORE_ONLY: LEAN_TRACE / LEVEL_TRACE do not apply");
-  if (pr->mu1_dense || pr->mu2_dense)
+  if (!ft && (pr->mu1_dense || pr->mu2_dense))
     return fail(BIALIGN_E_UNSUPPORTED, "null batches take the LOOKUP form only (a dense table's columns would have to be permuted per replica)");
+  if (ft && pr->mu1_dense)  // (mu2_dense is ignored in FEATURE form, as in bialign_batch_create_features)
+    return fail(BIALIGN_E_UNSUPPORTED, "FEATURE-form null batches take mu1 in LOOKUP form only (a dense table's columns would have to be permuted per replica)");
   if (!pr->len_a || !pr->len_b || !pr->off_a || !pr->off_b) return fail(BIALIGN_E_INVALID, "len_a / len_b / off_a / off_b are NULL");
   if (!pr->seq_a || !pr->seq_b) return fail(BIALIGN_E_INVALID, "seq_a / seq_b are NULL (LOOKUP form)");
-  if (!pr->cls_a || !pr->cls_b) return fail(BIALIGN_E_INVALID, "cls_a / cls_b are NULL (LOOKUP form)");
+  if (!ft && (!pr->cls_a || !pr->cls_b)) return fail(BIALIGN_E_INVALID, "cls_a / cls_b are NULL (LOOKUP form)");
   const int R = spec->replicas;
   const size_t nv = (size_t)pr->npairs * R;
-  // the virtual pairs, pair-major: v = p * R + r is real pair p against replica r, whose codes start at
-  // R * (sum of len_b before p) + r * len_b[p] of the replica buffers
+  // the virtual pairs, pair-major: v = p * R + r is real pair p against replica r, whose codes (and, in FEATURE form,
+  // features) start at R * (sum of len_b before p) + r * len_b[p] of the replica buffers
   std::vector<int32_t> len_a(nv), len_b(nv);
   std::vector<int64_t> off_a(nv), off_b(nv);
-  NullPlan plan{R, spec->seed, pr->npairs, pr->off_b, pr->seq_b, pr->cls_b, 0};
+  NullPlan plan{R, spec->seed, pr->npairs, pr->off_b, pr->seq_b, ft ? nullptr : pr->cls_b, 0, 0};
   int64_t before = 0;
   for (int p = 0; p < pr->npairs; ++p) {
     const int n = pr->len_a[p], m = pr->len_b[p];
     if (n < 1 || m < 1) return fail(BIALIGN_E_INVALID, "pair %d: empty molecule (n=%d, m=%d)", p, n, m);
     if (pr->off_b[p] < 0) return fail(BIALIGN_E_INVALID, "pair %d: negative off_b", p);
+    if (ft && m > NULL_FEAT_MAX_M)  // the feature shuffle's index array is uint16 (bialign_null.hpp)
+      return fail(BIALIGN_E_UNSUPPORTED, "pair %d: B molecule of %d residues, a FEATURE-form null batch takes up to %d", p, m, NULL_FEAT_MAX_M);
+    plan.max_m = std::max(plan.max_m, m);
     for (int r = 0; r < R; ++r) {
       const size_t v = (size_t)p * R + r;
       len_a[v] = n;
@@ -991,9 +1017,25 @@ int bialign_batch_create_null(bialign_engine* eng, const bialign_params* prm, co
   vp.len_b = len_b.data();
   vp.off_a = off_a.data();
   vp.off_b = off_b.data();
+  if (ft) vp.mu2_dense = nullptr, vp.mu2_off = nullptr;  // ignored in FEATURE form
   bialign_params vprm = *prm;
   vprm.flags = BIALIGN_BATCH_SCORE_ONLY;
-  return create_batch(eng, &vprm, sc, &vp, nullptr, hbm_budget, out, &plan);
+  return create_batch(eng, &vprm, sc, &vp, ft, hbm_budget, out, &plan);
+}
+
+int bialign_batch_create_null(bialign_engine* eng, const bialign_params* prm, const bialign_scoring* sc,
+                              const bialign_pairs* pr, const bialign_null_spec* spec, int64_t hbm_budget, bialign_batch** out) {
+  return create_null(eng, prm, sc, pr, nullptr, spec, hbm_budget, out);
+}
+
+int bialign_batch_create_null_features(bialign_engine* eng, const bialign_params* prm, const bialign_scoring* sc,
+                                       const bialign_pairs* pr, const bialign_features* ft, const bialign_null_spec* spec,
+                                       int64_t hbm_budget, bialign_batch** out) {
+  if (out) *out = nullptr;
+  if (!ft) return fail(BIALIGN_E_INVALID, "feat is NULL");
+  if (!ft->up_a || !ft->down_a || !ft->unp_a || !ft->up_b || !ft->down_b || !ft->unp_b)
+    return fail(BIALIGN_E_INVALID, "a feature array is NULL");
+  return create_null(eng, prm, sc, pr, ft, spec, hbm_budget, out);
 }
 
 void bialign_batch_destroy(bialign_batch* b) {
@@ -1298,6 +1340,9 @@ int bialign_batch_dump_layers(bialign_batch* b, int32_t pair, int32_t* out) {
 
 int bialign_batch_dump_mu2(bialign_batch* b, int32_t pair, int32_t* out) {
   if (!b || !out) return fail(BIALIGN_E_INVALID, "NULL argument");
+  if (b->null_R)
+    return fail(BIALIGN_E_INVALID, "a null batch has no table of a real pair to dump: its tables are those of the replicas "
+                                   "(bialign_batch_dump_null_features shows what they are built from)");
   if (pair < 0 || pair >= b->npairs) return fail(BIALIGN_E_INVALID, "pair %d out of range", pair);
   if (!b->dense) return fail(BIALIGN_E_INVALID, "mu2 of this batch is in LOOKUP form: there is no table to dump");
   if (int rc = bialign_batch_wait(b)) return rc;
@@ -1363,7 +1408,7 @@ int bialign_batch_get_null_info(const bialign_batch* b, bialign_null_info* info)
   if (int rc = bialign_batch_wait(const_cast<bialign_batch*>(b))) return rc;
   info->shuffle_ms = b->shuffle_ms;
   info->stats_ms = b->stats_ms;
-  info->replica_bytes = (int64_t)(b->d_seq_b.n + b->d_cls_b.n);
+  info->replica_bytes = (int64_t)(b->d_seq_b.n + b->d_cls_b.n + (b->feat ? b->d_feat_b.n * sizeof(double) : 0));
   return BIALIGN_OK;
 }
 
@@ -1381,6 +1426,26 @@ int bialign_batch_dump_null_codes(bialign_batch* b, int32_t pair, int32_t replic
   const PairDesc& d = b->pairs[v];
   HIP_TRY(hipMemcpyAsync(seq, b->d_seq_b.p + d.seq_b, (size_t)d.m, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(cls, b->d_cls_b.p + d.seq_b, (size_t)d.m, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return BIALIGN_OK;
+}
+
+int bialign_batch_dump_null_features(bialign_batch* b, int32_t pair, int32_t replica, double* up, double* down, double* unp) {
+  if (!b || !up || !down || !unp) return fail(BIALIGN_E_INVALID, "NULL argument");
+  if (!b->null_R || !b->feat) return fail(BIALIGN_E_INVALID, "not a FEATURE-form null batch (bialign_batch_create_null_features)");
+  if (pair < 0 || pair >= b->null_npairs) return fail(BIALIGN_E_INVALID, "pair %d out of range", pair);
+  if (replica < 0 || replica >= b->null_R) return fail(BIALIGN_E_INVALID, "replica %d out of range", replica);
+  if (int rc = bialign_batch_wait(b)) return rc;
+  HIP_TRY(hipSetDevice(b->eng->device));
+  hipStream_t st = b->eng->stream;
+  HIP_TRY(hipStreamWaitEvent(st, b->uploaded, 0));
+  const int v = pair * b->null_R + replica;
+  if (int rc = launch_shuffle_null(b, v, 1)) return rc;
+  const PairDesc& d = b->pairs[v];
+  double* const out[3] = {up, down, unp};
+  for (int f = 0; f < 3; ++f)
+    HIP_TRY(hipMemcpyAsync(out[f], b->d_feat_b.p + (size_t)f * b->feat_tot_b + d.seq_b, (size_t)d.m * sizeof(double),
+                           hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return BIALIGN_OK;
 }

@@ -151,6 +151,11 @@ struct bialign_batch {
   uint32_t null_seed = 0;
   DevBuf<uint8_t> d_null_seq, d_null_cls;
   DevBuf<int64_t> d_null_off;
+  // FEATURE-form null batch (bialign_batch_create_null_features): d_feat_b holds the replica planes (feat_tot_b = R * sum of
+  // len_b doubles per plane, indexed by the virtual pairs' seq_b like d_seq_b), shuffle_features_kernel fills them and
+  // d_seq_b from the uploaded B features kept here, three planes of d_null_seq.n doubles; d_cls_b stays zero.
+  DevBuf<double> d_null_feat;
+  int null_max_m = 0;                       // longest B of the batch: sizes the shuffle's index array in LDS
   DevBuf<int32_t> d_null_obs;               // observed scores of the last bialign_batch_get_null_stats
   DevBuf<bialign_null_stats> d_null_stats;  // ... and its result
   hipEvent_t null_evs[4] = {nullptr, nullptr, nullptr, nullptr};  // around the shuffle launch of a run, around the reduction
@@ -239,6 +244,8 @@ int launch_build_mu2(bialign_batch* b, int first, int count);
 
 // Null batch (bialign_null.hip): write the replicas of virtual pairs first .. first + count into the replica buffers, and
 // reduce every real pair's replica scores (d_scores) into d_null_stats; both on the engine's stream.
+// (FEATURE-form null batches: codes and feature planes; its index array in LDS is uint16, so len_b <= NULL_FEAT_MAX_M)
+constexpr int NULL_FEAT_MAX_M = 65535;
 int launch_shuffle_null(bialign_batch* b, int first, int count);
 int launch_null_stats(bialign_batch* b, const int32_t* d_observed);
 

@@ -4,11 +4,13 @@
 // v = p * R + r being real pair p against replica r of its B molecule.  The sweeps run on it exactly as on any batch:
 // a virtual pair's PairDesc::seq_a is the real pair's, its seq_b points into the replica buffers, which
 // shuffle_codes_kernel fills from the one uploaded copy of B.  null_stats_kernel then reduces every real pair's R
-// scores to exact integers; no floating point on the device.
+// scores to exact integers; no floating point on the device.  A FEATURE-form null batch
+// (bialign_batch_create_null_features) has replica planes of doubles beside the replica codes, which
+// shuffle_features_kernel fills (below); build_mu2_kernel reads them through the same seq_b.
 //
 // The permutation is the one include/bialign.h states (normative there; bialign_amd/significance.py mirrors it).
 //
-// Mapping of the shuffle: one thread per virtual pair.  It copies B into its own slice of the replica buffers and
+// Mapping of shuffle_codes_kernel: one thread per virtual pair.  It copies B into its own slice of the replica buffers and
 // runs the Fisher-Yates swaps there in place (swapping the values is the same as gathering through the permuted
 // index array: seq'[x] = seq_b[perm[x]]).  The chain of swaps is sequential per replica by definition, the replicas
 // are independent: npairs * R threads, each O(m) dependent byte accesses that stay in L2 -- against O(m^2) lattice
@@ -120,6 +122,83 @@ __global__ __launch_bounds__(NULL_BLOCK) void null_stats_kernel(NullStatsArgs A)
     s.n_ge = nge;
     s.replicas = R;
     A.out[p] = s;
+  }
+}
+
+// ---- FEATURE-form null batches (bialign_batch_create_null_features): the replicas' sequence codes and their three
+// planes of doubles (up, down, unp), a residue's letter and its three numbers moving together.
+//
+// Mapping: one wave per virtual pair, not shuffle_codes_kernel's thread per replica -- that one swaps in place in
+// global memory, which with three doubles per residue would be four dependent 8-byte read-modify-writes per swap.
+// Here the swaps run on an index array in LDS and the data moves once:
+//   1. perm = identity, uint16 (m < 65536 is the host's check), 2 * m bytes of dynamic LDS;
+//   2. draw(t) depends on (h, t) only, not on the array: per block of 64 values of t every lane computes one draw into
+//      a register, and the chain of swaps -- sequential by definition -- takes them from there by readlane.  The loop
+//      is wave-uniform; the two LDS reads of a step are broadcasts, lane 0 alone stores (so lane 0 only ever reads
+//      what it wrote itself: no barrier inside the chain);
+//   3. all lanes gather seq, up, down, unp through perm: random reads inside the one B molecule (24 * m bytes, cache
+//      resident), coalesced stores of 512 bytes per plane and wave.  The doubles are moved, never recomputed.
+// (Draws kept in LDS as well would double the array to 4 * m bytes, beyond a workgroup's 160 KiB for the longest
+// molecules the engine takes; registers + readlane need none.)
+// Vector loads and stores, 64-bit offsets, no atomics.  m = 1: the chain is empty, the identity.
+struct ShuffleFeatArgs {
+  const PairDesc* pairs;    // the VIRTUAL pairs: m, and seq_b = start of the replica's slice in dst_seq / dst_*
+  const int64_t* src_off;   // [real pairs] start of pair p's B in src_seq / src_*
+  const uint8_t* src_seq;   // the uploaded B codes
+  const double *src_up, *src_down, *src_unp;  // ... and features
+  uint8_t* dst_seq;         // the replica buffers
+  double *dst_up, *dst_down, *dst_unp;
+  int32_t first, count;     // virtual pairs first .. first + count
+  int32_t replicas;
+  uint32_t seed;
+};
+
+// (the index array is uint16: m <= NULL_FEAT_MAX_M = 65535, bialign_host.hpp, checked where the batch is created)
+constexpr int NULL_FEAT_MAX_GRID = 1 << 20;  // workgroups of a launch; more virtual pairs loop
+
+__global__ __launch_bounds__(64) void shuffle_features_kernel(ShuffleFeatArgs A) {
+  extern __shared__ uint16_t null_perm[];  // [longest m of the launch]
+  const int32_t lane = (int32_t)threadIdx.x;
+  for (int64_t w = blockIdx.x; w < A.count; w += gridDim.x) {
+    const int32_t v = A.first + (int32_t)w;
+    const int32_t p = v / A.replicas, r = v - p * A.replicas;
+    const PairDesc& pd = A.pairs[v];
+    const int32_t m = __builtin_amdgcn_readfirstlane(pd.m);
+    const int64_t src = A.src_off[p], dst = pd.seq_b;
+    const uint32_t h = null_hash(A.seed, (uint32_t)p, (uint32_t)r);
+    for (int32_t x = lane; x < m; x += 64) null_perm[x] = (uint16_t)x;
+    __syncthreads();
+    for (int32_t tb = (m - 1) & ~63; tb >= 0; tb -= 64) {
+      const uint32_t d = null_draw(h, (uint32_t)(tb + lane));  // lane k holds draw(tb + k) <= tb + k
+      const int32_t khi = m - 1 - tb < 63 ? m - 1 - tb : 63, klo = tb == 0 ? 1 : 0;
+      for (int32_t k = khi; k >= klo; --k) {
+        const int32_t t = tb + k;                                    // m - 1 down to 1
+        const int32_t j = __builtin_amdgcn_readlane((int32_t)d, k);  // <= t < m: inside the array
+        const uint16_t pt = null_perm[t], pj = null_perm[j];
+        if (lane == 0) {
+          null_perm[t] = pj;
+          null_perm[j] = pt;
+        }
+      }
+    }
+    __syncthreads();
+    // (source and replica buffers are distinct allocations: the four loads of a residue go out together)
+    const uint8_t* __restrict__ const ss = A.src_seq + src;
+    const double* __restrict__ const su = A.src_up + src;
+    const double* __restrict__ const sd = A.src_down + src;
+    const double* __restrict__ const sp = A.src_unp + src;
+    uint8_t* __restrict__ const ds = A.dst_seq + dst;
+    double* __restrict__ const du = A.dst_up + dst;
+    double* __restrict__ const dd = A.dst_down + dst;
+    double* __restrict__ const dp = A.dst_unp + dst;
+    for (int32_t x = lane; x < m; x += 64) {
+      const int32_t s = null_perm[x];  // < m
+      ds[x] = ss[s];
+      du[x] = su[s];
+      dd[x] = sd[s];
+      dp[x] = sp[s];
+    }
+    __syncthreads();  // (the next virtual pair of this workgroup overwrites the array)
   }
 }
 

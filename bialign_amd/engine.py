@@ -93,7 +93,9 @@ class Batch:
     (``batch.make_feature_batch``).  Replaces the class codes / ``s2``; excludes ``mu2_dense``.
     ``null``: ``(replicas, seed)``, a null batch (bialign_batch_create_null; ``significance.null_batch``): every pair
     against ``replicas`` shuffles of its B molecule, made on the GPU from the one uploaded copy of B, as one score-only
-    batch.  Results come from ``null_scores()`` / ``null_stats()``; ``scores()`` raises.  LOOKUP form only.
+    batch.  Results come from ``null_scores()`` / ``null_stats()``; ``scores()`` raises.  mu1 in LOOKUP form; mu2 in
+    LOOKUP form or, together with ``mu2_features``, in FEATURE form (bialign_batch_create_null_features;
+    ``significance.null_feature_batch``): a residue's three numbers then move with its letter.
     """
 
     def __init__(self, engine, mols_a, mols_b, s1, s2, gap_opening_cost, gap_cost, shift_cost,
@@ -101,8 +103,9 @@ class Batch:
                  lean_trace=False, mu1_dense=None, mu2_features=None, level_trace=False, null=None):
         if null is not None:
             replicas, seed = check_null(null)
-            if mu2_features is not None or mu2_dense is not None or mu1_dense is not None:
-                raise ValueError("a null batch takes the LOOKUP form only (no mu1_dense / mu2_dense / mu2_features)")
+            if mu2_dense is not None or mu1_dense is not None:
+                raise ValueError("a null batch takes mu1 in LOOKUP form and mu2 in LOOKUP or FEATURE form "
+                                 "(no mu1_dense / mu2_dense)")
             if lean_trace or level_trace:
                 raise ValueError("a null batch is score-only: lean_trace / level_trace do not apply")
         if mu2_features is not None and mu2_dense is not None:
@@ -165,8 +168,15 @@ class Batch:
                 raise ValueError("npairs * replicas exceeds INT32_MAX")
             self.replicas = replicas
             spec = _lib.NullSpec(replicas, seed)
-            check(lib.bialign_batch_create_null(engine._h, ctypes.byref(prm), ctypes.byref(sc), ctypes.byref(pr),
-                                                ctypes.byref(spec), int(hbm_budget_bytes), ctypes.byref(self._h)))
+            if feat is None:
+                check(lib.bialign_batch_create_null(engine._h, ctypes.byref(prm), ctypes.byref(sc), ctypes.byref(pr),
+                                                    ctypes.byref(spec), int(hbm_budget_bytes), ctypes.byref(self._h)))
+            else:
+                sw, fa, fb = feat
+                ft = _lib.Features(sw, *(_ptr(x, ctypes.c_double) for x in fa + fb))
+                check(lib.bialign_batch_create_null_features(engine._h, ctypes.byref(prm), ctypes.byref(sc),
+                                                             ctypes.byref(pr), ctypes.byref(ft), ctypes.byref(spec),
+                                                             int(hbm_budget_bytes), ctypes.byref(self._h)))
         elif feat is None:
             check(lib.bialign_batch_create(engine._h, ctypes.byref(prm), ctypes.byref(sc), ctypes.byref(pr),
                                            int(hbm_budget_bytes), ctypes.byref(self._h)))
@@ -257,7 +267,7 @@ class Batch:
 
     def null_info(self):
         """Null batch: kernel times of the shuffle (last run) and of the last ``null_stats`` reduction, and the bytes of
-        the replicas' codes in HBM."""
+        the replicas' codes (FEATURE form: and feature planes) in HBM."""
         self._need_null()
         ni = _lib.NullInfo()
         check(lib.bialign_batch_get_null_info(self._h, ctypes.byref(ni)))
@@ -271,6 +281,16 @@ class Batch:
         check(lib.bialign_batch_dump_null_codes(self._h, int(pair), int(replica), _ptr(seq, ctypes.c_uint8),
                                                 _ptr(cls, ctypes.c_uint8)))
         return seq, cls
+
+    def dump_null_features(self, pair, replica):
+        """FEATURE-form null batch, test hook: ``(up, down, unp)`` of one replica of one pair's B as the table builder
+        reads them, float64 arrays of len B."""
+        self._need_null()
+        m = int(self.len_b[pair])
+        out = tuple(np.empty(m, dtype=np.float64) for _ in range(3))
+        check(lib.bialign_batch_dump_null_features(self._h, int(pair), int(replica),
+                                                   *(_ptr(x, ctypes.c_double) for x in out)))
+        return out
 
     def _need_null(self):
         if self.replicas is None:

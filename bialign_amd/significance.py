@@ -6,8 +6,13 @@ report where the real score lies in that distribution.  A *null batch* (include/
 runs those npairs x R alignments as one score-only batch; B is uploaded once, the GPU writes the shuffles and reduces
 every pair's R scores to exact integer sums, and ``zscores`` forms mean, standard deviation and z from them here.
 
-``permutation`` and ``shuffle_b`` restate the header's permutation in plain Python: the documented way to reproduce
-any replica on the host.  Nothing in this module loads the HIP library before its arguments are checked.
+RNA molecules with real-valued structure features (``batch.make_feature_batch``) have the same in FEATURE form:
+``null_feature_batch`` / ``zscores_features`` (bialign_batch_create_null_features), a residue's three numbers moving
+with its letter.
+
+``permutation``, ``shuffle_b`` and ``shuffle_features`` restate the header's permutation in plain Python: the
+documented way to reproduce any replica on the host.  Nothing in this module loads the HIP library before its
+arguments are checked.
 """
 import numpy as np
 
@@ -58,6 +63,22 @@ def shuffle_b(pair_tuple, seed, pair, replica, rna=False):
         from .scoring import rna_classes
         str_b = "".join(_RNA_CLASS_LETTERS[c] for c in rna_classes(str_b).tolist())
     return seq_a, "".join(seq_b[x] for x in perm), str_a, "".join(str_b[x] for x in perm)
+
+
+def shuffle_features(seq, feats, seed, pair, replica):
+    """``(seq, (up, down, unp))`` of a B molecule as replica ``replica`` of pair ``pair`` has it in a FEATURE-form null
+    batch: a plain gather through ``permutation`` -- the letter and its three numbers land at the same index, and the
+    numbers are moved, not recomputed (float64, bit for bit the source's).  -> ``(str, (up, down, unp))``."""
+    seq = str(seq)
+    try:
+        up, down, unp = feats
+    except (TypeError, ValueError):
+        raise ValueError("features must be a triple (up, down, unp)") from None
+    planes = tuple(np.asarray(f, dtype=np.float64) for f in (up, down, unp))
+    if any(f.shape != (len(seq),) for f in planes):
+        raise ValueError("every feature must hold one number per residue")
+    perm = permutation(seed, pair, replica, len(seq))
+    return "".join(seq[x] for x in perm.tolist()), tuple(np.ascontiguousarray(f[perm]) for f in planes)
 
 
 def check_null(null):
@@ -134,6 +155,65 @@ def zscores(pairs, params, replicas=100, seed=0, observed=None, engine=None, hbm
         finally:
             b.close()
     nb = null_batch(pairs, params, replicas, seed=seed, engine=engine, hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence)
+    try:
+        nb.run()
+        stats = nb.null_stats(observed)
+    finally:
+        nb.close()
+    return zscores_from_stats(observed, stats)
+
+
+def _check_feature_args(molecules, pair_index, replicas, seed):
+    """The arguments of a FEATURE-form null batch, checked as ``batch.make_feature_batch`` and the C ABI check them --
+    here, so that nothing is loaded for a call that cannot succeed.  -> (molecules, pair_index, replicas, seed)."""
+    from .scoring import check_features
+    replicas, seed = check_null((replicas, seed))
+    molecules = list(molecules)
+    pair_index = [(int(ia), int(ib)) for ia, ib in pair_index]
+    if not molecules or not pair_index:
+        raise ValueError("need at least one molecule and one pair")
+    for p, (ia, ib) in enumerate(pair_index):
+        if not (0 <= ia < len(molecules) and 0 <= ib < len(molecules)):
+            raise ValueError(f"pair {p}: molecule index ({ia}, {ib}) out of range (0..{len(molecules) - 1})")
+    if len(pair_index) * replicas > 2 ** 31 - 1:
+        raise ValueError("npairs * replicas exceeds INT32_MAX")
+    for t, (seq, feats) in enumerate(molecules):
+        check_features(feats, len(str(seq)), f"molecule {t}")
+    return molecules, pair_index, replicas, seed
+
+
+def null_feature_batch(molecules, pair_index, params, replicas, seed=0, engine=None, hbm_budget_bytes=0, recurrence=0):
+    """A FEATURE-form null batch: ``molecules`` (``(seq, (up, down, unp))`` each) and ``pair_index`` as
+    ``batch.make_feature_batch`` takes them, every pair against ``replicas`` shuffles of its B -- letters and
+    features, made on the GPU from the one uploaded copy of every molecule.  -> ``engine.Batch``; ``run()`` it, then
+    ``null_scores()`` / ``null_stats()``."""
+    molecules, pair_index, replicas, seed = _check_feature_args(molecules, pair_index, replicas, seed)
+    from .batch import make_feature_batch
+    return make_feature_batch(molecules, pair_index, params, engine=engine, hbm_budget_bytes=hbm_budget_bytes,
+                              recurrence=recurrence, score_only=True, null=(replicas, seed))
+
+
+def zscores_features(molecules, pair_index, params, replicas=100, seed=0, observed=None, engine=None, hbm_budget_bytes=0,
+                     recurrence=0):
+    """``zscores`` for RNA molecules with real-valued structure features: z-scores of the pairs' optimal scores
+    against ``replicas`` shuffles of each pair's B (``zscores_from_stats``).  ``observed``: the pairs' real scores if
+    the caller has them; else ``make_feature_batch(score_only=True)`` computes them first."""
+    molecules, pair_index, replicas, seed = _check_feature_args(molecules, pair_index, replicas, seed)
+    if observed is not None:
+        observed = np.ascontiguousarray(observed, dtype=np.int32)
+        if observed.shape != (len(pair_index),):
+            raise ValueError("observed needs one score per pair")
+    if observed is None:
+        from .batch import make_feature_batch
+        b = make_feature_batch(molecules, pair_index, params, engine=engine, hbm_budget_bytes=hbm_budget_bytes,
+                               recurrence=recurrence, score_only=True)
+        try:
+            b.run()
+            observed = b.scores().copy()
+        finally:
+            b.close()
+    nb = null_feature_batch(molecules, pair_index, params, replicas, seed=seed, engine=engine,
+                            hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence)
     try:
         nb.run()
         stats = nb.null_stats(observed)

@@ -22,7 +22,8 @@
  * or, mu2 only, in FEATURE form (bialign_features, bialign_batch_create_features):
  * three doubles per residue from which the GPU builds each pair's table itself.
  * A *null batch* (bialign_null_spec, bialign_batch_create_null) scores every pair against shuffles of its B
- * molecule that the GPU makes itself, for z-scores of the optimal scores.
+ * molecule that the GPU makes itself, for z-scores of the optimal scores; bialign_batch_create_null_features is the
+ * same with mu2 in FEATURE form.
  *
  * The engine is GPU only.  There is no CPU fallback behind this ABI.
  */
@@ -187,8 +188,14 @@ typedef struct bialign_feature_info {
  * result depends on (seed, p, r, m) only -- not on chunking, team size, launch order or device; pairs that share a B
  * molecule through off_b get different shuffles because p differs.  bialign_amd/significance.py restates it in Python.
  *
- * LOOKUP form only: with mu1_dense or mu2_dense set bialign_batch_create_null fails with BIALIGN_E_UNSUPPORTED (a
- * table's columns would have to be permuted per replica), and there is no FEATURE-form null batch. */
+ * bialign_batch_create_null takes the LOOKUP form only: with mu1_dense or mu2_dense set it fails with
+ * BIALIGN_E_UNSUPPORTED (a table's columns would have to be permuted per replica).
+ * FEATURE form of mu2 (RNA with real-valued structure features, bialign_features): bialign_batch_create_null_features.
+ * Replica r of pair p's B then has, with the same perm,
+ *     seq'[x] = seq_b[perm[x]],  up'[x] = up_b[perm[x]],  down'[x] = down_b[perm[x]],  unp'[x] = unp_b[perm[x]]
+ * -- a residue's letter and its three numbers move together, and the doubles are moved, never recomputed: each is bit
+ * for bit the source's.  This is the same null model as the LOOKUP RNA null, in which a position's structure annotation
+ * (there its class, here its three numbers) travels with its letter. */
 typedef struct bialign_null_spec {
   int32_t replicas; /* R, 1..65535 */
   uint32_t seed;
@@ -206,7 +213,9 @@ typedef struct bialign_null_stats {
 typedef struct bialign_null_info {
   double shuffle_ms;     /* HIP-event time of the shuffle kernel of the last run; not part of fill_ms */
   double stats_ms;       /* ... of the last bialign_batch_get_null_stats reduction */
-  int64_t replica_bytes; /* the replicas' B codes in HBM, both kinds: 2 * R * (sum of len_b); outside hbm_budget_bytes */
+  int64_t replica_bytes; /* the replicas' B codes in HBM, both kinds: 2 * R * (sum of len_b); outside hbm_budget_bytes.
+                            A FEATURE-form null batch adds the replicas' three planes of doubles: what was allocated
+                            is codes plus planes, 26 * R * (sum of len_b) */
 } bialign_null_info;
 
 typedef struct bialign_batch_info {
@@ -315,7 +324,8 @@ int bialign_batch_get_traces(const bialign_batch* b, uint8_t* trace, int64_t* tr
  * out must hold nlayers*(n+1)*(m+1)*(2s+1)^2 int32. */
 int bialign_batch_dump_layers(bialign_batch* b, int32_t pair, int32_t* out);
 /* dump_mu2: pair's mu2 table as the sweep reads it, out[(k-1)*m + (l-1)], n*m int32.  FEATURE form: the table is built
- * anew for this pair; DENSE form: the uploaded table; LOOKUP form: BIALIGN_E_INVALID. */
+ * anew for this pair; DENSE form: the uploaded table; LOOKUP form, and any null batch (its tables are the replicas'):
+ * BIALIGN_E_INVALID. */
 int bialign_batch_dump_mu2(bialign_batch* b, int32_t pair, int32_t* out);
 
 /* A null batch: every pair of `pairs` against `spec->replicas` shuffles of its B molecule (THE PERMUTATION above), as a
@@ -341,6 +351,33 @@ int bialign_batch_get_null_info(const bialign_batch* b, bialign_null_info* info)
 /* Test hook: the codes of one replica of one pair's B as the sweep reads them (len_b bytes each; the shuffle kernel is
  * run for that replica). */
 int bialign_batch_dump_null_codes(bialign_batch* b, int32_t pair, int32_t replica, uint8_t* seq, uint8_t* cls);
+
+/* A null batch with mu2 in FEATURE form: the union of bialign_batch_create_features and bialign_batch_create_null (new in
+ * ABI 10 as added symbols: no existing struct or function changes).  B's codes and features are uploaded once; the GPU
+ * writes the R shuffled copies of every pair's B -- sequence codes and three planes of doubles, THE PERMUTATION above --
+ * and builds each chunk's mu2 tables from the replicas' planes.  SCORE_ONLY is forced (LEAN_TRACE / LEVEL_TRACE:
+ * BIALIGN_E_INVALID).  mu1 in LOOKUP form only: mu1_dense set is BIALIGN_E_UNSUPPORTED, for the reason
+ * bialign_batch_create_null gives; cls_a / cls_b / mu2_dense / mu2_off are ignored (may be NULL).  A NULL argument, feat
+ * or one of its arrays NULL, spec NULL, replicas outside 1..65535, npairs * replicas above INT32_MAX, a NaN, infinite or
+ * negative feature (the message names pair and position): BIALIGN_E_INVALID.  The features are checked, and the pair's
+ * bound (bialign_batch_create_features) is taken, on the real pairs, once each: a shuffle moves B's numbers and leaves
+ * their maxima, so the real pair's bound serves all its replicas; a bound outside the int32 safety window, or replicas *
+ * bound^2 outside int64: BIALIGN_E_RANGE.  The one-layer recurrence beyond BIALIGN_MAX_SHIFT_TILED, or a B molecule of
+ * more than 65535 residues (the shuffle's index array is 16 bits wide): BIALIGN_E_UNSUPPORTED.
+ * Memory: the replicas' planes, 24 * R * (sum of len_b) bytes, are input data like the replicas' codes -- outside
+ * hbm_budget_bytes, and subtracted from the free memory a budget of 0 is taken from.  Every replica's n x m table is
+ * per-chunk scratch inside the chunk plan, as for any FEATURE batch; one replica's table plus layers beyond the budget:
+ * BIALIGN_E_NOMEM.
+ * get_null_scores / get_null_stats / get_null_info / dump_null_codes (cls: zeros) work as for any null batch,
+ * get_feature_info says FEATURE (build_ms, build_launches, table_bytes as usual); get_scores, get_traces, dump_layers
+ * and dump_mu2 refuse as for null batches. */
+int bialign_batch_create_null_features(bialign_engine* eng, const bialign_params* params, const bialign_scoring* scoring,
+                                       const bialign_pairs* pairs, const bialign_features* feat,
+                                       const bialign_null_spec* spec, int64_t hbm_budget_bytes, bialign_batch** out);
+/* Test hook: the features of one replica of one pair's B as the table builder reads them (len_b doubles each; the
+ * shuffle kernel is run for that replica).  Not a FEATURE-form null batch: BIALIGN_E_INVALID. */
+int bialign_batch_dump_null_features(bialign_batch* b, int32_t pair, int32_t replica, double* up, double* down,
+                                     double* unp);
 
 #ifdef __cplusplus
 }
