@@ -131,6 +131,10 @@ SYMBOLS = [
       ctypes.POINTER(Features), ctypes.POINTER(NullSpec), ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p)]),
     ("bialign_batch_dump_null_features", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, c_f64p, c_f64p, c_f64p]),
+    ("bialign_batch_create_null_dense", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.POINTER(Params), ctypes.POINTER(Scoring), ctypes.POINTER(Pairs),
+      ctypes.POINTER(NullSpec), ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p)]),
+    ("bialign_batch_dump_null_tables", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, c_i32p, c_i32p]),
 ]
 
 #: Declared in include/bialign.h as well, but kept apart from SYMBOLS: tests/test_capi_symbols.py collects the header's

@@ -75,17 +75,25 @@ def encode_pairs(pairs, params):
 
 
 def make_batch(pairs, params, engine=None, hbm_budget_bytes=0, recurrence=0, mu2_dense=None,
-               score_only=False, lean_trace=False, mu1_dense=None, level_trace=False):
+               score_only=False, lean_trace=False, mu1_dense=None, level_trace=False, null_dense=None):
     """``mu1_dense`` / ``mu2_dense``: optional lists of one (len A, len B) int table per pair (engine.Batch).
-    ``level_trace``: full results from checkpointed levels, for bands beyond the tiled kernels (engine.Batch)."""
+    ``level_trace``: full results from checkpointed levels, for bands beyond the tiled kernels (engine.Batch).
+    ``null_dense``: ``(replicas, seed)``, a null batch of these pairs with their dense tables
+    (``significance.null_dense_batch``): score-only, no ``lean_trace`` / ``level_trace``."""
     _check_storage(score_only, lean_trace, level_trace)
+    if null_dense is not None:
+        from .significance import check_dense_args
+        if lean_trace or level_trace:
+            raise ValueError("a null batch is score-only: lean_trace / level_trace do not apply")
+        pairs, replicas, seed = check_dense_args(pairs, null_dense, mu1_dense, mu2_dense)
+        null_dense = (replicas, seed)
     from .engine import Batch, default_engine  # loads the HIP library (no CPU fallback)
     model, fb = encode_flat(pairs, params)
     return Batch(engine or default_engine(), fb, None, model.s1, model.s2,
                  params["gap_opening_cost"], params["gap_cost"], params["shift_cost"],
                  params["max_shift"], hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence,
                  mu2_dense=mu2_dense, score_only=score_only, lean_trace=lean_trace, mu1_dense=mu1_dense,
-                 level_trace=level_trace)
+                 level_trace=level_trace, **({} if null_dense is None else dict(null_dense=null_dense)))
 
 
 def _check_storage(score_only, lean_trace, level_trace):

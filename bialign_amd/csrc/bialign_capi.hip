@@ -378,11 +378,12 @@ int launch_dump_any(const bialign_batch* b, const DeviceBatch& v, int pid, int32
 // idle); inside a chunk the longest sweeps are launched first.
 //   FEATURE-form batches: a pair's mu2 table (bialign_batch::tab_dwords) is per-chunk scratch in a buffer of its own
 // and counts toward the budget with the pair's layers; its tables lie end to end like the layers (PairDesc::tab_off).
+// So do a replica's permuted tables in a DENSE-form null batch.
 // layer_cap / tab_cap: a re-plan within buffers the batch already holds -- neither kind may outgrow its buffer.
 int plan_chunks(bialign_batch* b, const std::vector<int64_t>& pair_dwords, int64_t budget_dw, int64_t layer_cap = INT64_MAX,
                 int64_t tab_cap = INT64_MAX) {
   const int npairs = b->npairs;
-  const bool feat = b->feat;
+  const bool feat = b->tab_scratch();  // (FEATURE form, and the DENSE-form null batch: its replicas' permuted tables)
   auto tab_of = [&](int p) { return feat ? b->tab_dwords[p] : (int64_t)0; };
   b->order.resize(npairs);
   std::iota(b->order.begin(), b->order.end(), 0);
@@ -391,6 +392,9 @@ int plan_chunks(bialign_batch* b, const std::vector<int64_t>& pair_dwords, int64
   b->max_chunk_tab_dwords = 0;
   int64_t total_dw = 0;
   for (int p = 0; p < npairs; ++p) {
+    if (pair_dwords[p] + tab_of(p) > budget_dw && b->null_dense)
+      return fail(BIALIGN_E_NOMEM, "pair %d: one replica needs %lld bytes of layers and %lld of permuted tables, budget is %lld",
+                  p / b->null_R, (long long)pair_dwords[p] * 4, (long long)tab_of(p) * 4, (long long)budget_dw * 4);
     if (pair_dwords[p] + tab_of(p) > budget_dw && b->null_R && feat)
       return fail(BIALIGN_E_NOMEM, "pair %d: one replica needs %lld bytes of layers and %lld of mu2 table, budget is %lld",
                   p / b->null_R, (long long)pair_dwords[p] * 4, (long long)tab_of(p) * 4, (long long)budget_dw * 4);
@@ -527,6 +531,9 @@ struct NullPlan {
   int64_t tot_b;                 // their extent
   int32_t max_m;                 // the longest B
   // FEATURE form: ft->up_b / down_b / unp_b are the real pairs' planes, indexed by off_b above like seq_b
+  // DENSE form (bialign_batch_create_null_dense): the virtual pairs' mu1_off / mu2_off are their real pair's, and the
+  // tables are read through the first replica of each
+  bool dense = false;
 };
 
 // bialign_batch_create (ft == nullptr), bialign_batch_create_features, and bialign_batch_create_null (nul != nullptr: pr
@@ -562,7 +569,7 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
   b->dense = b->feat || pr->mu2_dense != nullptr;  // (the FEATURE form's tables feed the DENSE consumers)
   if (b->feat) b->feat_sw = ft->structure_weight;
   b->dense1 = pr->mu1_dense != nullptr;
-  if (nul) b->null_R = nul->replicas, b->null_npairs = nul->npairs, b->null_seed = nul->seed;
+  if (nul) b->null_R = nul->replicas, b->null_npairs = nul->npairs, b->null_seed = nul->seed, b->null_dense = nul->dense;
   const auto shown = [&](int p) { return nul ? p / nul->replicas : p; };  // the pair an error message names: the real one
   b->lean_trace = (prm->flags & BIALIGN_BATCH_LEAN_TRACE) != 0;
   b->lean = b->lean_trace || (prm->flags & BIALIGN_BATCH_SCORE_ONLY) != 0;
@@ -593,9 +600,11 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
   for (int t = 0; t < sc->k1 * sc->k1; ++t) amax = std::max<int64_t>(amax, std::llabs((long long)sc->s1[t]));
   int64_t bmax = 0;
   for (int t = 0; t < sc->k2 * sc->k2; ++t) bmax = std::max<int64_t>(bmax, std::llabs((long long)sc->s2[t]));
+  // (null batch: the real pairs' tables, once each, through their first replicas -- a column permutation leaves a table's
+  //  maximum where it is)
   auto dense_max = [&](const int32_t* tab, const int64_t* off) {
     int64_t mx = 0;
-    for (int p = 0; p < pr->npairs; ++p) {
+    for (int p = 0; p < pr->npairs; p += nul ? nul->replicas : 1) {
       const int64_t cnt = (int64_t)std::max(pr->len_a[p], 0) * std::max(pr->len_b[p], 0);
       for (int64_t t = 0; t < cnt; ++t) mx = std::max<int64_t>(mx, std::llabs((long long)tab[off[p] + t]));
     }
@@ -674,6 +683,7 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
     d.tab_off = tot_tab;  // dense forms: the pair's tables, end to end (mu2's, then mu1's); FEATURE form: plan_chunks
     tot_tab += (int64_t)n * m * ((b->dense ? 1 : 0) + (b->dense1 ? 1 : 0));
     if (b->feat) b->tab_dwords.push_back((int64_t)n * m * (b->dense1 ? 2 : 1));
+    if (b->null_dense) b->tab_dwords.push_back((int64_t)n * m * ((b->dense ? 1 : 0) + (b->dense1 ? 1 : 0)));
     b->trace_bytes += d.trace_cap;
     b->cells += cells_of(n, m, S);
     tot_a = std::max<int64_t>(tot_a, pr->off_a[p] + n);
@@ -724,13 +734,19 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
     HIP_TRY(b->d_cls_b.alloc((size_t)tot_b));
     if (b->feat) HIP_TRY(b->d_feat_b.alloc(3 * (size_t)tot_b));  // ... and so the replicas' three planes of features
     b->null_max_m = nul->max_m;
+    if (b->null_dense) {  // ... the replicas' permutations, and the real pairs' tables, which stay resident
+      HIP_TRY(b->d_null_perm.alloc((size_t)tot_b));
+      size_t real_dw = 0;
+      for (int p = 0; p < pr->npairs; p += nul->replicas) real_dw += (size_t)b->tab_dwords[p];
+      HIP_TRY(b->d_null_tab.alloc(real_dw));
+    }
   }
 
   // ---- chunking under the HBM budget; inside a chunk longest sweeps first
   size_t free_b = 0, total_b = 0;
   HIP_TRY(hipMemGetInfo(&free_b, &total_b));
   free_b += (eng->layer_cache.n + eng->layer_cache2.n) * sizeof(int32_t);  // reused or released below, ours either way
-  if (b->feat) free_b += eng->tab_cache.n * sizeof(int32_t);               // ... and so the cached table buffer
+  if (b->tab_scratch()) free_b += eng->tab_cache.n * sizeof(int32_t);      // ... and so the cached table buffer
   int64_t budget = hbm_budget > 0 ? hbm_budget : (int64_t)(free_b * 0.85);
   budget = std::min<int64_t>(budget, (int64_t)(free_b * 0.95));
   const int64_t budget_dw = budget / 4;
@@ -758,7 +774,7 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
   // what the largest pair needs inside the budget: its layers, and in FEATURE form its mu2 table
   auto max_need = [&]() {
     int64_t mx = 0;
-    for (int p = 0; p < pr->npairs; ++p) mx = std::max(mx, pair_dwords[p] + (b->feat ? b->tab_dwords[p] : 0));
+    for (int p = 0; p < pr->npairs; ++p) mx = std::max(mx, pair_dwords[p] + (b->tab_scratch() ? b->tab_dwords[p] : 0));
     return mx;
   };
   // lean traceback: few pairs -> several strips per round (they re-sweep in parallel), as memory allows
@@ -846,8 +862,9 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
     if (int rc = plan_chunks(b.get(), pair_dwords, smaller)) return rc;
   }
 
-  // ---- FEATURE form: the table buffer of the largest chunk, the engine's cached one if that is large enough
-  if (b->feat) {
+  // ---- FEATURE form, DENSE-form null batch: the table buffer of the largest chunk, the engine's cached one if that is
+  //      large enough
+  if (b->tab_scratch()) {
     const size_t tab_dw = (size_t)b->max_chunk_tab_dwords;
     if (eng->tab_cache.p && eng->tab_cache.n >= tab_dw) {
       b->d_tab.swap(eng->tab_cache);
@@ -857,7 +874,7 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
         const hipError_t err = hipGetLastError();
         b->d_tab.p = nullptr;
         b->d_tab.n = 0;
-        return fail(BIALIGN_E_DEVICE, "hipMalloc of %zu bytes of mu2 table storage failed: %s", tab_dw * 4, hipGetErrorString(err));
+        return fail(BIALIGN_E_DEVICE, "hipMalloc of %zu bytes of table storage failed: %s", tab_dw * 4, hipGetErrorString(err));
       }
     }
   }
@@ -873,8 +890,10 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
   HIP_TRY(b->d_seq_a.upload(b->dense1 ? zeros.data() : pr->seq_a, tot_a, st));
   HIP_TRY(b->d_cls_a.upload(b->dense ? zeros.data() : pr->cls_a, tot_a, st));
   if (nul) {  // B once, as the caller gave it: the shuffle kernel writes d_seq_b / d_cls_b from it ahead of every run's sweeps
-    HIP_TRY(b->d_null_seq.upload(nul->seq_b, (size_t)nul->tot_b, st));
-    if (b->feat)  // FEATURE form: no classes; the replicas' (unused) class codes are zero like those of any FEATURE batch
+    // (codes a dense form replaces are not uploaded: the replicas' codes of that kind are zero like those of any dense batch)
+    if (b->dense1) HIP_TRY(hipMemsetAsync(b->d_seq_b.p, 0, std::max<size_t>((size_t)tot_b, 1), st));
+    else HIP_TRY(b->d_null_seq.upload(nul->seq_b, (size_t)nul->tot_b, st));
+    if (b->dense)  // (FEATURE form too: no classes)
       HIP_TRY(hipMemsetAsync(b->d_cls_b.p, 0, std::max<size_t>((size_t)tot_b, 1), st));
     else
       HIP_TRY(b->d_null_cls.upload(nul->cls_b, (size_t)nul->tot_b, st));
@@ -911,6 +930,19 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
       HIP_TRY(b->d_mu1.upload(tabs.data(), tabs.size(), st));
       HIP_TRY(b->d_mu1_off.upload(mu1_offs.data(), mu1_offs.size(), st));
     }
+  } else if (b->null_dense) {  // the REAL pairs' tables end to end, mu2's, then mu1's; every replica's are made from them per chunk
+    const int R = nul->replicas;
+    std::vector<int64_t> offs((size_t)nul->npairs);
+    tabs.resize(b->d_null_tab.n);
+    int64_t at = 0;
+    for (int p = 0; p < nul->npairs; ++p) {
+      const size_t v = (size_t)p * R, nm = (size_t)pr->len_a[v] * pr->len_b[v];
+      offs[p] = at;
+      if (b->dense) std::memcpy(tabs.data() + at, pr->mu2_dense + pr->mu2_off[v], nm * sizeof(int32_t)), at += (int64_t)nm;
+      if (b->dense1) std::memcpy(tabs.data() + at, pr->mu1_dense + pr->mu1_off[v], nm * sizeof(int32_t)), at += (int64_t)nm;
+    }
+    if (!tabs.empty()) HIP_TRY(hipMemcpyAsync(b->d_null_tab.p, tabs.data(), tabs.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(b->d_null_tab_off.upload(offs.data(), offs.size(), st));
   } else if (b->dense || b->dense1) {  // the pairs' tables end to end (PairDesc::tab_off): mu2's, then mu1's
     tabs.resize((size_t)tot_tab);
     for (int p = 0; p < pr->npairs; ++p) {
@@ -966,9 +998,10 @@ int bialign_batch_create_features(bialign_engine* eng, const bialign_params* prm
   return create_batch(eng, prm, sc, pr, ft, hbm_budget, out);
 }
 
-// bialign_batch_create_null (ft == nullptr) and bialign_batch_create_null_features
+// bialign_batch_create_null (ft == nullptr), bialign_batch_create_null_features, and bialign_batch_create_null_dense (dense)
 static int create_null(bialign_engine* eng, const bialign_params* prm, const bialign_scoring* sc, const bialign_pairs* pr,
-                       const bialign_features* ft, const bialign_null_spec* spec, int64_t hbm_budget, bialign_batch** out) {
+                       const bialign_features* ft, const bialign_null_spec* spec, int64_t hbm_budget, bialign_batch** out,
+                       bool dense = false) {
   if (out) *out = nullptr;
   if (!eng || !prm || !sc || !pr || !out) return fail(BIALIGN_E_INVALID, "NULL argument");
   if (!spec) return fail(BIALIGN_E_INVALID, "spec is NULL");
@@ -979,20 +1012,27 @@ static int create_null(bialign_engine* eng, const bialign_params* prm, const bia
     return fail(BIALIGN_E_INVALID, "npairs * replicas = %lld exceeds INT32_MAX", (long long)pr->npairs * spec->replicas);
   if (prm->flags & (BIALIGN_BATCH_LEAN_TRACE | BIALIGN_BATCH_LEVEL_TRACE))
     return fail(BIALIGN_E_INVALID, "a null batch is SCORE_ONLY: LEAN_TRACE / LEVEL_TRACE do not apply");
-  if (!ft && (pr->mu1_dense || pr->mu2_dense))
+  if (dense && !pr->mu1_dense && !pr->mu2_dense)
+    return fail(BIALIGN_E_INVALID, "neither mu1_dense nor mu2_dense is set: a null batch in LOOKUP form is bialign_batch_create_null's");
+  if (dense && pr->mu1_dense && !pr->mu1_off) return fail(BIALIGN_E_INVALID, "mu1_dense given without mu1_off");
+  if (dense && pr->mu2_dense && !pr->mu2_off) return fail(BIALIGN_E_INVALID, "mu2_dense given without mu2_off");
+  if (!dense && !ft && (pr->mu1_dense || pr->mu2_dense))
     return fail(BIALIGN_E_UNSUPPORTED, "null batches take the LOOKUP form only (a dense table's columns would have to be permuted per replica)");
   if (ft && pr->mu1_dense)  // (mu2_dense is ignored in FEATURE form, as in bialign_batch_create_features)
     return fail(BIALIGN_E_UNSUPPORTED, "FEATURE-form null batches take mu1 in LOOKUP form only (a dense table's columns would have to be permuted per replica)");
   if (!pr->len_a || !pr->len_b || !pr->off_a || !pr->off_b) return fail(BIALIGN_E_INVALID, "len_a / len_b / off_a / off_b are NULL");
-  if (!pr->seq_a || !pr->seq_b) return fail(BIALIGN_E_INVALID, "seq_a / seq_b are NULL (LOOKUP form)");
-  if (!ft && (!pr->cls_a || !pr->cls_b)) return fail(BIALIGN_E_INVALID, "cls_a / cls_b are NULL (LOOKUP form)");
+  // (DENSE form: the codes of whichever of mu1 / mu2 is in LOOKUP form)
+  if (!(dense && pr->mu1_dense) && (!pr->seq_a || !pr->seq_b)) return fail(BIALIGN_E_INVALID, "seq_a / seq_b are NULL (LOOKUP form)");
+  if (!ft && !(dense && pr->mu2_dense) && (!pr->cls_a || !pr->cls_b)) return fail(BIALIGN_E_INVALID, "cls_a / cls_b are NULL (LOOKUP form)");
   const int R = spec->replicas;
   const size_t nv = (size_t)pr->npairs * R;
   // the virtual pairs, pair-major: v = p * R + r is real pair p against replica r, whose codes (and, in FEATURE form,
   // features) start at R * (sum of len_b before p) + r * len_b[p] of the replica buffers
   std::vector<int32_t> len_a(nv), len_b(nv);
   std::vector<int64_t> off_a(nv), off_b(nv);
+  std::vector<int64_t> mu1_off(dense && pr->mu1_dense ? nv : 0), mu2_off(dense && pr->mu2_dense ? nv : 0);  // the real pair's
   NullPlan plan{R, spec->seed, pr->npairs, pr->off_b, pr->seq_b, ft ? nullptr : pr->cls_b, 0, 0};
+  plan.dense = dense;
   int64_t before = 0;
   for (int p = 0; p < pr->npairs; ++p) {
     const int n = pr->len_a[p], m = pr->len_b[p];
@@ -1000,6 +1040,8 @@ static int create_null(bialign_engine* eng, const bialign_params* prm, const bia
     if (pr->off_b[p] < 0) return fail(BIALIGN_E_INVALID, "pair %d: negative off_b", p);
     if (ft && m > NULL_FEAT_MAX_M)  // the feature shuffle's index array is uint16 (bialign_null.hpp)
       return fail(BIALIGN_E_UNSUPPORTED, "pair %d: B molecule of %d residues, a FEATURE-form null batch takes up to %d", p, m, NULL_FEAT_MAX_M);
+    if (dense && m > NULL_FEAT_MAX_M)  // ... and so the index shuffle's, and the permutations in HBM
+      return fail(BIALIGN_E_UNSUPPORTED, "pair %d: B molecule of %d residues, a DENSE-form null batch takes up to %d", p, m, NULL_FEAT_MAX_M);
     plan.max_m = std::max(plan.max_m, m);
     for (int r = 0; r < R; ++r) {
       const size_t v = (size_t)p * R + r;
@@ -1007,6 +1049,8 @@ static int create_null(bialign_engine* eng, const bialign_params* prm, const bia
       len_b[v] = m;
       off_a[v] = pr->off_a[p];
       off_b[v] = before * R + (int64_t)r * m;
+      if (!mu1_off.empty()) mu1_off[v] = pr->mu1_off[p];
+      if (!mu2_off.empty()) mu2_off[v] = pr->mu2_off[p];
     }
     before += m;
     plan.tot_b = std::max<int64_t>(plan.tot_b, pr->off_b[p] + m);
@@ -1018,6 +1062,8 @@ static int create_null(bialign_engine* eng, const bialign_params* prm, const bia
   vp.off_a = off_a.data();
   vp.off_b = off_b.data();
   if (ft) vp.mu2_dense = nullptr, vp.mu2_off = nullptr;  // ignored in FEATURE form
+  if (!mu1_off.empty()) vp.mu1_off = mu1_off.data();
+  if (!mu2_off.empty()) vp.mu2_off = mu2_off.data();
   bialign_params vprm = *prm;
   vprm.flags = BIALIGN_BATCH_SCORE_ONLY;
   return create_batch(eng, &vprm, sc, &vp, ft, hbm_budget, out, &plan);
@@ -1038,6 +1084,11 @@ int bialign_batch_create_null_features(bialign_engine* eng, const bialign_params
   return create_null(eng, prm, sc, pr, ft, spec, hbm_budget, out);
 }
 
+int bialign_batch_create_null_dense(bialign_engine* eng, const bialign_params* prm, const bialign_scoring* sc,
+                                    const bialign_pairs* pr, const bialign_null_spec* spec, int64_t hbm_budget, bialign_batch** out) {
+  return create_null(eng, prm, sc, pr, nullptr, spec, hbm_budget, out, true);
+}
+
 void bialign_batch_destroy(bialign_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->eng->device);
@@ -1049,7 +1100,7 @@ void bialign_batch_destroy(bialign_batch* b) {
     if (!slot) slot = eng->layer_cache.n <= eng->layer_cache2.n ? &eng->layer_cache : &eng->layer_cache2;
     if (!slot->p || b->d_layers.n > slot->n) slot->swap(b->d_layers);
   }
-  if (b->feat && b->d_tab.p && !eng->closing) {  // ... and so the table buffer (the stream is idle here or was never used)
+  if (b->tab_scratch() && b->d_tab.p && !eng->closing) {  // ... and so the table buffer (the stream is idle here or was never used)
     (void)hipStreamSynchronize(eng->stream);
     if (!eng->tab_cache.p || b->d_tab.n > eng->tab_cache.n) eng->tab_cache.swap(b->d_tab);
   }
@@ -1143,7 +1194,7 @@ static int enqueue_run(bialign_batch* b, uint32_t flags) {
     HIP_TRY(hipEventCreate(&e));
     b->evs.push_back(e);
   }
-  while (b->feat && (int)b->build_evs.size() < 2 * nchunks) {
+  while (b->tab_scratch() && (int)b->build_evs.size() < 2 * nchunks) {
     hipEvent_t e = nullptr;
     HIP_TRY(hipEventCreate(&e));
     b->build_evs.push_back(e);
@@ -1159,12 +1210,13 @@ static int enqueue_run(bialign_batch* b, uint32_t flags) {
   }
   for (int c = 0; c < nchunks; ++c) {  // stream order keeps chunk c's traceback ahead of chunk c+1's sweep
     const int first = b->chunk_begin[c], count = b->chunk_begin[c + 1] - first;
-    if (b->feat) {
+    if (b->tab_scratch()) {
       // FEATURE form: the chunk's mu2 tables, built into the table buffer ahead of the sweep (timed on its own, outside
       // fill_ms).  They stay until the next chunk's build, which stream order puts behind this chunk's tracebacks -- every
-      // lean re-sweep round included -- so no round has to build them again.
+      // lean re-sweep round included -- so no round has to build them again.  DENSE-form null batch: the chunk's
+      // replicas' tables, the real pairs' with their columns permuted, in the same slot.
       HIP_TRY(hipEventRecord(b->build_evs[2 * c], st));
-      if (int rc = launch_build_mu2(b, first, count)) return rc;
+      if (int rc = b->null_dense ? launch_permute_tables(b, first, count) : launch_build_mu2(b, first, count)) return rc;
       HIP_TRY(hipEventRecord(b->build_evs[2 * c + 1], st));
       ++b->build_launches;
     }
@@ -1208,7 +1260,7 @@ int bialign_batch_wait(bialign_batch* b) {
       HIP_TRY(hipEventElapsedTime(&t, b->evs[3 * c + 1], b->evs[3 * c + 2]));
       b->timing.fill_ms += f;
       b->timing.traceback_ms += t;
-      if (b->feat) {
+      if (b->tab_scratch()) {
         HIP_TRY(hipEventElapsedTime(&f, b->build_evs[2 * c], b->build_evs[2 * c + 1]));
         b->build_ms += f;
       }
@@ -1342,7 +1394,8 @@ int bialign_batch_dump_mu2(bialign_batch* b, int32_t pair, int32_t* out) {
   if (!b || !out) return fail(BIALIGN_E_INVALID, "NULL argument");
   if (b->null_R)
     return fail(BIALIGN_E_INVALID, "a null batch has no table of a real pair to dump: its tables are those of the replicas "
-                                   "(bialign_batch_dump_null_features shows what they are built from)");
+                                   "(bialign_batch_dump_null_features shows what they are built from, "
+                                   "bialign_batch_dump_null_tables a DENSE-form null batch's)");
   if (pair < 0 || pair >= b->npairs) return fail(BIALIGN_E_INVALID, "pair %d out of range", pair);
   if (!b->dense) return fail(BIALIGN_E_INVALID, "mu2 of this batch is in LOOKUP form: there is no table to dump");
   if (int rc = bialign_batch_wait(b)) return rc;
@@ -1365,9 +1418,9 @@ int bialign_batch_get_feature_info(const bialign_batch* b, bialign_feature_info*
   info->form = b->feat ? BIALIGN_MU2_FEATURE : (b->dense ? BIALIGN_MU2_DENSE : BIALIGN_MU2_LOOKUP);
   info->build_launches = b->build_launches;
   int64_t dense_dw = 0;  // DENSE: every pair's mu2 table is resident
-  if (b->dense && !b->feat)
+  if (b->dense && !b->tab_scratch())
     for (const PairDesc& d : b->pairs) dense_dw += (int64_t)d.n * d.m;
-  info->table_bytes = 4 * (b->feat ? b->max_chunk_tab_dwords : dense_dw);
+  info->table_bytes = 4 * (b->tab_scratch() ? b->max_chunk_tab_dwords : dense_dw);
   info->build_ms = b->build_ms;
   return BIALIGN_OK;
 }
@@ -1408,7 +1461,8 @@ int bialign_batch_get_null_info(const bialign_batch* b, bialign_null_info* info)
   if (int rc = bialign_batch_wait(const_cast<bialign_batch*>(b))) return rc;
   info->shuffle_ms = b->shuffle_ms;
   info->stats_ms = b->stats_ms;
-  info->replica_bytes = (int64_t)(b->d_seq_b.n + b->d_cls_b.n + (b->feat ? b->d_feat_b.n * sizeof(double) : 0));
+  info->replica_bytes = (int64_t)(b->d_seq_b.n + b->d_cls_b.n + (b->feat ? b->d_feat_b.n * sizeof(double) : 0) +
+                                  b->d_null_perm.n * sizeof(uint16_t));
   return BIALIGN_OK;
 }
 
@@ -1446,6 +1500,32 @@ int bialign_batch_dump_null_features(bialign_batch* b, int32_t pair, int32_t rep
   for (int f = 0; f < 3; ++f)
     HIP_TRY(hipMemcpyAsync(out[f], b->d_feat_b.p + (size_t)f * b->feat_tot_b + d.seq_b, (size_t)d.m * sizeof(double),
                            hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return BIALIGN_OK;
+}
+
+int bialign_batch_dump_null_tables(bialign_batch* b, int32_t pair, int32_t replica, int32_t* mu1_out, int32_t* mu2_out) {
+  if (!b) return fail(BIALIGN_E_INVALID, "NULL argument");
+  if (!b->null_R || !b->null_dense) return fail(BIALIGN_E_INVALID, "not a DENSE-form null batch (bialign_batch_create_null_dense)");
+  if (pair < 0 || pair >= b->null_npairs) return fail(BIALIGN_E_INVALID, "pair %d out of range", pair);
+  if (replica < 0 || replica >= b->null_R) return fail(BIALIGN_E_INVALID, "replica %d out of range", replica);
+  if (mu1_out && !b->dense1) return fail(BIALIGN_E_INVALID, "mu1_out given, but mu1 of this batch is in LOOKUP form");
+  if (mu2_out && !b->dense) return fail(BIALIGN_E_INVALID, "mu2_out given, but mu2 of this batch is in LOOKUP form");
+  if (int rc = bialign_batch_wait(b)) return rc;
+  HIP_TRY(hipSetDevice(b->eng->device));
+  hipStream_t st = b->eng->stream;
+  HIP_TRY(hipStreamWaitEvent(st, b->uploaded, 0));
+  // the replica's permutation, then its tables in their place in the chunk buffer (which may hold another chunk's by now;
+  // results of a run live elsewhere)
+  const int v = pair * b->null_R + replica;
+  const int pos = (int)(std::find(b->order.begin(), b->order.end(), v) - b->order.begin());
+  if (int rc = launch_shuffle_null(b, v, 1)) return rc;
+  if (int rc = launch_permute_tables(b, pos, 1)) return rc;
+  const PairDesc& d = b->pairs[v];
+  const size_t nm = (size_t)d.n * d.m;
+  if (mu2_out) HIP_TRY(hipMemcpyAsync(mu2_out, b->d_tab.p + d.tab_off, nm * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (mu1_out)
+    HIP_TRY(hipMemcpyAsync(mu1_out, b->d_tab.p + d.tab_off + (b->dense ? nm : 0), nm * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return BIALIGN_OK;
 }

@@ -156,6 +156,16 @@ struct bialign_batch {
   // d_seq_b from the uploaded B features kept here, three planes of d_null_seq.n doubles; d_cls_b stays zero.
   DevBuf<double> d_null_feat;
   int null_max_m = 0;                       // longest B of the batch: sizes the shuffle's index array in LDS
+  // DENSE-form null batch (bialign_batch_create_null_dense): the real pairs' tables stay resident in d_null_tab (pair p's
+  // at d_null_tab_off[p]: mu2's, then mu1's), d_null_perm holds every replica's permutation (uint16, indexed by the virtual
+  // pairs' seq_b like d_seq_b; shuffle_index_kernel fills it), and d_tab is per-chunk scratch as in FEATURE form:
+  // permute_tables_kernel writes each chunk's tables there ahead of its sweep; tab_dwords, max_chunk_tab_dwords, build_evs,
+  // build_ms and build_launches above serve it likewise.
+  bool null_dense = false;
+  DevBuf<int32_t> d_null_tab;
+  DevBuf<int64_t> d_null_tab_off;
+  DevBuf<uint16_t> d_null_perm;
+  bool tab_scratch() const { return feat || null_dense; }  // d_tab is per-chunk scratch inside the chunk plan
   DevBuf<int32_t> d_null_obs;               // observed scores of the last bialign_batch_get_null_stats
   DevBuf<bialign_null_stats> d_null_stats;  // ... and its result
   hipEvent_t null_evs[4] = {nullptr, nullptr, nullptr, nullptr};  // around the shuffle launch of a run, around the reduction
@@ -244,9 +254,12 @@ int launch_build_mu2(bialign_batch* b, int first, int count);
 
 // Null batch (bialign_null.hip): write the replicas of virtual pairs first .. first + count into the replica buffers, and
 // reduce every real pair's replica scores (d_scores) into d_null_stats; both on the engine's stream.
-// (FEATURE-form null batches: codes and feature planes; its index array in LDS is uint16, so len_b <= NULL_FEAT_MAX_M)
+// (FEATURE- and DENSE-form null batches: the shuffle's index array in LDS is uint16, so len_b <= NULL_FEAT_MAX_M)
 constexpr int NULL_FEAT_MAX_M = 65535;
 int launch_shuffle_null(bialign_batch* b, int first, int count);
+// DENSE-form null batch: permute the real tables' columns into the chunk's table buffer for virtual pairs
+// order[first .. first+count), on the engine's stream; launch_shuffle_null must have written their permutations.
+int launch_permute_tables(bialign_batch* b, int first, int count);
 int launch_null_stats(bialign_batch* b, const int32_t* d_observed);
 
 // ---- launching: every kernel of the library starts through launch() or launch_team()

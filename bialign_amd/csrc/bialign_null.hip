@@ -29,9 +29,54 @@ static int launch_shuffle_features(bialign_batch* b, int first, int count) {
   return launch(shuffle_features_kernel, dim3((unsigned)std::min(count, NULL_FEAT_MAX_GRID)), dim3(64), lds, b->eng->stream, a);
 }
 
+// DENSE-form null batch: one wave per virtual pair, the same index array; the finished permutations go to d_null_perm
+static int launch_shuffle_index(bialign_batch* b, int first, int count) {
+  if (b->null_max_m < 1 || b->null_max_m > NULL_FEAT_MAX_M)  // (bialign_batch_create_null_dense refuses longer ones)
+    return fail(BIALIGN_E_UNSUPPORTED, "index shuffle: longest B molecule %d outside 1..%d", b->null_max_m, NULL_FEAT_MAX_M);
+  ShuffleIndexArgs a{};
+  a.pairs = b->d_pairs.p;
+  a.src_off = b->d_null_off.p;
+  a.src_seq = b->dense1 ? nullptr : b->d_null_seq.p;
+  a.src_cls = b->dense ? nullptr : b->d_null_cls.p;
+  a.dst_seq = b->d_seq_b.p;
+  a.dst_cls = b->d_cls_b.p;
+  a.dst_perm = b->d_null_perm.p;
+  a.first = first;
+  a.count = count;
+  a.replicas = b->null_R;
+  a.seed = b->null_seed;
+  const size_t lds = ((size_t)b->null_max_m * sizeof(uint16_t) + 15) / 16 * 16;
+  return launch(shuffle_index_kernel, dim3((unsigned)std::min(count, NULL_FEAT_MAX_GRID)), dim3(64), lds, b->eng->stream, a);
+}
+
+int launch_permute_tables(bialign_batch* b, int first, int count) {
+  if (!b->null_dense || count < 1) return BIALIGN_OK;
+  PermuteArgs a{};
+  a.pairs = b->d_pairs.p;
+  a.order = b->d_order.p + first;
+  a.perm = b->d_null_perm.p;
+  a.src = b->d_null_tab.p;
+  a.src_off = b->d_null_tab_off.p;
+  a.tab = b->d_tab.p;
+  a.replicas = b->null_R;
+  a.forms = (b->dense ? 1 : 0) + (b->dense1 ? 1 : 0);
+  int64_t groups = 1;  // workgroups per pair: one per tile of the launch's tallest stack of tables
+  size_t lds = 0;      // ... with the launch's largest LDS tile
+  for (int t = first; t < first + count; ++t) {
+    const PairDesc& d = b->pairs[b->order[t]];
+    const int32_t T = permute_tile_rows(d.m);
+    const int64_t rows = (int64_t)d.n * a.forms, tr = T ? T : PERM_ROWS;
+    groups = std::max(groups, (rows + tr - 1) / tr);
+    lds = std::max(lds, (size_t)std::min<int64_t>(T, rows) * d.m * sizeof(int32_t));
+  }
+  return launch(permute_tables_kernel, dim3(count, (unsigned)std::min<int64_t>(groups, PERM_MAX_GRID_Y)), dim3(64 * PERM_WAVES), lds,
+                b->eng->stream, a);
+}
+
 int launch_shuffle_null(bialign_batch* b, int first, int count) {
   if (!b->null_R || count < 1) return BIALIGN_OK;
   if (b->feat) return launch_shuffle_features(b, first, count);
+  if (b->null_dense) return launch_shuffle_index(b, first, count);
   ShuffleArgs a{};
   a.pairs = b->d_pairs.p;
   a.src_off = b->d_null_off.p;

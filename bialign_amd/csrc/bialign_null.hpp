@@ -6,7 +6,10 @@
 // shuffle_codes_kernel fills from the one uploaded copy of B.  null_stats_kernel then reduces every real pair's R
 // scores to exact integers; no floating point on the device.  A FEATURE-form null batch
 // (bialign_batch_create_null_features) has replica planes of doubles beside the replica codes, which
-// shuffle_features_kernel fills (below); build_mu2_kernel reads them through the same seq_b.
+// shuffle_features_kernel fills (below); build_mu2_kernel reads them through the same seq_b.  A DENSE-form null batch
+// (bialign_batch_create_null_dense) keeps every replica's finished permutation in an index array beside the replica
+// codes (shuffle_index_kernel), through which permute_tables_kernel gathers the columns of the real pairs' tables into
+// each chunk's table scratch (below).
 //
 // The permutation is the one include/bialign.h states (normative there; bialign_amd/significance.py mirrors it).
 //
@@ -199,6 +202,126 @@ __global__ __launch_bounds__(64) void shuffle_features_kernel(ShuffleFeatArgs A)
       dp[x] = sp[s];
     }
     __syncthreads();  // (the next virtual pair of this workgroup overwrites the array)
+  }
+}
+
+// ---- DENSE-form null batches (bialign_batch_create_null_dense): a residue of B carries a COLUMN of the pair's n x m
+// table(s), so replica r's tables are the real pair's with their columns gathered through perm.  Two stages:
+//
+// shuffle_index_kernel, once per run ahead of the first sweep: the chain of shuffle_features_kernel, one wave per
+// virtual pair, and the finished perm stored to an HBM index array (uint16, laid out like the replica codes: the virtual
+// pair's at its seq_b), together with the gathered codes of whichever of mu1 / mu2 is in LOOKUP form (a nullptr source:
+// that form is dense, the replicas' codes of that kind stay zero).
+//
+// permute_tables_kernel, once per chunk in the table builder's slot: a pure gather, no chain.  The real pair's tables
+// lie end to end (mu2's, then mu1's: the order the consumers expect them in), and so do the replica's in the chunk's
+// scratch -- forms * n rows of m values, all gathered through the same perm.  Grid (virtual pairs of the chunk in
+// launch order, tile groups).  A workgroup of PERM_WAVES waves takes a tile of T rows: it loads them coalesced into LDS
+// (T * m dwords, contiguous in the source), then lanes run along x -- one coalesced 2-byte load of perm[x] per column
+// tile of 64 --, the waves take every PERM_WAVES-th row of the tile, read LDS at perm[x] and store 256-byte row
+// segments: HBM sees each source byte once and each destination byte once.  T = permute_tile_rows(m): PERM_ROWS rows,
+// fewer where they exceed the 64 KiB tile; a row that alone exceeds it (m > PERM_LDS_DW) is gathered straight from
+// global memory.  Vector loads and stores, 64-bit offsets, no atomics.  perm[x] < m: the index kernel ran first.
+struct ShuffleIndexArgs {
+  const PairDesc* pairs;    // the VIRTUAL pairs: m, and seq_b = start of the replica's slice in dst_*
+  const int64_t* src_off;   // [real pairs] start of pair p's B in src_seq / src_cls
+  const uint8_t *src_seq, *src_cls;  // the uploaded B codes; nullptr: mu1 (seq) / mu2 (cls) is dense
+  uint8_t *dst_seq, *dst_cls;        // the replica buffers
+  uint16_t* dst_perm;                // the replicas' permutations
+  int32_t first, count;     // virtual pairs first .. first + count
+  int32_t replicas;
+  uint32_t seed;
+};
+
+__global__ __launch_bounds__(64) void shuffle_index_kernel(ShuffleIndexArgs A) {
+  extern __shared__ uint16_t null_perm[];  // [longest m of the launch]
+  const int32_t lane = (int32_t)threadIdx.x;
+  for (int64_t w = blockIdx.x; w < A.count; w += gridDim.x) {
+    const int32_t v = A.first + (int32_t)w;
+    const int32_t p = v / A.replicas, r = v - p * A.replicas;
+    const PairDesc& pd = A.pairs[v];
+    const int32_t m = __builtin_amdgcn_readfirstlane(pd.m);
+    const int64_t src = A.src_off[p], dst = pd.seq_b;
+    const uint32_t h = null_hash(A.seed, (uint32_t)p, (uint32_t)r);
+    // (the chain of shuffle_features_kernel, restated: shared through a device function, that kernel's code moved)
+    for (int32_t x = lane; x < m; x += 64) null_perm[x] = (uint16_t)x;
+    __syncthreads();
+    for (int32_t tb = (m - 1) & ~63; tb >= 0; tb -= 64) {
+      const uint32_t d = null_draw(h, (uint32_t)(tb + lane));  // lane k holds draw(tb + k) <= tb + k
+      const int32_t khi = m - 1 - tb < 63 ? m - 1 - tb : 63, klo = tb == 0 ? 1 : 0;
+      for (int32_t k = khi; k >= klo; --k) {
+        const int32_t t = tb + k;                                    // m - 1 down to 1
+        const int32_t j = __builtin_amdgcn_readlane((int32_t)d, k);  // <= t < m: inside the array
+        const uint16_t pt = null_perm[t], pj = null_perm[j];
+        if (lane == 0) {
+          null_perm[t] = pj;
+          null_perm[j] = pt;
+        }
+      }
+    }
+    __syncthreads();
+    uint16_t* __restrict__ const dp = A.dst_perm + dst;
+    for (int32_t x = lane; x < m; x += 64) {
+      const int32_t s = null_perm[x];  // < m
+      dp[x] = (uint16_t)s;
+      if (A.src_seq) A.dst_seq[dst + x] = A.src_seq[src + s];
+      if (A.src_cls) A.dst_cls[dst + x] = A.src_cls[src + s];
+    }
+    __syncthreads();  // (the next virtual pair of this workgroup overwrites the array)
+  }
+}
+
+constexpr int PERM_WAVES = 4;           // waves per workgroup
+constexpr int PERM_ROWS = 16;           // rows per tile at most
+constexpr int PERM_LDS_DW = 16384;      // dwords of the LDS tile: 64 KiB
+constexpr int PERM_MAX_GRID_Y = 4096;   // tile groups per pair in the grid; taller tables loop
+
+// rows of an LDS tile for tables of m columns; 0: one row exceeds the tile, gather from global memory
+__host__ __device__ inline int32_t permute_tile_rows(int32_t m) {
+  return m > PERM_LDS_DW ? 0 : (PERM_LDS_DW / m < PERM_ROWS ? PERM_LDS_DW / m : PERM_ROWS);
+}
+
+struct PermuteArgs {
+  const PairDesc* pairs;    // the VIRTUAL pairs: n, m, tab_off (chunk-relative), seq_b = start of the replica's perm
+  const int32_t* order;     // launch order of the pairs to permute (block x -> virtual pair id)
+  const uint16_t* perm;     // what shuffle_index_kernel wrote
+  const int32_t* src;       // the real pairs' resident tables
+  const int64_t* src_off;   // [real pairs] start of pair p's tables in src
+  int32_t* tab;             // the chunk's table buffer
+  int32_t replicas;
+  int32_t forms;            // dense forms of the batch, 1 or 2: tables per pair
+};
+
+__global__ __launch_bounds__(64 * PERM_WAVES) void permute_tables_kernel(PermuteArgs A) {
+  extern __shared__ int32_t perm_tile[];  // [T * m of the launch's widest LDS tile]
+  const int32_t pid = A.order[blockIdx.x];
+  const PairDesc& pd = A.pairs[pid];
+  const int32_t m = pd.m;
+  const int64_t rows = (int64_t)pd.n * A.forms;
+  const int32_t lane = (int32_t)(threadIdx.x & 63);
+  const int32_t wave = __builtin_amdgcn_readfirstlane((int32_t)(threadIdx.x >> 6));
+  const int32_t* __restrict__ const src = A.src + A.src_off[pid / A.replicas];
+  int32_t* __restrict__ const dst = A.tab + pd.tab_off;
+  const uint16_t* __restrict__ const perm = A.perm + pd.seq_b;
+  const int32_t T = permute_tile_rows(m);
+  const int32_t TR = T ? T : PERM_ROWS;
+  const int64_t ntiles = (rows + TR - 1) / TR;
+  for (int64_t t = blockIdx.y; t < ntiles; t += gridDim.y) {  // (uniform over the workgroup: the barriers are met by all)
+    const int64_t r0 = t * TR;
+    const int32_t nr = rows - r0 < TR ? (int32_t)(rows - r0) : TR;
+    const int32_t* const srow = src + r0 * m;
+    int32_t* const drow = dst + r0 * m;
+    if (T) {
+      const int32_t cnt = nr * m;  // <= PERM_LDS_DW
+      for (int32_t i = (int32_t)threadIdx.x; i < cnt; i += 64 * PERM_WAVES) perm_tile[i] = srow[i];
+      __syncthreads();
+    }
+    for (int32_t x = lane; x < m; x += 64) {
+      const int32_t s = perm[x];  // < m
+      for (int32_t r = wave; r < nr; r += PERM_WAVES)
+        drow[(int64_t)r * m + x] = T ? perm_tile[r * m + s] : srow[(int64_t)r * m + s];
+    }
+    if (T) __syncthreads();  // (the next tile overwrites the array)
   }
 }
 

@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import lib, check
-from .significance import check_null
+from .significance import check_dense_tables, check_null
 
 STATES = [(0, 1, 0, 1), (0, 1, 1, 0), (0, 1, 1, 1), (1, 0, 0, 1), (1, 0, 1, 0),
           (1, 0, 1, 1), (1, 1, 0, 1), (1, 1, 1, 0), (1, 1, 1, 1)]  # pyx:61-65
@@ -96,11 +96,24 @@ class Batch:
     batch.  Results come from ``null_scores()`` / ``null_stats()``; ``scores()`` raises.  mu1 in LOOKUP form; mu2 in
     LOOKUP form or, together with ``mu2_features``, in FEATURE form (bialign_batch_create_null_features;
     ``significance.null_feature_batch``): a residue's three numbers then move with its letter.
+    ``null_dense``: ``(replicas, seed)``, a null batch with ``mu1_dense`` and / or ``mu2_dense``
+    (bialign_batch_create_null_dense; ``significance.null_dense_batch``): a residue of B carries its column of every
+    table, and the GPU permutes the columns of the one uploaded copy of the tables per replica, chunk by chunk.  The other
+    of mu1 / mu2 may stay in LOOKUP form.  Excludes ``null``, ``mu2_features``, ``lean_trace`` and ``level_trace``; the
+    tables must be of an integer dtype.  Results as for ``null``; ``null_tables()`` shows a replica's tables.
     """
 
     def __init__(self, engine, mols_a, mols_b, s1, s2, gap_opening_cost, gap_cost, shift_cost,
                  max_shift, hbm_budget_bytes=0, recurrence=0, mu2_dense=None, score_only=False,
-                 lean_trace=False, mu1_dense=None, mu2_features=None, level_trace=False, null=None):
+                 lean_trace=False, mu1_dense=None, mu2_features=None, level_trace=False, null=None, null_dense=None):
+        if null_dense is not None:
+            if mu1_dense is None and mu2_dense is None:
+                raise ValueError("null_dense needs mu1_dense and / or mu2_dense (a LOOKUP null batch is null=)")
+            if null is not None or mu2_features is not None:
+                raise ValueError("null_dense excludes null and mu2_features")
+            if lean_trace or level_trace:
+                raise ValueError("a null batch is score-only: lean_trace / level_trace do not apply")
+            replicas, seed = check_null(null_dense)
         if null is not None:
             replicas, seed = check_null(null)
             if mu2_dense is not None or mu1_dense is not None:
@@ -144,6 +157,10 @@ class Batch:
         if cls_a.size and (cls_a.max() >= s2.shape[0] or cls_b.max() >= s2.shape[0]):
             raise ValueError("structure class outside the S2 table")
         feat = None if mu2_features is None else self._features(mu2_features, flat, len(seq_a), len(seq_b), off_a, off_b)
+        if null_dense is not None:  # (stricter than a plain batch: no silent cast of floats or of values beyond int32)
+            for tables, name in ((mu1_dense, "mu1_dense"), (mu2_dense, "mu2_dense")):
+                if tables is not None:
+                    check_dense_tables(tables, self.len_a, self.len_b, name)
         mu2_flat, mu2_off = self._dense_tables(mu2_dense, "mu2_dense")
         mu1_flat, mu1_off = self._dense_tables(mu1_dense, "mu1_dense")
         mu2_ptr = mu2_off_ptr = mu1_ptr = mu1_off_ptr = None
@@ -163,7 +180,16 @@ class Batch:
                         mu1_ptr, mu1_off_ptr)
         self._h = ctypes.c_void_p()
         self.replicas = None
-        if null is not None:
+        self._null_forms = None
+        if null_dense is not None:
+            if self.npairs * replicas > 2 ** 31 - 1:
+                raise ValueError("npairs * replicas exceeds INT32_MAX")
+            self.replicas = replicas
+            self._null_forms = (mu1_flat is not None, mu2_flat is not None)
+            spec = _lib.NullSpec(replicas, seed)
+            check(lib.bialign_batch_create_null_dense(engine._h, ctypes.byref(prm), ctypes.byref(sc), ctypes.byref(pr),
+                                                      ctypes.byref(spec), int(hbm_budget_bytes), ctypes.byref(self._h)))
+        elif null is not None:
             if self.npairs * replicas > 2 ** 31 - 1:
                 raise ValueError("npairs * replicas exceeds INT32_MAX")
             self.replicas = replicas
@@ -292,9 +318,21 @@ class Batch:
                                                    *(_ptr(x, ctypes.c_double) for x in out)))
         return out
 
+    def null_tables(self, pair, replica):
+        """DENSE-form null batch, test hook: ``(mu1, mu2)`` of one replica of one pair as the sweep reads them, int32
+        arrays of shape (len A, len B); None for a form the batch holds in LOOKUP form."""
+        self._need_null()
+        if self._null_forms is None:
+            raise ValueError("not a DENSE-form null batch (create it with null_dense=(replicas, seed))")
+        shape = (int(self.len_a[pair]), int(self.len_b[pair]))
+        out = [np.empty(shape, dtype=np.int32) if have else None for have in self._null_forms]
+        check(lib.bialign_batch_dump_null_tables(self._h, int(pair), int(replica),
+                                                 *(None if x is None else _ptr(x, ctypes.c_int32) for x in out)))
+        return tuple(out)
+
     def _need_null(self):
         if self.replicas is None:
-            raise ValueError("not a null batch (create it with null=(replicas, seed))")
+            raise ValueError("not a null batch (create it with null=(replicas, seed) or null_dense=(replicas, seed))")
 
     def dump_mu2(self, pair):
         """The (len A, len B) int32 mu2 table of one pair as the sweep reads it (DENSE or FEATURE form)."""

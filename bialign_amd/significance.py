@@ -8,9 +8,11 @@ every pair's R scores to exact integer sums, and ``zscores`` forms mean, standar
 
 RNA molecules with real-valued structure features (``batch.make_feature_batch``) have the same in FEATURE form:
 ``null_feature_batch`` / ``zscores_features`` (bialign_batch_create_null_features), a residue's three numbers moving
-with its letter.
+with its letter.  Pairs scored through dense tables -- a PSSM or profile as ``mu1_dense``, structure scores computed
+outside as ``mu2_dense`` -- have it in DENSE form: ``null_dense_batch`` / ``zscores_dense``
+(bialign_batch_create_null_dense), a residue of B carrying its column of every table.
 
-``permutation``, ``shuffle_b`` and ``shuffle_features`` restate the header's permutation in plain Python: the
+``permutation``, ``shuffle_b``, ``shuffle_features`` and ``shuffle_tables`` restate the header's permutation in plain Python: the
 documented way to reproduce any replica on the host.  Nothing in this module loads the HIP library before its
 arguments are checked.
 """
@@ -79,6 +81,49 @@ def shuffle_features(seq, feats, seed, pair, replica):
         raise ValueError("every feature must hold one number per residue")
     perm = permutation(seed, pair, replica, len(seq))
     return "".join(seq[x] for x in perm.tolist()), tuple(np.ascontiguousarray(f[perm]) for f in planes)
+
+
+def shuffle_tables(table, seed, pair, replica):
+    """A pair's (len A, len B) table -- dense mu1 or mu2 -- as replica ``replica`` of pair ``pair`` has it in a
+    DENSE-form null batch: ``table[:, permutation(seed, pair, replica, len B)]``, the columns moved with B's residues, the
+    values untouched."""
+    table = np.asarray(table)
+    if table.ndim != 2 or table.shape[1] < 1:
+        raise ValueError("table must have shape (len A, len B)")
+    return np.ascontiguousarray(table[:, permutation(seed, pair, replica, table.shape[1])])
+
+
+def check_dense_tables(tables, lens_a, lens_b, name):
+    """One integer table of shape (len A, len B) per pair, every value an int32 -- refused otherwise, where
+    ``engine.Batch`` alone would cast."""
+    if len(tables) != len(lens_a):
+        raise ValueError(f"{name} needs one table per pair")
+    for p, tab in enumerate(tables):
+        try:
+            tab = np.asarray(tab)
+        except ValueError:
+            raise ValueError(f"{name}[{p}] is ragged: it must have shape (len A, len B)") from None
+        if tab.shape != (int(lens_a[p]), int(lens_b[p])):
+            raise ValueError(f"{name}[{p}] must have shape (len A, len B) = ({int(lens_a[p])}, {int(lens_b[p])}), "
+                             f"got {tab.shape}")
+        if tab.dtype == np.bool_ or not np.issubdtype(tab.dtype, np.integer):
+            raise ValueError(f"{name}[{p}] must be of an integer dtype, got {tab.dtype}")
+        if tab.size and (int(tab.min()) < -2 ** 31 or int(tab.max()) > 2 ** 31 - 1):
+            raise ValueError(f"{name}[{p}] holds values outside int32")
+
+
+def check_dense_args(pairs, null, mu1_dense, mu2_dense):
+    """The arguments of a DENSE-form null batch, checked as ``engine.Batch`` and the C ABI check them -- here, so that
+    nothing is loaded for a call that cannot succeed.  -> (pairs, replicas, seed)."""
+    replicas, seed = check_null(null)
+    pairs, replicas, seed = _check_pairs(pairs, replicas, seed)
+    if mu1_dense is None and mu2_dense is None:
+        raise ValueError("a DENSE-form null batch needs mu1_dense and / or mu2_dense (the LOOKUP form is null_batch / zscores)")
+    lens_a, lens_b = [len(p[0]) for p in pairs], [len(p[1]) for p in pairs]
+    for tables, name in ((mu1_dense, "mu1_dense"), (mu2_dense, "mu2_dense")):
+        if tables is not None:
+            check_dense_tables(tables, lens_a, lens_b, name)
+    return pairs, replicas, seed
 
 
 def check_null(null):
@@ -214,6 +259,48 @@ def zscores_features(molecules, pair_index, params, replicas=100, seed=0, observ
             b.close()
     nb = null_feature_batch(molecules, pair_index, params, replicas, seed=seed, engine=engine,
                             hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence)
+    try:
+        nb.run()
+        stats = nb.null_stats(observed)
+    finally:
+        nb.close()
+    return zscores_from_stats(observed, stats)
+
+
+def null_dense_batch(pairs, params, replicas, seed=0, mu1_dense=None, mu2_dense=None, engine=None, hbm_budget_bytes=0,
+                     recurrence=0):
+    """A DENSE-form null batch: ``pairs`` and their tables as ``batch.make_batch`` takes them (one integer table of shape
+    (len A, len B) per pair in ``mu1_dense`` and / or ``mu2_dense``), every pair against ``replicas`` shuffles of its B --
+    the tables' columns, and the codes of a form left in LOOKUP form, permuted on the GPU from the one uploaded copy.
+    -> ``engine.Batch``; ``run()`` it, then ``null_scores()`` / ``null_stats()``."""
+    pairs, replicas, seed = check_dense_args(pairs, (replicas, seed), mu1_dense, mu2_dense)
+    from .batch import make_batch
+    return make_batch(pairs, params, engine=engine, hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence,
+                      score_only=True, mu1_dense=mu1_dense, mu2_dense=mu2_dense, null_dense=(replicas, seed))
+
+
+def zscores_dense(pairs, params, replicas=100, seed=0, mu1_dense=None, mu2_dense=None, observed=None, engine=None,
+                  hbm_budget_bytes=0, recurrence=0):
+    """``zscores`` for pairs scored through dense tables (a PSSM as ``mu1_dense``, structure scores as ``mu2_dense``):
+    z-scores of the pairs' optimal scores against ``replicas`` shuffles of each pair's B (``zscores_from_stats``).
+    ``observed``: the pairs' real scores if the caller has them; else ``make_batch(score_only=True)`` with the same
+    tables computes them first."""
+    pairs, replicas, seed = check_dense_args(pairs, (replicas, seed), mu1_dense, mu2_dense)
+    if observed is not None:
+        observed = np.ascontiguousarray(observed, dtype=np.int32)
+        if observed.shape != (len(pairs),):
+            raise ValueError("observed needs one score per pair")
+    if observed is None:
+        from .batch import make_batch
+        b = make_batch(pairs, params, engine=engine, hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence,
+                       score_only=True, mu1_dense=mu1_dense, mu2_dense=mu2_dense)
+        try:
+            b.run()
+            observed = b.scores().copy()
+        finally:
+            b.close()
+    nb = null_dense_batch(pairs, params, replicas, seed=seed, mu1_dense=mu1_dense, mu2_dense=mu2_dense, engine=engine,
+                          hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence)
     try:
         nb.run()
         stats = nb.null_stats(observed)

@@ -170,6 +170,9 @@ typedef struct bialign_feature_info {
   int64_t table_bytes;    /* FEATURE: mu2 table bytes of the largest chunk (the scratch buffer's use, inside the HBM
                              budget); DENSE: bytes of all resident tables; LOOKUP: 0 */
   double build_ms;        /* HIP-event time of the builder launches of the last run; not part of fill_ms */
+  /* A DENSE-form null batch (bialign_batch_create_null_dense): form is DENSE when mu2 is dense, else LOOKUP;
+     build_launches counts the launches of the kernel that permutes the tables' columns, one per chunk, build_ms is their
+     time; table_bytes is the largest chunk's scratch, the replicas' permuted tables of every dense form. */
 } bialign_feature_info;
 
 /* ---- Shuffled-null significance (new in ABI 10 as added symbols: no existing struct or function changes).
@@ -189,13 +192,22 @@ typedef struct bialign_feature_info {
  * molecule through off_b get different shuffles because p differs.  bialign_amd/significance.py restates it in Python.
  *
  * bialign_batch_create_null takes the LOOKUP form only: with mu1_dense or mu2_dense set it fails with
- * BIALIGN_E_UNSUPPORTED (a table's columns would have to be permuted per replica).
+ * BIALIGN_E_UNSUPPORTED (a table's columns would have to be permuted per replica: bialign_batch_create_null_dense does).
  * FEATURE form of mu2 (RNA with real-valued structure features, bialign_features): bialign_batch_create_null_features.
  * Replica r of pair p's B then has, with the same perm,
  *     seq'[x] = seq_b[perm[x]],  up'[x] = up_b[perm[x]],  down'[x] = down_b[perm[x]],  unp'[x] = unp_b[perm[x]]
  * -- a residue's letter and its three numbers move together, and the doubles are moved, never recomputed: each is bit
  * for bit the source's.  This is the same null model as the LOOKUP RNA null, in which a position's structure annotation
- * (there its class, here its three numbers) travels with its letter. */
+ * (there its class, here its three numbers) travels with its letter.
+ *
+ * DENSE form of mu1 and / or mu2 (a PSSM or profile as mu1_dense, structure scores computed outside as mu2_dense):
+ * bialign_batch_create_null_dense.  A residue of B carries everything indexed by it -- here a column of each table.
+ * Replica r of pair p uses THE PERMUTATION above, unchanged: perm depends on (seed, p, r, m) only and is the same perm
+ * the LOOKUP and FEATURE nulls use for the same (seed, p, r, m).  With it
+ *     mu1'[(i-1)*m + x] = mu1[(i-1)*m + perm[x]]      (dense mu1)
+ *     mu2'[(k-1)*m + x] = mu2[(k-1)*m + perm[x]]      (dense mu2)
+ *     seq'[x] = seq_b[perm[x]],  cls'[x] = cls_b[perm[x]]   (whichever of mu1 / mu2 is in LOOKUP form)
+ * Values are moved, never recomputed.  A is never shuffled; m = 1 gives the identity. */
 typedef struct bialign_null_spec {
   int32_t replicas; /* R, 1..65535 */
   uint32_t seed;
@@ -215,7 +227,8 @@ typedef struct bialign_null_info {
   double stats_ms;       /* ... of the last bialign_batch_get_null_stats reduction */
   int64_t replica_bytes; /* the replicas' B codes in HBM, both kinds: 2 * R * (sum of len_b); outside hbm_budget_bytes.
                             A FEATURE-form null batch adds the replicas' three planes of doubles: what was allocated
-                            is codes plus planes, 26 * R * (sum of len_b) */
+                            is codes plus planes, 26 * R * (sum of len_b).  A DENSE-form null batch adds the replicas'
+                            permutations, 16 bits per residue: codes plus index arrays, 4 * R * (sum of len_b) */
 } bialign_null_info;
 
 typedef struct bialign_batch_info {
@@ -378,6 +391,34 @@ int bialign_batch_create_null_features(bialign_engine* eng, const bialign_params
  * shuffle kernel is run for that replica).  Not a FEATURE-form null batch: BIALIGN_E_INVALID. */
 int bialign_batch_dump_null_features(bialign_batch* b, int32_t pair, int32_t replica, double* up, double* down,
                                      double* unp);
+
+/* A null batch with mu1 and / or mu2 in DENSE form (new in ABI 10 as added symbols: no existing struct or function
+ * changes).  The null model is stated with THE PERMUTATION above: every replica's tables are the real pair's with their
+ * columns permuted, on the GPU -- nothing of size R * n * m is made or uploaded by the host.  At least one of
+ * pairs->mu1_dense / mu2_dense must be set (neither: BIALIGN_E_INVALID -- that batch is bialign_batch_create_null's); a
+ * table without its offsets (mu1_off / mu2_off): BIALIGN_E_INVALID.  The other of mu1 / mu2 may be in LOOKUP form; its
+ * codes (seq_a / seq_b for mu1, cls_a / cls_b for mu2) are then required as in bialign_batch_create_null, the codes of a
+ * dense form are ignored (may be NULL).  SCORE_ONLY is forced (LEAN_TRACE / LEVEL_TRACE: BIALIGN_E_INVALID); spec,
+ * replicas and npairs * replicas are checked as in bialign_batch_create_null.  The one-layer recurrence beyond
+ * BIALIGN_MAX_SHIFT_TILED, or a B molecule of more than 65535 residues (the permutations are kept 16 bits wide):
+ * BIALIGN_E_UNSUPPORTED.  The range checks (the int32 safety window from the tables' largest magnitude, then replicas *
+ * bound^2 within int64: BIALIGN_E_RANGE) are taken on the real tables, once: a column permutation leaves a table's
+ * maximum where it is.  Dense mu1 together with FEATURE mu2 in a null batch does not exist.
+ * Memory: the real pairs' tables stay resident, uploaded once, 4 * (sum of n * m) bytes per dense form; like the replicas'
+ * codes and permutations (bialign_null_info.replica_bytes) they are input data outside hbm_budget_bytes, and subtracted
+ * from the free memory a budget of 0 is taken from.  Every replica's permuted tables are per-chunk scratch inside the
+ * chunk plan (4 * n * m bytes per dense form, mu2's table first, then mu1's); one replica's tables plus layers beyond the
+ * budget: BIALIGN_E_NOMEM.
+ * get_null_scores / get_null_stats / get_null_info / dump_null_codes (the codes of a dense form: zeros) work as for any
+ * null batch, get_feature_info as bialign_feature_info says; get_scores, get_traces, dump_layers and dump_mu2 refuse as
+ * for null batches. */
+int bialign_batch_create_null_dense(bialign_engine* eng, const bialign_params* params, const bialign_scoring* scoring,
+                                    const bialign_pairs* pairs, const bialign_null_spec* spec, int64_t hbm_budget_bytes,
+                                    bialign_batch** out);
+/* Test hook: the tables of one replica of one pair as the sweep reads them, out[(i-1)*m + x], n * m int32 each (the
+ * permutation and the tables are made anew for that replica).  An out pointer may be NULL -- and must be for a form the
+ * batch holds in LOOKUP form.  Not a DENSE-form null batch: BIALIGN_E_INVALID. */
+int bialign_batch_dump_null_tables(bialign_batch* b, int32_t pair, int32_t replica, int32_t* mu1_out, int32_t* mu2_out);
 
 #ifdef __cplusplus
 }
