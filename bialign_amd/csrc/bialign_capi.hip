@@ -392,20 +392,15 @@ int plan_chunks(bialign_batch* b, const std::vector<int64_t>& pair_dwords, int64
   b->max_chunk_tab_dwords = 0;
   int64_t total_dw = 0;
   for (int p = 0; p < npairs; ++p) {
-    if (pair_dwords[p] + tab_of(p) > budget_dw && b->null_dense)
-      return fail(BIALIGN_E_NOMEM, "pair %d: one replica needs %lld bytes of layers and %lld of permuted tables, budget is %lld",
-                  p / b->null_R, (long long)pair_dwords[p] * 4, (long long)tab_of(p) * 4, (long long)budget_dw * 4);
-    if (pair_dwords[p] + tab_of(p) > budget_dw && b->null_R && feat)
-      return fail(BIALIGN_E_NOMEM, "pair %d: one replica needs %lld bytes of layers and %lld of mu2 table, budget is %lld",
-                  p / b->null_R, (long long)pair_dwords[p] * 4, (long long)tab_of(p) * 4, (long long)budget_dw * 4);
-    if (pair_dwords[p] + tab_of(p) > budget_dw && b->null_R)
-      return fail(BIALIGN_E_NOMEM, "pair %d: one replica needs %lld bytes of layers, budget is %lld", p / b->null_R,
-                  (long long)pair_dwords[p] * 4, (long long)budget_dw * 4);
-    if (pair_dwords[p] + tab_of(p) > budget_dw)
-      return feat ? fail(BIALIGN_E_NOMEM, "pair %d needs %lld bytes of layers and %lld of mu2 table, budget is %lld", p,
-                         (long long)pair_dwords[p] * 4, (long long)tab_of(p) * 4, (long long)budget_dw * 4)
-                  : fail(BIALIGN_E_NOMEM, "pair %d needs %lld bytes of layers, budget is %lld", p,
-                         (long long)pair_dwords[p] * 4, (long long)budget_dw * 4);
+    if (pair_dwords[p] + tab_of(p) > budget_dw) {
+      // who asks (a real pair, or a replica of real pair p / R), and for what beside its layers
+      const char* const who = b->null_R ? ": one replica" : "";
+      const char* const tabs = b->null_dense ? "permuted tables" : "mu2 table";
+      const long long lay = (long long)pair_dwords[p] * 4, tab = (long long)tab_of(p) * 4, bud = (long long)budget_dw * 4;
+      const int shown = b->null_R ? p / b->null_R : p;
+      return feat ? fail(BIALIGN_E_NOMEM, "pair %d%s needs %lld bytes of layers and %lld of %s, budget is %lld", shown, who, lay, tab, tabs, bud)
+                  : fail(BIALIGN_E_NOMEM, "pair %d%s needs %lld bytes of layers, budget is %lld", shown, who, lay, bud);
+    }
     total_dw += pair_dwords[p] + tab_of(p);
   }
   const int64_t want_chunks = (total_dw + budget_dw - 1) / budget_dw;
@@ -1038,10 +1033,9 @@ static int create_null(bialign_engine* eng, const bialign_params* prm, const bia
     const int n = pr->len_a[p], m = pr->len_b[p];
     if (n < 1 || m < 1) return fail(BIALIGN_E_INVALID, "pair %d: empty molecule (n=%d, m=%d)", p, n, m);
     if (pr->off_b[p] < 0) return fail(BIALIGN_E_INVALID, "pair %d: negative off_b", p);
-    if (ft && m > NULL_FEAT_MAX_M)  // the feature shuffle's index array is uint16 (bialign_null.hpp)
-      return fail(BIALIGN_E_UNSUPPORTED, "pair %d: B molecule of %d residues, a FEATURE-form null batch takes up to %d", p, m, NULL_FEAT_MAX_M);
-    if (dense && m > NULL_FEAT_MAX_M)  // ... and so the index shuffle's, and the permutations in HBM
-      return fail(BIALIGN_E_UNSUPPORTED, "pair %d: B molecule of %d residues, a DENSE-form null batch takes up to %d", p, m, NULL_FEAT_MAX_M);
+    if ((ft || dense) && m > NULL_FEAT_MAX_M)  // the wave shuffles' index array is uint16 (bialign_null.hpp), and so the permutations in HBM
+      return fail(BIALIGN_E_UNSUPPORTED, "pair %d: B molecule of %d residues, a %s-form null batch takes up to %d", p, m,
+                  ft ? "FEATURE" : "DENSE", NULL_FEAT_MAX_M);
     plan.max_m = std::max(plan.max_m, m);
     for (int r = 0; r < R; ++r) {
       const size_t v = (size_t)p * R + r;
@@ -1466,17 +1460,24 @@ int bialign_batch_get_null_info(const bialign_batch* b, bialign_null_info* info)
   return BIALIGN_OK;
 }
 
-int bialign_batch_dump_null_codes(bialign_batch* b, int32_t pair, int32_t replica, uint8_t* seq, uint8_t* cls) {
-  if (!b || !seq || !cls) return fail(BIALIGN_E_INVALID, "NULL argument");
-  if (!b->null_R) return fail(BIALIGN_E_INVALID, "not a null batch (bialign_batch_create_null)");
+// What the three dumps below share once their own arguments are checked: the replica is in range, the batch idle and
+// uploaded, and virtual pair *v = pair * R + replica shuffled anew on the engine's stream.
+static int null_dump_begin(bialign_batch* b, int32_t pair, int32_t replica, int* v) {
   if (pair < 0 || pair >= b->null_npairs) return fail(BIALIGN_E_INVALID, "pair %d out of range", pair);
   if (replica < 0 || replica >= b->null_R) return fail(BIALIGN_E_INVALID, "replica %d out of range", replica);
   if (int rc = bialign_batch_wait(b)) return rc;
   HIP_TRY(hipSetDevice(b->eng->device));
+  HIP_TRY(hipStreamWaitEvent(b->eng->stream, b->uploaded, 0));
+  *v = pair * b->null_R + replica;
+  return launch_shuffle_null(b, *v, 1);
+}
+
+int bialign_batch_dump_null_codes(bialign_batch* b, int32_t pair, int32_t replica, uint8_t* seq, uint8_t* cls) {
+  if (!b || !seq || !cls) return fail(BIALIGN_E_INVALID, "NULL argument");
+  if (!b->null_R) return fail(BIALIGN_E_INVALID, "not a null batch (bialign_batch_create_null)");
+  int v;
+  if (int rc = null_dump_begin(b, pair, replica, &v)) return rc;
   hipStream_t st = b->eng->stream;
-  HIP_TRY(hipStreamWaitEvent(st, b->uploaded, 0));
-  const int v = pair * b->null_R + replica;
-  if (int rc = launch_shuffle_null(b, v, 1)) return rc;
   const PairDesc& d = b->pairs[v];
   HIP_TRY(hipMemcpyAsync(seq, b->d_seq_b.p + d.seq_b, (size_t)d.m, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(cls, b->d_cls_b.p + d.seq_b, (size_t)d.m, hipMemcpyDeviceToHost, st));
@@ -1487,14 +1488,9 @@ int bialign_batch_dump_null_codes(bialign_batch* b, int32_t pair, int32_t replic
 int bialign_batch_dump_null_features(bialign_batch* b, int32_t pair, int32_t replica, double* up, double* down, double* unp) {
   if (!b || !up || !down || !unp) return fail(BIALIGN_E_INVALID, "NULL argument");
   if (!b->null_R || !b->feat) return fail(BIALIGN_E_INVALID, "not a FEATURE-form null batch (bialign_batch_create_null_features)");
-  if (pair < 0 || pair >= b->null_npairs) return fail(BIALIGN_E_INVALID, "pair %d out of range", pair);
-  if (replica < 0 || replica >= b->null_R) return fail(BIALIGN_E_INVALID, "replica %d out of range", replica);
-  if (int rc = bialign_batch_wait(b)) return rc;
-  HIP_TRY(hipSetDevice(b->eng->device));
+  int v;
+  if (int rc = null_dump_begin(b, pair, replica, &v)) return rc;
   hipStream_t st = b->eng->stream;
-  HIP_TRY(hipStreamWaitEvent(st, b->uploaded, 0));
-  const int v = pair * b->null_R + replica;
-  if (int rc = launch_shuffle_null(b, v, 1)) return rc;
   const PairDesc& d = b->pairs[v];
   double* const out[3] = {up, down, unp};
   for (int f = 0; f < 3; ++f)
@@ -1507,19 +1503,14 @@ int bialign_batch_dump_null_features(bialign_batch* b, int32_t pair, int32_t rep
 int bialign_batch_dump_null_tables(bialign_batch* b, int32_t pair, int32_t replica, int32_t* mu1_out, int32_t* mu2_out) {
   if (!b) return fail(BIALIGN_E_INVALID, "NULL argument");
   if (!b->null_R || !b->null_dense) return fail(BIALIGN_E_INVALID, "not a DENSE-form null batch (bialign_batch_create_null_dense)");
-  if (pair < 0 || pair >= b->null_npairs) return fail(BIALIGN_E_INVALID, "pair %d out of range", pair);
-  if (replica < 0 || replica >= b->null_R) return fail(BIALIGN_E_INVALID, "replica %d out of range", replica);
   if (mu1_out && !b->dense1) return fail(BIALIGN_E_INVALID, "mu1_out given, but mu1 of this batch is in LOOKUP form");
   if (mu2_out && !b->dense) return fail(BIALIGN_E_INVALID, "mu2_out given, but mu2 of this batch is in LOOKUP form");
-  if (int rc = bialign_batch_wait(b)) return rc;
-  HIP_TRY(hipSetDevice(b->eng->device));
-  hipStream_t st = b->eng->stream;
-  HIP_TRY(hipStreamWaitEvent(st, b->uploaded, 0));
   // the replica's permutation, then its tables in their place in the chunk buffer (which may hold another chunk's by now;
   // results of a run live elsewhere)
-  const int v = pair * b->null_R + replica;
+  int v;
+  if (int rc = null_dump_begin(b, pair, replica, &v)) return rc;
+  hipStream_t st = b->eng->stream;
   const int pos = (int)(std::find(b->order.begin(), b->order.end(), v) - b->order.begin());
-  if (int rc = launch_shuffle_null(b, v, 1)) return rc;
   if (int rc = launch_permute_tables(b, pos, 1)) return rc;
   const PairDesc& d = b->pairs[v];
   const size_t nm = (size_t)d.n * d.m;

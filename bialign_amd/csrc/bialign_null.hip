@@ -5,14 +5,33 @@
 
 namespace bialign {
 
-// FEATURE-form null batch: one wave per virtual pair, the index array of the batch's longest B in LDS
-static int launch_shuffle_features(bialign_batch* b, int first, int count) {
-  if (b->null_max_m < 1 || b->null_max_m > NULL_FEAT_MAX_M)  // (bialign_batch_create_null_features refuses longer ones)
-    return fail(BIALIGN_E_UNSUPPORTED, "feature shuffle: longest B molecule %d outside 1..%d", b->null_max_m, NULL_FEAT_MAX_M);
-  const int64_t src_tot = (int64_t)b->d_null_seq.n;  // doubles per plane of the uploaded B features
-  ShuffleFeatArgs a{};
+// the fields the three shuffle kernels share
+template <class Args>
+static Args shuffle_args(const bialign_batch* b, int first, int count) {
+  Args a{};
   a.pairs = b->d_pairs.p;
   a.src_off = b->d_null_off.p;
+  a.first = first;
+  a.count = count;
+  a.replicas = b->null_R;
+  a.seed = b->null_seed;
+  return a;
+}
+
+// The two wave-per-pair kernels: one wave per virtual pair, the index array of the batch's longest B in LDS
+// (bialign_batch_create_null_features / _dense refuse longer ones than NULL_FEAT_MAX_M)
+template <class Args>
+static int launch_wave_shuffle(void (*kernel)(Args), const char* what, const bialign_batch* b, const Args& a) {
+  if (b->null_max_m < 1 || b->null_max_m > NULL_FEAT_MAX_M)
+    return fail(BIALIGN_E_UNSUPPORTED, "%s shuffle: longest B molecule %d outside 1..%d", what, b->null_max_m, NULL_FEAT_MAX_M);
+  const size_t lds = ((size_t)b->null_max_m * sizeof(uint16_t) + 15) / 16 * 16;
+  return launch(kernel, dim3((unsigned)std::min(a.count, NULL_FEAT_MAX_GRID)), dim3(64), lds, b->eng->stream, a);
+}
+
+// FEATURE-form null batch
+static int launch_shuffle_features(bialign_batch* b, int first, int count) {
+  const int64_t src_tot = (int64_t)b->d_null_seq.n;  // doubles per plane of the uploaded B features
+  ShuffleFeatArgs a = shuffle_args<ShuffleFeatArgs>(b, first, count);
   a.src_seq = b->d_null_seq.p;
   a.src_up = b->d_null_feat.p;
   a.src_down = b->d_null_feat.p + src_tot;
@@ -21,32 +40,18 @@ static int launch_shuffle_features(bialign_batch* b, int first, int count) {
   a.dst_up = b->d_feat_b.p;
   a.dst_down = b->d_feat_b.p + b->feat_tot_b;
   a.dst_unp = b->d_feat_b.p + 2 * b->feat_tot_b;
-  a.first = first;
-  a.count = count;
-  a.replicas = b->null_R;
-  a.seed = b->null_seed;
-  const size_t lds = ((size_t)b->null_max_m * sizeof(uint16_t) + 15) / 16 * 16;
-  return launch(shuffle_features_kernel, dim3((unsigned)std::min(count, NULL_FEAT_MAX_GRID)), dim3(64), lds, b->eng->stream, a);
+  return launch_wave_shuffle(shuffle_features_kernel, "feature", b, a);
 }
 
-// DENSE-form null batch: one wave per virtual pair, the same index array; the finished permutations go to d_null_perm
+// DENSE-form null batch: the finished permutations go to d_null_perm
 static int launch_shuffle_index(bialign_batch* b, int first, int count) {
-  if (b->null_max_m < 1 || b->null_max_m > NULL_FEAT_MAX_M)  // (bialign_batch_create_null_dense refuses longer ones)
-    return fail(BIALIGN_E_UNSUPPORTED, "index shuffle: longest B molecule %d outside 1..%d", b->null_max_m, NULL_FEAT_MAX_M);
-  ShuffleIndexArgs a{};
-  a.pairs = b->d_pairs.p;
-  a.src_off = b->d_null_off.p;
+  ShuffleIndexArgs a = shuffle_args<ShuffleIndexArgs>(b, first, count);
   a.src_seq = b->dense1 ? nullptr : b->d_null_seq.p;
   a.src_cls = b->dense ? nullptr : b->d_null_cls.p;
   a.dst_seq = b->d_seq_b.p;
   a.dst_cls = b->d_cls_b.p;
   a.dst_perm = b->d_null_perm.p;
-  a.first = first;
-  a.count = count;
-  a.replicas = b->null_R;
-  a.seed = b->null_seed;
-  const size_t lds = ((size_t)b->null_max_m * sizeof(uint16_t) + 15) / 16 * 16;
-  return launch(shuffle_index_kernel, dim3((unsigned)std::min(count, NULL_FEAT_MAX_GRID)), dim3(64), lds, b->eng->stream, a);
+  return launch_wave_shuffle(shuffle_index_kernel, "index", b, a);
 }
 
 int launch_permute_tables(bialign_batch* b, int first, int count) {
@@ -77,17 +82,11 @@ int launch_shuffle_null(bialign_batch* b, int first, int count) {
   if (!b->null_R || count < 1) return BIALIGN_OK;
   if (b->feat) return launch_shuffle_features(b, first, count);
   if (b->null_dense) return launch_shuffle_index(b, first, count);
-  ShuffleArgs a{};
-  a.pairs = b->d_pairs.p;
-  a.src_off = b->d_null_off.p;
+  ShuffleArgs a = shuffle_args<ShuffleArgs>(b, first, count);
   a.src_seq = b->d_null_seq.p;
   a.src_cls = b->d_null_cls.p;
   a.dst_seq = b->d_seq_b.p;
   a.dst_cls = b->d_cls_b.p;
-  a.first = first;
-  a.count = count;
-  a.replicas = b->null_R;
-  a.seed = b->null_seed;
   return launch(shuffle_codes_kernel, dim3((unsigned)(((int64_t)count + NULL_BLOCK - 1) / NULL_BLOCK)), dim3(NULL_BLOCK), 0,
                 b->eng->stream, a);
 }

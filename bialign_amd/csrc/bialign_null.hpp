@@ -55,6 +55,7 @@ struct ShuffleArgs {
 
 constexpr int NULL_BLOCK = 256;
 
+// (not moved onto the wave kernels below: their uint16 index array would refuse len_b > 65535, which this form takes)
 __global__ __launch_bounds__(NULL_BLOCK) void shuffle_codes_kernel(ShuffleArgs A) {
   const int64_t t0 = (int64_t)blockIdx.x * NULL_BLOCK + threadIdx.x;
   if (t0 >= A.count) return;
@@ -144,20 +145,46 @@ __global__ __launch_bounds__(NULL_BLOCK) void null_stats_kernel(NullStatsArgs A)
 // (Draws kept in LDS as well would double the array to 4 * m bytes, beyond a workgroup's 160 KiB for the longest
 // molecules the engine takes; registers + readlane need none.)
 // Vector loads and stores, 64-bit offsets, no atomics.  m = 1: the chain is empty, the identity.
-struct ShuffleFeatArgs {
-  const PairDesc* pairs;    // the VIRTUAL pairs: m, and seq_b = start of the replica's slice in dst_seq / dst_*
-  const int64_t* src_off;   // [real pairs] start of pair p's B in src_seq / src_*
-  const uint8_t* src_seq;   // the uploaded B codes
-  const double *src_up, *src_down, *src_unp;  // ... and features
-  uint8_t* dst_seq;         // the replica buffers
-  double *dst_up, *dst_down, *dst_unp;
+// What the wave-per-pair kernels' arguments share with ShuffleArgs, field for field (the launchers fill them in one place,
+// bialign_null.hip).  ShuffleArgs itself keeps its layout: extending this would move shuffle_codes_kernel's argument loads.
+struct ShuffleBase {
+  const PairDesc* pairs;    // the VIRTUAL pairs: m, and seq_b = start of the replica's slice in the dst_* buffers
+  const int64_t* src_off;   // [real pairs] start of pair p's B in the src_* buffers
   int32_t first, count;     // virtual pairs first .. first + count
   int32_t replicas;
   uint32_t seed;
 };
 
+struct ShuffleFeatArgs : ShuffleBase {
+  const uint8_t* src_seq;   // the uploaded B codes
+  const double *src_up, *src_down, *src_unp;  // ... and features
+  uint8_t* dst_seq;         // the replica buffers
+  double *dst_up, *dst_down, *dst_unp;
+};
+
 // (the index array is uint16: m <= NULL_FEAT_MAX_M = 65535, bialign_host.hpp, checked where the batch is created)
 constexpr int NULL_FEAT_MAX_GRID = 1 << 20;  // workgroups of a launch; more virtual pairs loop
+
+// The permutation of replica hash h over 0..m-1, left in perm[0..m) for every lane of the one wave that calls it (steps
+// 1 and 2 above; m is wave-uniform).  The only statement of the chain on the device: both wave-per-pair kernels call it.
+__device__ __forceinline__ void null_perm_to_lds(uint32_t h, int32_t m, int32_t lane, uint16_t* perm) {
+  for (int32_t x = lane; x < m; x += 64) perm[x] = (uint16_t)x;
+  __syncthreads();
+  for (int32_t tb = (m - 1) & ~63; tb >= 0; tb -= 64) {
+    const uint32_t d = null_draw(h, (uint32_t)(tb + lane));  // lane k holds draw(tb + k) <= tb + k
+    const int32_t khi = m - 1 - tb < 63 ? m - 1 - tb : 63, klo = tb == 0 ? 1 : 0;
+    for (int32_t k = khi; k >= klo; --k) {
+      const int32_t t = tb + k;                                    // m - 1 down to 1
+      const int32_t j = __builtin_amdgcn_readlane((int32_t)d, k);  // <= t < m: inside the array
+      const uint16_t pt = perm[t], pj = perm[j];
+      if (lane == 0) {
+        perm[t] = pj;
+        perm[j] = pt;
+      }
+    }
+  }
+  __syncthreads();
+}
 
 __global__ __launch_bounds__(64) void shuffle_features_kernel(ShuffleFeatArgs A) {
   extern __shared__ uint16_t null_perm[];  // [longest m of the launch]
@@ -169,22 +196,7 @@ __global__ __launch_bounds__(64) void shuffle_features_kernel(ShuffleFeatArgs A)
     const int32_t m = __builtin_amdgcn_readfirstlane(pd.m);
     const int64_t src = A.src_off[p], dst = pd.seq_b;
     const uint32_t h = null_hash(A.seed, (uint32_t)p, (uint32_t)r);
-    for (int32_t x = lane; x < m; x += 64) null_perm[x] = (uint16_t)x;
-    __syncthreads();
-    for (int32_t tb = (m - 1) & ~63; tb >= 0; tb -= 64) {
-      const uint32_t d = null_draw(h, (uint32_t)(tb + lane));  // lane k holds draw(tb + k) <= tb + k
-      const int32_t khi = m - 1 - tb < 63 ? m - 1 - tb : 63, klo = tb == 0 ? 1 : 0;
-      for (int32_t k = khi; k >= klo; --k) {
-        const int32_t t = tb + k;                                    // m - 1 down to 1
-        const int32_t j = __builtin_amdgcn_readlane((int32_t)d, k);  // <= t < m: inside the array
-        const uint16_t pt = null_perm[t], pj = null_perm[j];
-        if (lane == 0) {
-          null_perm[t] = pj;
-          null_perm[j] = pt;
-        }
-      }
-    }
-    __syncthreads();
+    null_perm_to_lds(h, m, lane, null_perm);
     // (source and replica buffers are distinct allocations: the four loads of a residue go out together)
     const uint8_t* __restrict__ const ss = A.src_seq + src;
     const double* __restrict__ const su = A.src_up + src;
@@ -222,15 +234,10 @@ __global__ __launch_bounds__(64) void shuffle_features_kernel(ShuffleFeatArgs A)
 // segments: HBM sees each source byte once and each destination byte once.  T = permute_tile_rows(m): PERM_ROWS rows,
 // fewer where they exceed the 64 KiB tile; a row that alone exceeds it (m > PERM_LDS_DW) is gathered straight from
 // global memory.  Vector loads and stores, 64-bit offsets, no atomics.  perm[x] < m: the index kernel ran first.
-struct ShuffleIndexArgs {
-  const PairDesc* pairs;    // the VIRTUAL pairs: m, and seq_b = start of the replica's slice in dst_*
-  const int64_t* src_off;   // [real pairs] start of pair p's B in src_seq / src_cls
+struct ShuffleIndexArgs : ShuffleBase {
   const uint8_t *src_seq, *src_cls;  // the uploaded B codes; nullptr: mu1 (seq) / mu2 (cls) is dense
   uint8_t *dst_seq, *dst_cls;        // the replica buffers
   uint16_t* dst_perm;                // the replicas' permutations
-  int32_t first, count;     // virtual pairs first .. first + count
-  int32_t replicas;
-  uint32_t seed;
 };
 
 __global__ __launch_bounds__(64) void shuffle_index_kernel(ShuffleIndexArgs A) {
@@ -243,23 +250,7 @@ __global__ __launch_bounds__(64) void shuffle_index_kernel(ShuffleIndexArgs A) {
     const int32_t m = __builtin_amdgcn_readfirstlane(pd.m);
     const int64_t src = A.src_off[p], dst = pd.seq_b;
     const uint32_t h = null_hash(A.seed, (uint32_t)p, (uint32_t)r);
-    // (the chain of shuffle_features_kernel, restated: shared through a device function, that kernel's code moved)
-    for (int32_t x = lane; x < m; x += 64) null_perm[x] = (uint16_t)x;
-    __syncthreads();
-    for (int32_t tb = (m - 1) & ~63; tb >= 0; tb -= 64) {
-      const uint32_t d = null_draw(h, (uint32_t)(tb + lane));  // lane k holds draw(tb + k) <= tb + k
-      const int32_t khi = m - 1 - tb < 63 ? m - 1 - tb : 63, klo = tb == 0 ? 1 : 0;
-      for (int32_t k = khi; k >= klo; --k) {
-        const int32_t t = tb + k;                                    // m - 1 down to 1
-        const int32_t j = __builtin_amdgcn_readlane((int32_t)d, k);  // <= t < m: inside the array
-        const uint16_t pt = null_perm[t], pj = null_perm[j];
-        if (lane == 0) {
-          null_perm[t] = pj;
-          null_perm[j] = pt;
-        }
-      }
-    }
-    __syncthreads();
+    null_perm_to_lds(h, m, lane, null_perm);
     uint16_t* __restrict__ const dp = A.dst_perm + dst;
     for (int32_t x = lane; x < m; x += 64) {
       const int32_t s = null_perm[x];  // < m

@@ -106,21 +106,22 @@ class Batch:
     def __init__(self, engine, mols_a, mols_b, s1, s2, gap_opening_cost, gap_cost, shift_cost,
                  max_shift, hbm_budget_bytes=0, recurrence=0, mu2_dense=None, score_only=False,
                  lean_trace=False, mu1_dense=None, mu2_features=None, level_trace=False, null=None, null_dense=None):
+        null_kind = "dense" if null_dense is not None else ("lookup" if null is not None else None)
         if null_dense is not None:
             if mu1_dense is None and mu2_dense is None:
                 raise ValueError("null_dense needs mu1_dense and / or mu2_dense (a LOOKUP null batch is null=)")
             if null is not None or mu2_features is not None:
                 raise ValueError("null_dense excludes null and mu2_features")
-            if lean_trace or level_trace:
-                raise ValueError("a null batch is score-only: lean_trace / level_trace do not apply")
-            replicas, seed = check_null(null_dense)
-        if null is not None:
+        elif null is not None:
             replicas, seed = check_null(null)
             if mu2_dense is not None or mu1_dense is not None:
                 raise ValueError("a null batch takes mu1 in LOOKUP form and mu2 in LOOKUP or FEATURE form "
                                  "(no mu1_dense / mu2_dense)")
+        if null_kind:
             if lean_trace or level_trace:
                 raise ValueError("a null batch is score-only: lean_trace / level_trace do not apply")
+            if null_dense is not None:
+                replicas, seed = check_null(null_dense)
         if mu2_features is not None and mu2_dense is not None:
             raise ValueError("mu2_features and mu2_dense exclude each other")
         if level_trace and (score_only or lean_trace):
@@ -180,37 +181,22 @@ class Batch:
                         mu1_ptr, mu1_off_ptr)
         self._h = ctypes.c_void_p()
         self.replicas = None
-        self._null_forms = None
-        if null_dense is not None:
-            if self.npairs * replicas > 2 ** 31 - 1:
-                raise ValueError("npairs * replicas exceeds INT32_MAX")
-            self.replicas = replicas
-            self._null_forms = (mu1_flat is not None, mu2_flat is not None)
-            spec = _lib.NullSpec(replicas, seed)
-            check(lib.bialign_batch_create_null_dense(engine._h, ctypes.byref(prm), ctypes.byref(sc), ctypes.byref(pr),
-                                                      ctypes.byref(spec), int(hbm_budget_bytes), ctypes.byref(self._h)))
-        elif null is not None:
-            if self.npairs * replicas > 2 ** 31 - 1:
-                raise ValueError("npairs * replicas exceeds INT32_MAX")
-            self.replicas = replicas
-            spec = _lib.NullSpec(replicas, seed)
-            if feat is None:
-                check(lib.bialign_batch_create_null(engine._h, ctypes.byref(prm), ctypes.byref(sc), ctypes.byref(pr),
-                                                    ctypes.byref(spec), int(hbm_budget_bytes), ctypes.byref(self._h)))
-            else:
-                sw, fa, fb = feat
-                ft = _lib.Features(sw, *(_ptr(x, ctypes.c_double) for x in fa + fb))
-                check(lib.bialign_batch_create_null_features(engine._h, ctypes.byref(prm), ctypes.byref(sc),
-                                                             ctypes.byref(pr), ctypes.byref(ft), ctypes.byref(spec),
-                                                             int(hbm_budget_bytes), ctypes.byref(self._h)))
-        elif feat is None:
-            check(lib.bialign_batch_create(engine._h, ctypes.byref(prm), ctypes.byref(sc), ctypes.byref(pr),
-                                           int(hbm_budget_bytes), ctypes.byref(self._h)))
-        else:
+        self._null_forms = (mu1_flat is not None, mu2_flat is not None) if null_dense is not None else None
+        args = [engine._h, ctypes.byref(prm), ctypes.byref(sc), ctypes.byref(pr)]
+        if feat is not None:
             sw, fa, fb = feat
             ft = _lib.Features(sw, *(_ptr(x, ctypes.c_double) for x in fa + fb))
-            check(lib.bialign_batch_create_features(engine._h, ctypes.byref(prm), ctypes.byref(sc), ctypes.byref(pr),
-                                                    ctypes.byref(ft), int(hbm_budget_bytes), ctypes.byref(self._h)))
+            args.append(ctypes.byref(ft))
+        if null_kind:
+            if self.npairs * replicas > 2 ** 31 - 1:
+                raise ValueError("npairs * replicas exceeds INT32_MAX")
+            self.replicas = replicas
+            spec = _lib.NullSpec(replicas, seed)
+            args.append(ctypes.byref(spec))
+        create = {(None, False): lib.bialign_batch_create, (None, True): lib.bialign_batch_create_features,
+                  ("lookup", False): lib.bialign_batch_create_null, ("lookup", True): lib.bialign_batch_create_null_features,
+                  ("dense", False): lib.bialign_batch_create_null_dense}[null_kind, feat is not None]
+        check(create(*args, int(hbm_budget_bytes), ctypes.byref(self._h)))
         engine._batches.add(self)
         self.info = self.current_info()
         self.affine = bool(self.info["affine"])

@@ -183,29 +183,36 @@ def zscores_from_stats(score, stats):
     return dict(score=score, mean=mean, std=std, z=z, p_emp=(n_ge + 1) / (reps + 1), n_ge=n_ge, replicas=reps)
 
 
+def _run_and_close(batch, result):
+    try:
+        batch.run()
+        return result(batch)
+    finally:
+        batch.close()
+
+
+def _zscores(npairs, observed, score_batch, null_batch):
+    """What the three ``zscores*`` share once their arguments are checked: the observed scores (the caller's, or those
+    of the score-only batch ``score_batch()`` makes), the null batch ``null_batch()`` makes, its reductions, the z-scores."""
+    if observed is not None:
+        observed = np.ascontiguousarray(observed, dtype=np.int32)
+        if observed.shape != (npairs,):
+            raise ValueError("observed needs one score per pair")
+    else:
+        observed = _run_and_close(score_batch(), lambda b: b.scores().copy())
+    return zscores_from_stats(observed, _run_and_close(null_batch(), lambda nb: nb.null_stats(observed)))
+
+
 def zscores(pairs, params, replicas=100, seed=0, observed=None, engine=None, hbm_budget_bytes=0, recurrence=0):
     """z-scores of the pairs' optimal scores against ``replicas`` shuffles of each pair's B (``zscores_from_stats``).
     ``observed``: the pairs' real scores if the caller has them; else a score-only batch computes them first."""
     pairs, replicas, seed = _check_pairs(pairs, replicas, seed)
-    if observed is not None:
-        observed = np.ascontiguousarray(observed, dtype=np.int32)
-        if observed.shape != (len(pairs),):
-            raise ValueError("observed needs one score per pair")
-    from .batch import make_batch
-    if observed is None:
-        b = make_batch(pairs, params, engine=engine, hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence, score_only=True)
-        try:
-            b.run()
-            observed = b.scores().copy()
-        finally:
-            b.close()
-    nb = null_batch(pairs, params, replicas, seed=seed, engine=engine, hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence)
-    try:
-        nb.run()
-        stats = nb.null_stats(observed)
-    finally:
-        nb.close()
-    return zscores_from_stats(observed, stats)
+    common = dict(engine=engine, hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence)
+
+    def score_batch():
+        from .batch import make_batch
+        return make_batch(pairs, params, score_only=True, **common)
+    return _zscores(len(pairs), observed, score_batch, lambda: null_batch(pairs, params, replicas, seed=seed, **common))
 
 
 def _check_feature_args(molecules, pair_index, replicas, seed):
@@ -244,27 +251,13 @@ def zscores_features(molecules, pair_index, params, replicas=100, seed=0, observ
     against ``replicas`` shuffles of each pair's B (``zscores_from_stats``).  ``observed``: the pairs' real scores if
     the caller has them; else ``make_feature_batch(score_only=True)`` computes them first."""
     molecules, pair_index, replicas, seed = _check_feature_args(molecules, pair_index, replicas, seed)
-    if observed is not None:
-        observed = np.ascontiguousarray(observed, dtype=np.int32)
-        if observed.shape != (len(pair_index),):
-            raise ValueError("observed needs one score per pair")
-    if observed is None:
+    common = dict(engine=engine, hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence)
+
+    def score_batch():
         from .batch import make_feature_batch
-        b = make_feature_batch(molecules, pair_index, params, engine=engine, hbm_budget_bytes=hbm_budget_bytes,
-                               recurrence=recurrence, score_only=True)
-        try:
-            b.run()
-            observed = b.scores().copy()
-        finally:
-            b.close()
-    nb = null_feature_batch(molecules, pair_index, params, replicas, seed=seed, engine=engine,
-                            hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence)
-    try:
-        nb.run()
-        stats = nb.null_stats(observed)
-    finally:
-        nb.close()
-    return zscores_from_stats(observed, stats)
+        return make_feature_batch(molecules, pair_index, params, score_only=True, **common)
+    return _zscores(len(pair_index), observed, score_batch,
+                    lambda: null_feature_batch(molecules, pair_index, params, replicas, seed=seed, **common))
 
 
 def null_dense_batch(pairs, params, replicas, seed=0, mu1_dense=None, mu2_dense=None, engine=None, hbm_budget_bytes=0,
@@ -286,24 +279,10 @@ def zscores_dense(pairs, params, replicas=100, seed=0, mu1_dense=None, mu2_dense
     ``observed``: the pairs' real scores if the caller has them; else ``make_batch(score_only=True)`` with the same
     tables computes them first."""
     pairs, replicas, seed = check_dense_args(pairs, (replicas, seed), mu1_dense, mu2_dense)
-    if observed is not None:
-        observed = np.ascontiguousarray(observed, dtype=np.int32)
-        if observed.shape != (len(pairs),):
-            raise ValueError("observed needs one score per pair")
-    if observed is None:
+    common = dict(mu1_dense=mu1_dense, mu2_dense=mu2_dense, engine=engine, hbm_budget_bytes=hbm_budget_bytes,
+                  recurrence=recurrence)
+
+    def score_batch():
         from .batch import make_batch
-        b = make_batch(pairs, params, engine=engine, hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence,
-                       score_only=True, mu1_dense=mu1_dense, mu2_dense=mu2_dense)
-        try:
-            b.run()
-            observed = b.scores().copy()
-        finally:
-            b.close()
-    nb = null_dense_batch(pairs, params, replicas, seed=seed, mu1_dense=mu1_dense, mu2_dense=mu2_dense, engine=engine,
-                          hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence)
-    try:
-        nb.run()
-        stats = nb.null_stats(observed)
-    finally:
-        nb.close()
-    return zscores_from_stats(observed, stats)
+        return make_batch(pairs, params, score_only=True, **common)
+    return _zscores(len(pairs), observed, score_batch, lambda: null_dense_batch(pairs, params, replicas, seed=seed, **common))
