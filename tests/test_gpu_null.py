@@ -165,6 +165,29 @@ def test_stats_equal_numpy(R):
     b.close()
 
 
+def test_stats_equal_python_integers_at_large_scores():
+    """test_stats_equal_numpy's scores stay below 46341, where a 32-bit square, or a 32-bit shuffle of a partial sum of
+    squares, would pass it.  The same three shapes with every score multiplied by the largest factor the int32 safety
+    window admits (tests/window_edge.py): replica scores of 10^6 .. 10^7, 65 replicas (more than a wave's lanes),
+    reduced in Python integers."""
+    import window_edge as we
+    problems = [we.Problem("lookup", n, m, 1, 4700 + t) for t, (n, m) in enumerate([(30, 21), (9, 30), (25, 25)])]
+    k, R = we.batch_scale(problems), 65
+    assert max(p.product(k) for p in problems) < we.WINDOW <= max(p.product(k + 1) for p in problems)
+    b = sg.null_batch([p.pair for p in problems], problems[0].at(k), R, seed=R)
+    b.run()
+    rows = [[int(v) for v in row] for row in b.null_scores()]
+    assert max(abs(v) for v in rows[0]) > 1 << 22
+    observed = [sorted(rows[0])[R // 2], max(rows[1]) + 1, min(rows[2])]
+    st = b.null_stats(np.array(observed, dtype=np.int32))
+    b.close()
+    assert [int(v) for v in st["sum"]] == [sum(r) for r in rows]
+    assert [int(v) for v in st["sumsq"]] == [sum(v * v for v in r) for r in rows]
+    assert [int(v) for v in st["min"]] == [min(r) for r in rows] and [int(v) for v in st["max"]] == [max(r) for r in rows]
+    assert [int(v) for v in st["n_ge"]] == [sum(v >= o for v in r) for r, o in zip(rows, observed)]
+    assert max(int(v) for v in st["sumsq"]) > 1 << 50
+
+
 # ---- refusals
 
 def test_refusals():
