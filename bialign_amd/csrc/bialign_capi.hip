@@ -33,6 +33,7 @@ struct SweepInfo {
   int blk, min_goff;            // ghost feed: steps per prefetch block, age of a record when it is read
   int ring_dw, diet_ring_dw;    // ... dwords of a wave's ring, and in the DIET layout (half-length blocks)
   int ghost_np;                 // ... 16-byte pieces per (step, a)
+  int slim_offtab_dw;           // ... fill_affine_slim_kernel: the workgroup's table of steady-block lane offsets
   int mu2_ring_dw, mu1_ring_dw; // dense-mu2 and dense-mu1 rings of a wave
   int xch_dw;                   // exchange array of a wave: NCOL lanes x (XCH_ROWS per band column, affine) W values
 };
@@ -41,7 +42,7 @@ constexpr SweepInfo sweep_info_of() {
   using G = Geo<S>;
   using GF = GhostFeed<S, NL>;
   return SweepInfo{G::W, G::R, G::RR, G::MAXOFF, G::PADB, Rec<S, NL>::RECDW, Rec<S, NL, true>::RECDW, GF::BLK, GF::MIN_GOFF,
-                   GF::RING_DW, GhostFeed<S, NL, false, 2>::RING_DW, GF::NP, Mu2Feed<S>::RING_DW, Mu1Feed<S>::RING_DW,
+                   GF::RING_DW, GhostFeed<S, NL, false, 2>::RING_DW, GF::NP, slim_offtab_dw<S>(), Mu2Feed<S>::RING_DW, Mu1Feed<S>::RING_DW,
                    (NL == 9 ? XCH_ROWS : 1) * G::W * NCOL};
 }
 #define BIALIGN_SWEEP_INFO(S, X) {sweep_info_of<S, 1>(), sweep_info_of<S, 9>()},
@@ -294,9 +295,9 @@ size_t lds_need(const SweepInfo& g, int team, int k1, int k2, int n, int m, bool
 }
 
 // fill_affine_slim_kernel (bialign_fill_slim.hpp), a workgroup of twelve waves: twelve ghost rings, a block of sentinels,
-// progress words, score tables (lds_need_slim_base); per pair of the workgroup both molecules' codes (lds_need_slim_codes)
+// progress words, the ghost feed's lane-offset table, score tables (lds_need_slim_base); per pair of the workgroup both molecules' codes (lds_need_slim_codes)
 size_t lds_need_slim_base(const SweepInfo& g, int k1, int k2) {
-  return (12 * (size_t)g.ring_dw + 4 * g.ghost_np + LDS_PROG_WORDS + (size_t)k1 * k1 + (size_t)k2 * k2) * 4;
+  return (12 * (size_t)g.ring_dw + 4 * g.ghost_np + LDS_PROG_WORDS + g.slim_offtab_dw + (size_t)k1 * k1 + (size_t)k2 * k2) * 4;
 }
 size_t lds_need_slim_codes(const SweepInfo& g, int n, int m) { return 2 * (size_t)code_pad(n) + 2 * (size_t)code_pad(m, g.PADB); }
 

@@ -84,42 +84,56 @@ struct GhostFeed {
           : "memory");
     }
   }
-  // The same for a sweep with packed records (Pack<S>): the source of a piece is the packed record of an
-  // interior step (NPC pieces per lane; the surplus lanes of a round re-read piece 0) or the full record of
-  // any other step in the pair's second region (starting at dword bnd_off).  Not used by re-sweeps (Qbase = 0).
+  // Piece q of a ring half: its step of the block, band row and 16-byte piece (the inverse of slot()).
+  __host__ __device__ static inline void piece_of(int q, int& t, int& aa, int& c) {
+    if (PIECE_MAJOR) {
+      c = q / (BLK * W);
+      const int rem = q - c * (BLK * W);
+      t = rem / W;
+      aa = rem - t * W;
+    } else {
+      t = q / (W * NP);
+      const int rem = q - t * (W * NP);
+      aa = rem / NP;
+      c = rem - aa * NP;
+    }
+  }
+  // Where in a PACKED lane record piece c of storage slot sl lies (dwords from the record's start): pieces 0 .. NCH-1 are
+  // the 16-byte chunks, piece NCH the tail (TAILDW dwords, read 16 bytes wide); the surplus pieces re-read piece 0.
+  __host__ __device__ static inline int packed_piece_dw(int c, int sl) {
+    using PK = Pack<S>;
+    return c < PK::NCH ? c * R_::CH + sl * 4 : (c == PK::NCH && PK::TAILDW ? PK::NCH * R_::CH + sl * PK::TAILDW : sl * 4);
+  }
+  // Source of piece q of the block that starts at phase blk_rem of local strip blk_q, for a sweep with packed records
+  // (Pack<S>): the packed record of an interior step (NPC pieces per lane) or the full record of any other step in the
+  // pair's second region (starting at dword bnd_off).  `lay` is the pair's layers (the sweeps), or 0 as an int64_t: the
+  // source as a dword offset from there (host-side checks).
+  template <typename Base>
+  __host__ __device__ static inline Base packed_src(Base lay, int q, int64_t bnd_off, int blk_q, int blk_rem, int P, int T,
+                                                    int w, int m, int rec_last) {
+    using PK = Pack<S>;
+    int t, aa, c;
+    piece_of(q, t, aa, c);
+    const int xr = blk_rem + t - aa;
+    const int ql = blk_q + (xr >= P ? 1 : 0) - (xr < 0 ? 1 : 0);
+    const int jj = xr - (xr >= P ? P : 0) + (xr < 0 ? P : 0);  // the ghost lane's column
+    const int ts = jj + 2 * (R - 1) + aa;                      // the bottom lane row of the strip above was there at this t
+    const int cs = ts >= P ? ts - P : ts, qs = ql * T + w - 1 + (ts >= P ? 1 : 0);
+    const int64_t rec = (int64_t)(ql * T + w - 1) * P + ts;
+    const bool valid = rec >= 0 && rec <= rec_last;
+    const int sl = (R - 2) * W + aa;  // storage slot of the bottom real row
+    if (valid && PK::interior(qs, cs, m)) return lay + rec * PK::RECDW + packed_piece_dw(c, sl);
+    return lay + bnd_off + (valid ? PK::bidx(qs, cs, P, m) : 0) * R_::RECDW +
+           (c < R_::NCH4 ? c * R_::CH + sl * 4 : R_::NCH4 * R_::CH + sl * R_::TAIL);
+  }
+  // The DMAs of a block of a sweep with packed records -- any block: the general path.  Not used by re-sweeps (Qbase = 0).
   __device__ static __forceinline__ void issue_packed(const int32_t* lay, int64_t bnd_off, int m, int h0, int blk_q,
                                                       int blk_rem, int P, int T, int w, int rec_last, int lane,
                                                       uint32_t lds_base) {
-    using PK = Pack<S>;
 #pragma unroll
     for (int r = 0; r < ROUNDS; ++r) {
-      const int q = min(r * 64 + lane, NPIECE - 1);
-      int t, aa, c;
-      if (PIECE_MAJOR) {
-        c = q / (BLK * W);
-        const int rem = q - c * (BLK * W);
-        t = rem / W;
-        aa = rem - t * W;
-      } else {
-        t = q / (W * NP);
-        const int rem = q - t * (W * NP);
-        aa = rem / NP;
-        c = rem - aa * NP;
-      }
-      const int xr = blk_rem + t - aa;
-      const int ql = blk_q + (xr >= P ? 1 : 0) - (xr < 0 ? 1 : 0);
-      const int jj = xr - (xr >= P ? P : 0) + (xr < 0 ? P : 0);  // the ghost lane's column
-      const int ts = jj + 2 * (R - 1) + aa;                      // the bottom lane row of the strip above was there at this t
-      const int cs = ts >= P ? ts - P : ts, qs = ql * T + w - 1 + (ts >= P ? 1 : 0);
-      const int64_t rec = (int64_t)(ql * T + w - 1) * P + ts;
-      const bool valid = rec >= 0 && rec <= rec_last;
-      const int sl = (R - 2) * W + aa;  // storage slot of the bottom real row
-      const int32_t* p;
-      if (valid && PK::interior(qs, cs, m))  // pieces 0 .. NCH-1: the 16-byte chunks; piece NCH: the tail (TAILDW dwords, read 16 bytes wide)
-        p = lay + rec * PK::RECDW + (c < PK::NCH ? c * R_::CH + sl * 4 : (c == PK::NCH && PK::TAILDW ? PK::NCH * R_::CH + sl * PK::TAILDW : sl * 4));
-      else
-        p = lay + bnd_off + (valid ? PK::bidx(qs, cs, P, m) : 0) * R_::RECDW +
-            (c < R_::NCH4 ? c * R_::CH + sl * 4 : R_::NCH4 * R_::CH + sl * R_::TAIL);
+      const int q = min(r * 64 + lane, NPIECE - 1);  // (the surplus lanes of the last round repeat the last piece)
+      const int32_t* p = packed_src(lay, q, bnd_off, blk_q, blk_rem, P, T, w, m, rec_last);
       const uint32_t dst = lds_base + r * 1024;
       uint32_t keep;
       asm volatile(
@@ -127,6 +141,49 @@ struct GhostFeed {
           "global_load_lds_dwordx4 %1, off sc1\n\ts_mov_b32 m0, %0"
           : "=&s"(keep)
           : "v"(p), "s"(dst)
+          : "memory");
+    }
+  }
+
+  // STEADY blocks.  A block is steady when every one of its source records is a packed interior record of one strip
+  // and no ghost lane wraps around the period.  Then, in packed_src's terms, ql = blk_q and jj = xr for every
+  // piece, ts = blk_rem + t + 2(R-1) (the band row cancels) and the source is
+  //     steady_base_dword(blk_q, blk_rem)  +  lane_offset(round, lane) / 4 :
+  // a wave-uniform base plus a constant of the lane and the round, the same for every wave, pair and block -- no
+  // division, no wrap, no 64-bit product per lane.  The four tests are wave-uniform; the second one is
+  // blk_rem + 2(R-1) >= LO and also keeps xr >= 0, the third one keeps ts <= m - S < P.
+  __host__ __device__ static inline bool steady(int blk_q, int blk_rem, int P, int T, int w, int m, int rec_last) {
+    using PK = Pack<S>;
+    const int qs = blk_q * T + w - 1, ts_last = blk_rem + BLK - 1 + 2 * (R - 1);
+    return qs >= PK::Q0 && blk_rem >= 3 * S + 1 && ts_last <= m - S && (int64_t)qs * P + ts_last <= rec_last;
+  }
+  __host__ __device__ static inline int64_t steady_base_dword(int blk_q, int blk_rem, int P, int T, int w) {
+    return ((int64_t)(blk_q * T + w - 1) * P + blk_rem + 2 * (R - 1)) * Pack<S>::RECDW;
+  }
+  // byte offset of lane `lane`'s piece of round r from the base of a steady block
+  __host__ __device__ static inline uint32_t lane_offset(int r, int lane) {
+    int t, aa, c;
+    piece_of(r * 64 + lane < NPIECE - 1 ? r * 64 + lane : NPIECE - 1, t, aa, c);
+    return (uint32_t)(t * Pack<S>::RECDW + packed_piece_dw(c, (R - 2) * W + aa)) * 4u;
+  }
+  static constexpr int OFFTAB_DW = ROUNDS * 64;  // the lane offsets of all rounds as a table, [round][lane]
+  // The DMAs of a steady block: the base in scalar registers, lane l's offsets of the ROUNDS rounds at offtab[r * 64 + l]
+  // (LDS: they are read here, per block, and occupy no register in between).
+  __device__ static __forceinline__ void issue_steady(const int32_t* lay, int blk_q, int blk_rem, int P, int T, int w,
+                                                      const int32_t* offtab, int lane, uint32_t lds_base) {
+    const int32_t* base = lay + steady_base_dword(blk_q, blk_rem, P, T, w);
+    uint32_t off[ROUNDS];  // (read up front: no LDS load moves across a DMA's asm, each would wait for its own round trip)
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r) off[r] = (uint32_t)offtab[r * 64 + lane];
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r) {
+      const uint32_t dst = lds_base + r * 1024;
+      uint32_t keep;
+      asm volatile(
+          "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+          "global_load_lds_dwordx4 %1, %3 sc1\n\ts_mov_b32 m0, %0"
+          : "=&s"(keep)
+          : "v"(off[r]), "s"(dst), "s"(base)
           : "memory");
     }
   }
@@ -174,6 +231,11 @@ struct GhostFeed {
     }
   }
 };
+
+// LDS dwords of fill_affine_slim_kernel's table of steady-block lane offsets (one per workgroup; the LEAN form leaves
+// it unused).  The host sizes the workgroup's LDS with it (sweep_info_of).
+template <int S>
+constexpr int slim_offtab_dw() { return BIALIGN_FEED_FAST ? GhostFeed<S, 9>::OFFTAB_DW : 0; }
 
 // ---------------------------------------------------------------------------
 // Dense-mu2 feed (structure similarities that are not a

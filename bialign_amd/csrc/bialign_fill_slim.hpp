@@ -78,7 +78,10 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
   v4i* ring = reinterpret_cast<v4i*>(smem + wv * GF::RING_DW);        // ghost-row ring, two halves
   int32_t* sentblk = smem + NW * PERW;
   volatile int32_t* prog_lds = smem + NW * PERW + SENTBLK + pw * TW;  // [16]: this team's words
-  int32_t* s1 = smem + NW * PERW + SENTBLK + LDS_PROG_WORDS;                      // [k1*k1]
+  // the ghost feed's lane offsets of a steady block (GhostFeed::issue_steady), [round][lane]; one table per workgroup
+  constexpr bool FEED_FAST = BIALIGN_FEED_FAST && !LEAN;
+  int32_t* offtab = smem + NW * PERW + SENTBLK + LDS_PROG_WORDS;
+  int32_t* s1 = offtab + slim_offtab_dw<S>();                         // [k1*k1]
   int32_t* s2 = s1 + k1 * k1;                                         // [k2*k2]
   uint8_t* codes = reinterpret_cast<uint8_t*>(s2 + k2 * k2);          // per pair: seq A, cls A, seq B, cls B (A.slim_code_bytes each pair)
   const int npad = code_pad(n), mpad = code_pad(m, PADB);
@@ -89,6 +92,8 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
 
   for (int t = threadIdx.x; t < NW * PERW + SENTBLK; t += 64 * NW) smem[t] = SENT;
   if (threadIdx.x < LDS_PROG_WORDS) smem[NW * PERW + SENTBLK + threadIdx.x] = 0;
+  if (FEED_FAST)
+    for (int t = threadIdx.x; t < GF::OFFTAB_DW; t += 64 * NW) offtab[t] = (int32_t)GF::lane_offset(t >> 6, t & 63);
   for (int t = threadIdx.x; t < k1 * k1; t += 64 * NW) s1[t] = A.s1[t];
   for (int t = threadIdx.x; t < k2 * k2; t += 64 * NW) s2[t] = A.s2[t];
   if (have_pair) {  // each team stages its pair's codes
@@ -175,13 +180,20 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
       __builtin_amdgcn_s_sleep(16);
     }
   };
+  // is the block in flight a steady one (GhostFeed::steady: all of its ring entries are packed records)?  Set by the
+  // prefetch of a block, read by its unpacking one block later -- which comes before the next prefetch.  Wave-uniform.
+  bool blk_steady = false;
   auto prefetch_block = [&](int h0, int half) __attribute__((always_inline)) {
     wait_partner(h0 + GF::BLK - 1);
+    if (FEED_FAST) blk_steady = GF::steady(blk_q, blk_rem, P, T, w, m, rec_last);
     // (the lane number is laundered: everything the feed derives from it -- piece, band row, chunk, 64-bit source bases
-    //  for three rounds -- would otherwise be hoisted out of the sweep and sit in a dozen registers the step needs)
+    //  for three rounds; the table address of a steady block -- would otherwise be hoisted out of the sweep and sit in a
+    //  dozen registers the step needs)
     int Lv = L;
     asm volatile("" : "+v"(Lv));
-    if (LEAN) GF::issue(lay, h0, blk_q, blk_rem, P, T, w, P - 2 * (R - 1), rec_last, Lv, ring_lds + half * GF::SLOTS * 16);
+    if (FEED_FAST && blk_steady)  // nine blocks in ten at len 1024: a scalar base + the lane's offsets from the LDS table
+      GF::issue_steady(lay, blk_q, blk_rem, P, T, w, offtab, Lv, ring_lds + half * GF::SLOTS * 16);
+    else if (LEAN) GF::issue(lay, h0, blk_q, blk_rem, P, T, w, P - 2 * (R - 1), rec_last, Lv, ring_lds + half * GF::SLOTS * 16);
     else GF::issue_packed(lay, pk_bnd_off, m, h0, blk_q, blk_rem, P, T, w, rec_last, Lv, ring_lds + half * GF::SLOTS * 16);
     blk_rem += GF::BLK;
     if (blk_rem >= P) { blk_rem -= P; ++blk_q; }
@@ -226,14 +238,17 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
         pk_all = 0;
       }
       if (!LEAN) {  // the block that has just landed: lane t*W + a unpacks its entry in place (fill_affine_kernel, PK_COOP)
-        const int c0 = __builtin_amdgcn_readfirstlane(jj), q0 = __builtin_amdgcn_readfirstlane(strip);
         if (L < GF::BLK * W) {
-          const int t = L / W, ai = L - t * W;
-          int ph = c0 + t, qst = q0 * T + w;
-          if (ph >= P) { ph -= P; qst += T; }
-          const int ts = ph + 2 * (R - 1), over = ts >= P ? 1 : 0;
-          if (PK_::interior(qst - 1 + over, ts - over * P, m)) {
-            v4i* pc = ring + ghalf * GF::SLOTS + (t * W + ai) * GF::NP;
+          bool packed = true;  // a steady block: every entry is a packed record
+          if (!(FEED_FAST && blk_steady)) {
+            const int c0 = __builtin_amdgcn_readfirstlane(jj), q0 = __builtin_amdgcn_readfirstlane(strip);
+            int ph = c0 + L / W, qst = q0 * T + w;
+            if (ph >= P) { ph -= P; qst += T; }
+            const int ts = ph + 2 * (R - 1), over = ts >= P ? 1 : 0;
+            packed = PK_::interior(qst - 1 + over, ts - over * P, m);
+          }
+          if (packed) {
+            v4i* pc = ring + ghalf * GF::SLOTS + L * GF::NP;  // entry (t, a) = (L / W, L % W)
             int raw[4 * PK_::NPC], dec[4 * GF::NP];
 #pragma unroll
             for (int c = 0; c < PK_::NPC; ++c) {

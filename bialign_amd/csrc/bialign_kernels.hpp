@@ -48,6 +48,9 @@
 #ifndef BIALIGN_SLIM_DPP  // fill_affine_slim_kernel: 1 = lane L-1's values by DPP (as fill_affine_kernel), 0 = by ds_bpermute
 #define BIALIGN_SLIM_DPP 1  // like the rows': 21 VALU less, 21 LDS instructions more per step -- and 4.5 % slower (48.7 vs 46.6 ms)
 #endif
+#ifndef BIALIGN_FEED_FAST  // fill_affine_slim_kernel: 1 = steady ghost blocks take GhostFeed::issue_steady (scalar base + lane
+#define BIALIGN_FEED_FAST 1  // constants), 0 = every block recomputes its 3 x 64 source addresses (A/B builds only)
+#endif
 
 #ifdef BIALIGN_WPE  // experiment: cap the affine sweep's registers so that this many waves fit a SIMD
 #define BIALIGN_WPE_ATTR __attribute__((amdgpu_waves_per_eu(BIALIGN_WPE, BIALIGN_WPE)))

@@ -67,6 +67,12 @@ constexpr int UNROLL = 64, ITER = 4096;
 #define ADD_WAIT(a, b) asm volatile("v_add_u32 %0, %0, %1\n\ts_waitcnt lgkmcnt(0)" : "+v"(a) : "v"(b));
 #define SALU_ONLY(a, b) asm volatile("s_add_u32 s20, s20, 1" : : : "s20", "scc");
 #define ADD_E64(a, b) asm volatile("v_add_u32_e64 %0, %0, %1" : "+v"(a) : "v"(b));
+// the full and 64-bit multiplies of address arithmetic (a record number times a record size; a division by a constant):
+// what the ghost feed's general path spends per lane and round, and its steady-block path does not
+#define MAD_U64_U32(a, b) asm volatile("v_mad_u64_u32 %0, s[20:21], %1, %1, %0" : "+v"(a##w) : "v"(b) : "s20", "s21");
+#define MAD_I64_I32(a, b) asm volatile("v_mad_i64_i32 %0, s[20:21], %1, %1, %0" : "+v"(a##w) : "v"(b) : "s20", "s21");
+#define MUL_HI_I32(a, b) asm volatile("v_mul_hi_i32 %0, %0, %1" : "+v"(a) : "v"(b));
+#define MUL_LO_U32(a, b) asm volatile("v_mul_lo_u32 %0, %0, %1" : "+v"(a) : "v"(b));
 
 #define KERNEL(NAME, OP)                                                                         \
   __global__ void __launch_bounds__(256) NAME(int* out, long long* cyc, int seed) {              \
@@ -143,6 +149,10 @@ KERNEL(k_mix_add_max, MIX_ADD_MAX)
 KERNEL(k_mix_add_max3, MIX_ADD_MAX3)
 KERNEL(k_mix_sgpr, MIX_SGPR)
 KERNEL(k_add_e64, ADD_E64)
+KERNEL(k_mad_u64_u32, MAD_U64_U32)
+KERNEL(k_mad_i64_i32, MAD_I64_I32)
+KERNEL(k_mul_hi_i32, MUL_HI_I32)
+KERNEL(k_mul_lo_u32, MUL_LO_U32)
 KERNEL(k_add_salu, ADD_SALU)
 KERNEL(k_max3_salu, MAX3_SALU)
 KERNEL(k_max3_salu2, MAX3_SALU2)
@@ -172,7 +182,8 @@ int main() {
       {"v_mov_b64", k_mov_b64}, {"v_subrev_co_u32", k_subrev_co}, {"v_mad_i32_i24", k_mad_i24},
       {"v_add_u32 sgpr", k_add_sgpr}, {"v_add_u32 inline", k_add_inl}, {"v_add_u32 literal", k_add_lit}, {"v_max3 sgpr", k_max3_sgpr},
       {"add,max (x2)", k_mix_add_max}, {"add,add,add,max3 (x4)", k_mix_add_max3}, {"addS,addS,add,max3(x4)", k_mix_sgpr},
-      {"v_add_u32_e64", k_add_e64}, {"pair: v_add + s_add", k_add_salu}, {"pair: v_max3 + s_add", k_max3_salu},
+      {"v_add_u32_e64", k_add_e64}, {"v_mad_u64_u32", k_mad_u64_u32}, {"v_mad_i64_i32", k_mad_i64_i32},
+      {"v_mul_hi_i32", k_mul_hi_i32}, {"v_mul_lo_u32", k_mul_lo_u32}, {"pair: v_add + s_add", k_add_salu}, {"pair: v_max3 + s_add", k_max3_salu},
       {"trio: v_max3+s_add+s_and", k_max3_salu2}, {"pair: v_add + s_nop", k_add_nop}, {"pair: v_add + s_waitcnt", k_add_wait},
       {"s_add_u32 alone", k_salu_only},
       {"v_add_u32 exec=5 lanes", k_add_exec5}, {"v_add_u32 exec=16 lanes", k_add_exec16}, {"v_add_u32 exec=32 lanes", k_add_exec32},
