@@ -673,6 +673,7 @@ static int create_batch(bialign_engine* eng, const bialign_params* prm, const bi
     d.NS = d.P = d.G = 0;
     if (!b->wide) sweep_geometry(geo, n, m, &d.NS, &d.P, &d.G);
     d.trace_cap = 2 * (n + m) + 2;
+    if (const char* e = getenv("BIALIGN_TRACE_CAP")) d.trace_cap = std::min(d.trace_cap, std::max(1, atoi(e)));  // tests: the clip
     d.seq_a = pr->off_a[p];
     d.seq_b = pr->off_b[p];
     d.trace_off = b->trace_bytes;

@@ -530,10 +530,50 @@ int launch_traceback_kernel(const bialign_batch* b, void (*kern)(P...), bool do_
   return launch(kern, dim3(count), dim3(64), do_trace ? b->lds_trace : 0, b->eng->stream, w, count);
 }
 
+// traceback_affine_fast_kernel (bialign_trace_fast.hpp) exists for the walk over packed records with LOOKUP scores
+constexpr bool traceback_fast_exists(int S, unsigned F) { return F == (T_TRACE | T_PACK) && traceback_exists(true, S, F); }
+// ... and admits a pair whose storage stays below 2^31 dwords and whose two-strip window of packed records stays below
+// 2^32 bytes: its cell addresses are 32-bit byte offsets from the record 0 of the strip above the walk's
+template <int S>
+bool trace_fast_admits(const PairDesc& d) {
+  using TF = TraceFast<S>;
+  return Pack<S>::pair_dwords(d.G, d.P, d.m) < (int64_t(1) << 31) &&
+         (2 * (int64_t)d.P + Geo<S>::MAXOFF + TF::W + 2) * TF::RECB < (int64_t(1) << 32);
+}
+// LDS of a launch of the fast kernel: the staged inputs, the candidate table, and the trace buffer -- the longest trace
+// of the launch if the workgroup can spare it (BIALIGN_TRACE_LDS: tests, a smaller buffer), else flushed in pieces.
+// 0: the generic kernel serves (BIALIGN_TRACE_FAST=0: tests / A-B; dense mu2; a pair not admitted).
+constexpr int TRACE_FAST_TBUF_MAX = 16 * 1024;
+template <int S>
+size_t trace_fast_lds(const bialign_batch* b, int first, int count, int* tbuf) {
+  const char* sw = getenv("BIALIGN_TRACE_FAST");  // "0": tests / A-B, the generic kernel only
+  if ((sw && atoi(sw) == 0) || b->dense || b->dense1 || b->wide || b->lean) return 0;
+  int cap = 0;
+  for (int t = first; t < first + count; ++t) {
+    const PairDesc& d = b->pairs[b->order[t]];
+    if (!trace_fast_admits<S>(d)) return 0;
+    cap = std::max(cap, d.trace_cap);
+  }
+  int want = std::min((cap + 63) & ~63, TRACE_FAST_TBUF_MAX);
+  if (const char* e = getenv("BIALIGN_TRACE_LDS")) want = std::min(want, std::max(64, atoi(e) & ~63));
+  const size_t fixed = ((b->lds_trace + 15) & ~size_t(15)) + TraceFast<S>::TAB_BYTES;
+  if (fixed + 64 > 160 * 1024) return 0;
+  *tbuf = (int)std::min<size_t>(want, (160 * 1024 - fixed) & ~size_t(63));
+  return fixed + *tbuf;
+}
+
 template <int S>
 int launch_traceback_affine(const bialign_batch* b, const DeviceBatch& v, int first, int count, bool do_trace) {
   return with_flags<T_TRACE | T_PACK | T_DENSE1>(trace_flags(b, do_trace), [&](auto flags) -> int {
     constexpr unsigned F = decltype(flags)::value;
+    if constexpr (traceback_fast_exists(S, F)) {
+      int tbuf = 0;
+      if (const size_t lds = trace_fast_lds<S>(b, first, count, &tbuf)) {
+        DeviceBatch w = v;
+        w.order = v.order + first;
+        return launch(traceback_affine_fast_kernel<S>, dim3(count), dim3(64), lds, b->eng->stream, w, count, tbuf);
+      }
+    }
     if constexpr (traceback_exists(true, S, F)) return launch_traceback_kernel(b, traceback_affine_of<S, F>(), do_trace, v, first, count);
     else return fail(BIALIGN_E_UNSUPPORTED, "no affine traceback for max_shift %d in form %u", S, F);
   });

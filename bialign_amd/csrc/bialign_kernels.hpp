@@ -65,4 +65,5 @@
 #include "bialign_fill_linear.hpp"
 #include "bialign_wide.hpp"
 #include "bialign_traceback.hpp"
+#include "bialign_trace_fast.hpp"
 #include "bialign_dump.hpp"

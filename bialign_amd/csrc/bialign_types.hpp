@@ -229,7 +229,56 @@ struct Pack {
   }
 };
 
-// Layer value (state st) of lattice point (i, j, aa, bb) of a pair swept with packed records.
+// Where layer value (state st) of lattice point (i, j, aa, bb) lives in a pair swept with packed records: dwords from
+// the start of the pair's storage (layers + pd.layer_off): packed_cell's address arithmetic on its own.  The short-chain
+// traceback's side path loads through it, and tests/trace_fast_check.hip proves that kernel's incremental addresses
+// against it.
+struct PackedAddr {
+  bool packed;      // the point's step is interior: a packed record; else a full record, and only `dw` counts
+  bool corner;      // packed: a can_be_empty position, offset 0xffff there means -2^30
+  bool anchor;      // packed: the value the base is taken from (base + 0x8000, no halfword of its own)
+  int half;         // packed: which half of dword `hdw` holds the value's halfword
+  int64_t dw;       // packed: the lane record's base dword; full record: the value's dword
+  int64_t hdw;      // packed: the dword of the value's halfword (anchor: as dw)
+};
+template <int S>
+__host__ __device__ inline PackedAddr packed_addr(const PairDesc& pd, int i, int j, int aa, int bb, int st) {
+  using PK = Pack<S>;
+  constexpr int W = 2 * S + 1, RR = Geo<S>::RR;
+  const int strip = i / RR, il = i - strip * RR + 1;
+  const int t = j + 2 * il + aa, over = t >= pd.P ? 1 : 0;
+  const int slot = (il - 1) * W + aa;
+  PackedAddr a{};
+  if (PK::interior(strip + over, t - over * pd.P, pd.m)) {
+    const int v = bb * 9 + st, h = PK::hw(v);
+    const int64_t rec = ((int64_t)strip * pd.P + t) * PK::RECDW;
+    a.packed = true;
+    a.corner = pack_corner(W, st, bb);
+    a.anchor = v == PK::ANCHOR;
+    a.half = h & 1;
+    a.dw = rec + slot * 4;
+    a.hdw = a.anchor ? a.dw : rec + PK::dwpos(slot, h >> 1);
+    return a;
+  }
+  a.dw = (int64_t)pd.G * PK::RECDW + PK::bidx(strip + over, t - over * pd.P, pd.P, pd.m) * Rec<S, 9>::RECDW +
+         Rec<S, 9>::dword(0, slot, bb * 9 + st);
+  a.hdw = a.dw;
+  return a;
+}
+// ... and the value there, `base` being the start of the pair's storage
+template <int S>
+__host__ __device__ inline int packed_load(const int32_t* base, const PackedAddr& a) {
+  if (!a.packed) return base[a.dw];
+  const int b = base[a.dw];  // both loads issued together: one memory round trip per cell
+  if (a.anchor) return b + 0x8000;
+  const uint32_t word = (uint32_t)base[a.hdw];
+  const uint32_t e = Pack<S>::offset_of(a.half ? word >> 16 : word & 0xffffu, b);
+  return (a.corner && e == 0xffffu) ? NEG : b + (int)e;
+}
+
+// Layer value (state st) of lattice point (i, j, aa, bb) of a pair swept with packed records.  (The generic tracebacks
+// and the dump keep this form, and with it their device code, instruction for instruction; tests/trace_fast_check.hip
+// proves it equal to packed_load(packed_addr()) on every in-band cell.)
 template <int S>
 __host__ __device__ inline int packed_cell(const int32_t* layers, const PairDesc& pd, int i, int j, int aa, int bb, int st) {
   using PK = Pack<S>;

@@ -16,12 +16,23 @@ exec-mask skip first (some lane is active as a rule), else fall-through first --
 of wait_block's ladder it takes one rung, and it may include the few instructions of the range check that runs every
 16 steps.
 For a boundary path the script also prints its two sections: the unpack (first ds_read_b128 .. last ds_write_b128) and
-the DMA section (what follows the unpack up to the last DMA's m0 restore), and every 64-bit / full multiply on the path."""
+the DMA section (what follows the unpack up to the last DMA's m0 restore), and every 64-bit / full multiply on the path.
+
+    python tools/isa_hot_path.py --traceback k.s [kernel-name-substring] [top-N]
+
+Traceback mode: the column loop of an affine traceback kernel (default: traceback_affine_fast_kernelILi1E; the generic
+one is traceback_affine_kernelILi1ELb1ELb0ELb0ELb1ELb0ELb0E) is the depth-1 loop that holds the pick's v_readlane.  One
+path is printed, the common one of a column: through the candidates' global loads and the pick, with no 64-bit multiply-add
+where the loop has a path without one (the short-chain kernel's side path through full records divides and multiplies in
+64 bits; the generic kernel does so in every column) and without the trace buffer's flush."""
 import collections, re, sys
 
 sys.setrecursionlimit(100000)
+TRACEBACK = "--traceback" in sys.argv
+if TRACEBACK:
+    sys.argv.remove("--traceback")
 src = open(sys.argv[1]).read().split("\n")
-want = sys.argv[2] if len(sys.argv) > 2 else "fill_affine_slim_kernelILi1ELi3ELi4ELb0E"
+want = sys.argv[2] if len(sys.argv) > 2 else ("traceback_affine_fast_kernelILi1E" if TRACEBACK else "fill_affine_slim_kernelILi1ELi3ELi4ELb0E")
 top = int(sys.argv[3]) if len(sys.argv) > 3 else 14
 
 start = next((i for i, l in enumerate(src) if re.match(r"^_Z\w+:", l) and want in l), None)
@@ -93,16 +104,21 @@ for name in order:
         blocks[name] = blocks[name]._replace(loop=(name[2:], hdr_depth[name[2:]]))
 
 valu = lambda ops: sum(1 for o in ops if o.startswith("v_"))
+DEPTH = 1 if TRACEBACK else 2
 per_loop = collections.Counter()
 for name in order:
     b = blocks[name]
-    if isinstance(b.loop, tuple) and b.loop[1] == 2:
+    if isinstance(b.loop, tuple) and b.loop[1] == DEPTH:
         per_loop[b.loop[0]] += valu(b.ops)
+if TRACEBACK:  # the column loop: the one with the pick
+    picks = {blocks[n].loop[0] for n in order if isinstance(blocks[n].loop, tuple) and blocks[n].loop[1] == 1 and
+             any(o.startswith("v_readlane") for o in blocks[n].ops)}
+    per_loop = collections.Counter({k: v for k, v in per_loop.items() if k in picks})
 if not per_loop:
-    sys.exit("no depth-2 loop in this kernel")
+    sys.exit(f"no depth-{DEPTH} loop in this kernel")
 head = max(per_loop, key=per_loop.get)
-print(f"interior step loop: {head}  ({per_loop[head]} vector instructions in its blocks; depth-2 loops: {dict(per_loop)})")
-inside = {n for n in order if blocks[n].loop == (head, 2)}
+print(f"{'column' if TRACEBACK else 'interior step'} loop: {head}  ({per_loop[head]} vector instructions in its blocks; depth-{DEPTH} loops: {dict(per_loop)})")
+inside = {n for n in order if blocks[n].loop == (head, DEPTH)}
 HEAD = ".L" + head
 
 RARE = ("global_atomic", "s_sleep", "flat_load", "flat_store")
@@ -175,6 +191,13 @@ def report(title, path, sections):
 
 
 rare = lambda o: o.startswith(RARE)
+if TRACEBACK:
+    need = {"load": lambda o: o.startswith("global_load"), "pick": lambda o: o.startswith("v_readlane")}
+    wide = lambda o: o.startswith(("v_mad_i64", "v_mul_hi"))  # a division, a 64-bit product
+    flush = lambda o: o.startswith(("global_store_byte", "s_barrier")) and "fast" in want
+    path = find_path(lambda o: rare(o) or wide(o) or flush(o), need) or find_path(lambda o: rare(o) or flush(o), need)
+    report("per-column common path", path, False)
+    sys.exit(0)
 report("per-step hot path", find_path(lambda o: rare(o) or is_dma(o) or is_wait(o), {}), False)
 loop_ops = [o for n in inside | {HEAD} for o in blocks[n].ops]
 if any(is_steady_dma(o) for o in loop_ops):
