@@ -232,6 +232,25 @@ struct GhostFeed {
   }
 };
 
+// Ghost source of fill_affine_slim_kernel's interior steps (BIALIGN_STEP_SCALAR): the LDS byte address a lane reads its
+// stored layers from is  factor(lane) * ring_step_byte(g) + lane_byte(lane)  relative to the wave's ring for live lanes
+// (their (step, a) entry), and the sentinel block for the others.  `sent_rel` is that block's address, ring-relative
+// or absolute as long as ring_step_byte's base is of the same kind.
+template <int S, bool LEAN>
+struct GhostSrc {
+  using GF = GhostFeed<S, 9, LEAN, 0>;
+  static constexpr int W = 2 * S + 1, R = 64 / W;
+  static constexpr int STEPB = W * GF::NP * 16;    // bytes from one step's entries to the next
+  static constexpr int HALFB = GF::SLOTS * 16;     // bytes of a ring half
+  __host__ __device__ static inline uint32_t ring_step_byte(int g) {
+    return (uint32_t)(((g / GF::BLK) & 1) * HALFB + (g & (GF::BLK - 1)) * STEPB);
+  }
+  __host__ __device__ static inline uint32_t factor(int lane) { return lane < R * W ? 1u : 0u; }
+  __host__ __device__ static inline uint32_t lane_byte(int lane, uint32_t sent) {
+    return lane < R * W ? (uint32_t)((lane % W) * GF::NP * 16) : sent;
+  }
+};
+
 // LDS dwords of fill_affine_slim_kernel's table of steady-block lane offsets (one per workgroup; the LEAN form leaves
 // it unused).  The host sizes the workgroup's LDS with it (sweep_info_of).
 template <int S>

@@ -163,6 +163,30 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
   const uint32_t ring_lds = __builtin_amdgcn_readfirstlane(
       (uint32_t)(uintptr_t)(__attribute__((address_space(3))) int32_t*)smem) + wv * GF::RING_DW * 4;
 
+  // ---- interior steps (BIALIGN_STEP_SCALAR): what is wave-uniform there stays in scalar registers.  Every lane of an
+  // interior step is in lane 0's strip, so the step's record is one scalar base (StepAddr: + RECB per step) and a store
+  // goes to base + lane constant + immediate; the ghost source is the ring offset of (half, step in block) times a 0/1
+  // lane factor plus a lane constant (GhostSrc); lane 0's phase and strip have scalar mirrors for the interior test.
+  constexpr bool STEP_SCALAR = BIALIGN_STEP_SCALAR;
+  using SA = StepAddr<S, LEAN>;
+  using GS = GhostSrc<S, LEAN>;
+  typedef const __attribute__((address_space(3))) int32_t* lds_cptr;
+  typedef __attribute__((address_space(1))) char* gbl_ptr;  // (global, said outright: the base passes through integers)
+  typedef __attribute__((address_space(1))) v4i* gbl_v4i;
+  typedef __attribute__((address_space(1))) int32_t* gbl_i32;
+  uint32_t st_off = 0, st_toff = 0, gs_fac = 0, gs_lane = 0;  // (laundered like the predicates above: never re-derived)
+  if (STEP_SCALAR) {
+    st_off = SA::chunk_off(L);
+    st_toff = SA::tail_off(L);
+    gs_fac = GS::factor(L);
+    gs_lane = GS::lane_byte(L, ring_lds + (NW - wv) * GF::RING_DW * 4);  // (the sentinel block follows the last wave's ring)
+    asm volatile("" : "+v"(st_off), "+v"(st_toff), "+v"(gs_fac), "+v"(gs_lane));
+  }
+  int s_ph = 0, s_q = 0;   // lane 0's column and local strip (it starts at column 0: il = aa = 0), advanced with jj / strip
+  int s_adv = 0;           // interior steps since the last boundary step: jj waits at the run's first column meanwhile
+  uint32_t ring_u = 0;     // LDS byte address of this step's ghost entries of band row 0: set per block, + STEPB per step
+  gbl_ptr sbase = nullptr;  // the interior step's record: set at the end of every boundary step, + RECB per step
+
   // ---- team protocol (as fill_affine_kernel, in-workgroup form)
   int blk_q = 0, blk_rem = 0;  // (next block start) div / mod P
   int seen_prog = -0x40000000;  // the partner's progress as last read (INT_MAX once a hand-off has timed out: no further waits)
@@ -217,16 +241,20 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
 #pragma unroll
     for (int bb = 0; bb < W; ++bb) mu2n[bb] = s2[s2row + cb[jc + bb]];
   };
-  auto fetch_codes = [&]() __attribute__((always_inline)) {
-    const int jc1 = min(max(jj + 1, 0), m + 1);
+  auto fetch_codes = [&](auto clamp_tag) __attribute__((always_inline)) {
+    const int jc1 = decltype(clamp_tag)::value ? min(max(jj + 1, 0), m + 1) : jj + s_adv + 1;
     sbn = sb[jc1 - 1 + PADB];
     cbn = cb[jc1 + W - 1];
   };
   lookup_mu();
-  fetch_codes();
+  fetch_codes(BoolTag<true>{});
 
   auto step = [&](auto interior_tag, int g) __attribute__((always_inline)) {
     constexpr bool INTERIOR = decltype(interior_tag)::value;
+    if (STEP_SCALAR && !INTERIOR) {  // the columns of the interior run that has just ended
+      jj += s_adv;
+      s_adv = 0;
+    }
     // ---- 0. ghost feed, block boundary work
     const int gt = g & (GF::BLK - 1), ghalf = (g / GF::BLK) & 1;
     if (gt == 0) {
@@ -241,7 +269,8 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
         if (L < GF::BLK * W) {
           bool packed = true;  // a steady block: every entry is a packed record
           if (!(FEED_FAST && blk_steady)) {
-            const int c0 = __builtin_amdgcn_readfirstlane(jj), q0 = __builtin_amdgcn_readfirstlane(strip);
+            const int c0 = STEP_SCALAR ? s_ph : __builtin_amdgcn_readfirstlane(jj);
+            const int q0 = STEP_SCALAR ? s_q : __builtin_amdgcn_readfirstlane(strip);
             int ph = c0 + L / W, qst = q0 * T + w;
             if (ph >= P) { ph -= P; qst += T; }
             const int ts = ph + 2 * (R - 1), over = ts >= P ? 1 : 0;
@@ -274,6 +303,7 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
       }
       prefetch_block(g + GF::BLK, ghalf ^ 1);
       vm_younger = 0;
+      if (STEP_SCALAR) ring_u = ring_lds + ghalf * GS::HALFB;
       if (A.prio_mode) {  // rotate four priority levels over the workgroups of a CU by age (fill_affine_kernel)
         const int lvl = ((g >> 7) + (wv >> 2)) & 3;  // (waves wv, wv + 4, wv + 8 share a SIMD)
         if (lvl == 0) __builtin_amdgcn_s_setprio(0);
@@ -285,6 +315,19 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
     // where this lane's stored layers lie in LDS: its (step, a) entry of the ring, or the sentinel block (lane 63)
     const int32_t* const gsrc = live ? reinterpret_cast<const int32_t*>(ring + ghalf * GF::SLOTS + (gt * W + aa) * GF::NP)
                                      : sentblk;
+    // ... in an interior step (BIALIGN_STEP_SCALAR) as one VALU: the step's scalar ring address through the lane's 0/1
+    // factor, plus the lane constant (a * NP * 16, or the sentinel block's address)
+    // (written out: left to itself hipcc multiplies up here and adds inside the ring-fed lanes' branch)
+    uint32_t gaddr = 0;
+    if (STEP_SCALAR && INTERIOR) asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(gaddr) : "v"(gs_fac), "s"(ring_u), "v"(gs_lane));
+    const lds_cptr gsrc_s = (lds_cptr)(uintptr_t)gaddr;
+    // a store's lane offset, laundered at the store (in place: a laundered copy costs a move): extended to 64 bits
+    // anywhere else -- outside the loop, or in another block of the step -- it is added to the base per lane instead of
+    // riding in the store's 32-bit offset operand
+    auto at_store = [](uint32_t& off) __attribute__((always_inline)) -> uint32_t {
+      asm volatile("" : "+v"(off));
+      return off;
+    };
 
     // ---- 1. lane L-1 = (i, a-1) hands its values over in registers: DPP wave shift fused with the cap (s_nop 1: the
     //         wait states a DPP read needs, see fill_affine_kernel)
@@ -414,7 +457,7 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
       if (INTERIOR) {
         if (ringfed) {
 #pragma unroll
-          for (int q = 0; q < 9; ++q) M[q] = gsrc[bb * 9 + q];
+          for (int q = 0; q < 9; ++q) M[q] = STEP_SCALAR ? gsrc_s[bb * 9 + q] : gsrc[bb * 9 + q];
         } else {
           int Tv[9];
           cases(Tv);
@@ -452,7 +495,8 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
         for (int q = 0; q < 9; ++q) outv[PACKED ? 0 : bb * 9 + q] = M[q];
       }
       if (LEAN && bb == S) {  // score-only: the end cell (n,m,n,m) is all the host wants (pyx:509)
-        if (live && !ghost && aa == S && i == n && jj == m) {
+        // (an interior step is never at column m; under BIALIGN_STEP_SCALAR its jj is not the column either)
+        if (!(STEP_SCALAR && INTERIOR) && live && !ghost && aa == S && i == n && jj == m) {
           int best = M[0];
 #pragma unroll
           for (int q = 1; q < 9; ++q) best = imax(best, M[q]);
@@ -506,11 +550,16 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
               if (c < PK_::NCH) {
                 v4i v;
                 v.x = dw[0]; v.y = dw[1]; v.z = dw[2]; v.w = dw[3];
-                *reinterpret_cast<v4i*>(dstp + c * R_::CH + slot_ * 4) = v;
+                if (STEP_SCALAR) *reinterpret_cast<gbl_v4i>(sbase + SA::chunk_imm(c) + at_store(st_off)) = v;
+                else *reinterpret_cast<v4i*>(dstp + c * R_::CH + slot_ * 4) = v;
               } else if (slot_ < PK_::TSLOTS) {  // the tail piece: TAILDW dwords per lane
                 int32_t* tp = dstp + PK_::NCH * R_::CH + slot_ * PK_::TAILDW;
+                const gbl_i32 tps = STEP_SCALAR ? reinterpret_cast<gbl_i32>(sbase + SA::TAIL_IMM + at_store(st_toff)) : nullptr;
 #pragma unroll
-                for (int x = 0; x < PK_::TAILDW; ++x) tp[x] = dw[x];
+                for (int x = 0; x < PK_::TAILDW; ++x) {
+                  if (STEP_SCALAR) tps[x] = dw[x];
+                  else tp[x] = dw[x];
+                }
               }
             }
           }
@@ -523,12 +572,17 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
               v4i v;
               v.x = outv[PACKED ? 0 : 4 * c]; v.y = outv[PACKED ? 0 : 4 * c + 1];
               v.z = outv[PACKED ? 0 : 4 * c + 2]; v.w = outv[PACKED ? 0 : 4 * c + 3];
-              *reinterpret_cast<v4i*>(dst + c * R_::CH + slot_ * 4) = v;
+              if (STEP_SCALAR && INTERIOR) *reinterpret_cast<gbl_v4i>(sbase + SA::chunk_imm(c) + at_store(st_off)) = v;
+              else *reinterpret_cast<v4i*>(dst + c * R_::CH + slot_ * 4) = v;
             }
           }
           if (LEAN && bb == W - 1) {
+            const gbl_i32 tp = (STEP_SCALAR && INTERIOR) ? reinterpret_cast<gbl_i32>(sbase + SA::TAIL_IMM + at_store(st_toff)) : nullptr;
 #pragma unroll
-            for (int t = 0; t < TAIL; ++t) dst[NCH4 * R_::CH + slot_ * TAIL + t] = outv[PACKED ? 0 : 4 * NCH4 + t];
+            for (int t = 0; t < TAIL; ++t) {
+              if (STEP_SCALAR && INTERIOR) tp[t] = outv[PACKED ? 0 : 4 * NCH4 + t];
+              else dst[NCH4 * R_::CH + slot_ * TAIL + t] = outv[PACKED ? 0 : 4 * NCH4 + t];
+            }
           }
         }
         if (!LEAN && bb == W - 1) {  // the tail is stored by ALL 64 lanes (Rec::TAILSLOTS)
@@ -639,12 +693,28 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
     inB[W - 1][1] = bperm(addrB, defer[2]);
 
     // ---- advance
-    ++jj;
+    if (STEP_SCALAR && INTERIOR) ++s_adv;  // (every lane's column is jj + s_adv: one scalar add instead of one per lane)
+    else ++jj;
     if (!INTERIOR && jj == P) {  // (an interior step never ends a strip: its phase is at most m - S)
       jj = 0;
       ++strip;
       rec_base += (T - 1) * P;
       set_row(strip);
+    }
+    if (STEP_SCALAR) {  // the scalar mirrors of lane 0's column and strip; the next step's ghost entries; the next record
+      ++s_ph;
+      if (!INTERIOR && s_ph == P) {
+        s_ph = 0;
+        ++s_q;
+      }
+      ring_u += GS::STEPB;
+      if (INTERIOR) {
+        sbase += SA::RECB;
+      } else {  // an interior run may begin with the next step: its record, as a scalar (lane 0's strip is every lane's there)
+        const uint64_t b = (uint64_t)(uintptr_t)(reinterpret_cast<char*>(lay) + SA::record_byte(g + 1, s_q, T, w, P));
+        sbase = reinterpret_cast<gbl_ptr>((uintptr_t)((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32 |
+                                                      (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)b)));
+      }
     }
     if (INTERIOR) {  // same row, next column, inside the molecule: the window slides by one
       mu1n = s1[s1row + sbn];
@@ -654,10 +724,13 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
     } else {
       lookup_mu();
     }
-    fetch_codes();
+    // (an interior step leaves every lane at a column 1 <= jj + 1 <= m + 1: phase <= m - S, see Pack<S>::hi)
+    if (STEP_SCALAR && INTERIOR) fetch_codes(BoolTag<false>{});
+    else fetch_codes(BoolTag<true>{});
   };
 
   auto all_interior = [&]() __attribute__((always_inline)) {
+    if (STEP_SCALAR) return PK_::interior(s_q * T + w, s_ph, m);
     const int c0 = __builtin_amdgcn_readfirstlane(jj), q0 = __builtin_amdgcn_readfirstlane(strip);
     return PK_::interior(q0 * T + w, c0, m);
   };

@@ -51,6 +51,9 @@
 #ifndef BIALIGN_FEED_FAST  // fill_affine_slim_kernel: 1 = steady ghost blocks take GhostFeed::issue_steady (scalar base + lane
 #define BIALIGN_FEED_FAST 1  // constants), 0 = every block recomputes its 3 x 64 source addresses (A/B builds only)
 #endif
+#ifndef BIALIGN_STEP_SCALAR  // fill_affine_slim_kernel, interior steps: 1 = stores go to a scalar record base + lane constants
+#define BIALIGN_STEP_SCALAR 1  // (StepAddr), the ghost source is one v_mad_u32_u24 (GhostSrc), the codes are fetched unclamped
+#endif                         // and the interior test reads scalar mirrors of lane 0's phase and strip; 0 = per lane (A/B builds)
 
 #ifdef BIALIGN_WPE  // experiment: cap the affine sweep's registers so that this many waves fit a SIMD
 #define BIALIGN_WPE_ATTR __attribute__((amdgpu_waves_per_eu(BIALIGN_WPE, BIALIGN_WPE)))

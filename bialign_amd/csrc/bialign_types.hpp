@@ -229,6 +229,48 @@ struct Pack {
   }
 };
 
+// Store addresses of an INTERIOR step of fill_affine_slim_kernel (BIALIGN_STEP_SCALAR), factored so that host code can
+// call both halves (tests/step_addr_check.hip proves them against the sweep's per-lane bookkeeping).  In an interior
+// step every lane of the wave is in the same strip, so the step's record is wave-uniform:
+//     byte address of a store = pair's storage + record_byte(g, q, T, w, P)   -- scalar, + RECB per step
+//                             + chunk_off(lane) | tail_off(lane)              -- lane constants
+//                             + chunk_imm(c)    | TAIL_IMM                    -- immediates
+// Packed records (Pack<S>) in the full-storage form, the bottom row's plain records (Rec<S,9,true>) in the LEAN form.
+template <int S, bool LEAN>
+struct StepAddr {
+  using R_ = Rec<S, 9, LEAN>;
+  using PK_ = Pack<S>;
+  static constexpr int W = 2 * S + 1, R = 64 / W;
+  static constexpr int RECB = (LEAN ? R_::RECDW : PK_::RECDW) * 4;   // bytes from one step's record to the next
+  static constexpr int NCHUNK = LEAN ? R_::NCH4 : PK_::NCH;          // 16-byte chunk stores per lane and step
+  static constexpr int TAILB = (LEAN ? R_::TAIL : PK_::TAILDW) * 4;  // bytes of a lane's tail piece
+  static constexpr int TAIL_IMM = NCHUNK * R_::CH * 4;               // (s=1: 2880, within a global store's immediate)
+  __host__ __device__ static constexpr int chunk_imm(int c) { return c * R_::CH * 4; }
+  // local strip q of wave w (team of T) at local step g: the wave's steps continue the records of strips w, w+T, ...
+  __host__ __device__ static inline int64_t record(int g, int q, int T, int w, int P) {
+    return (int64_t)g + (int64_t)(q * (T - 1) + w) * P;
+  }
+  __host__ __device__ static inline int64_t record_byte(int g, int q, int T, int w, int P) {
+    return record(g, q, T, w, P) * RECB;
+  }
+  // lanes that own storage slots in an interior step, and the slot
+  __host__ __device__ static inline int pad_idx(int lane) { return lane < W ? lane : (lane >= R * W ? W + (lane - R * W) : 64); }
+  __host__ __device__ static inline bool stores(int lane) {
+    const int il = lane / W;
+    return (lane < R * W && (LEAN ? il == R - 1 : il != 0)) || (!LEAN && pad_idx(lane) < R_::SLP - R_::SL);
+  }
+  __host__ __device__ static inline bool stores_tail(int lane) {
+    return stores(lane) && TAILB != 0 && (LEAN || slot(lane) < PK_::TSLOTS);
+  }
+  __host__ __device__ static inline int slot(int lane) {
+    if (LEAN) return lane % W;
+    return pad_idx(lane) < R_::SLP - R_::SL ? R_::SL + pad_idx(lane) : lane - W;
+  }
+  // byte offsets of the lane's chunk slot and of its tail piece (lanes without a slot: 0, they store nothing)
+  __host__ __device__ static inline uint32_t chunk_off(int lane) { return stores(lane) ? (uint32_t)slot(lane) * 16u : 0u; }
+  __host__ __device__ static inline uint32_t tail_off(int lane) { return stores(lane) ? (uint32_t)(slot(lane) * TAILB) : 0u; }
+};
+
 // Where layer value (state st) of lattice point (i, j, aa, bb) lives in a pair swept with packed records: dwords from
 // the start of the pair's storage (layers + pd.layer_off): packed_cell's address arithmetic on its own.  The short-chain
 // traceback's side path loads through it, and tests/trace_fast_check.hip proves that kernel's incremental addresses

@@ -1,10 +1,11 @@
 """Instruction counts along the paths a wave takes through the INTERIOR-STEP loop of a fill kernel's ISA.
 
-    python tools/isa_hot_path.py k.s [kernel-name-substring] [top-N]
+    python tools/isa_hot_path.py [--dump] k.s [kernel-name-substring] [top-N]
 
 k.s is hipcc's -S output (--cuda-device-only) of a translation unit; the kernel is the first one whose symbol contains
-the substring (default: fill_affine_slim_kernelILi1ELi3ELi4ELb0E, the headline's).  The interior-step loop is the depth-2
-loop of that kernel with the most vector instructions (the other depth-2 loops are the spin loops of the team hand-off).
+the substring (default: fill_affine_slim_kernelILi1ELi3ELi4ELb0E, the headline's).  The interior-step loop is a depth-2
+loop of that kernel with at least 100 vector instructions (the others are the spin loops of the team hand-off); where the
+boundary steps form a depth-2 loop of their own (BIALIGN_STEP_SCALAR builds) it is the one with fewer of them.
 
 Two kinds of path from the loop header back to it are printed:
   * the per-step hot path: no ghost-block boundary work (no counted vmcnt wait, no DMA), no rare work;
@@ -12,7 +13,8 @@ Two kinds of path from the loop header back to it are printed:
     Where the loop holds the steady form of the DMAs (scalar base: `global_load_lds_dwordx4 v, s[..]`), the path through
     it is printed first, then the one through the general form (`global_load_lds_dwordx4 v[..], off`).
 A path avoids rare work (error flag, partner wait).  At a branch both ways are tried -- into the guarded block of an
-exec-mask skip first (some lane is active as a rule), else fall-through first -- and the first complete path counts:
+exec-mask skip first (some lane is active as a rule), else fall-through first (the hot path: also the taken way of scalar
+branches first, and the shorter of the two paths) -- and the first complete path counts:
 of wait_block's ladder it takes one rung, and it may include the few instructions of the range check that runs every
 16 steps.
 For a boundary path the script also prints its two sections: the unpack (first ds_read_b128 .. last ds_write_b128) and
@@ -31,6 +33,9 @@ sys.setrecursionlimit(100000)
 TRACEBACK = "--traceback" in sys.argv
 if TRACEBACK:
     sys.argv.remove("--traceback")
+DUMP = "--dump" in sys.argv  # also list the instructions of the per-step hot path, in order
+if DUMP:
+    sys.argv.remove("--dump")
 src = open(sys.argv[1]).read().split("\n")
 want = sys.argv[2] if len(sys.argv) > 2 else ("traceback_affine_fast_kernelILi1E" if TRACEBACK else "fill_affine_slim_kernelILi1ELi3ELi4ELb0E")
 top = int(sys.argv[3]) if len(sys.argv) > 3 else 14
@@ -116,7 +121,11 @@ if TRACEBACK:  # the column loop: the one with the pick
     per_loop = collections.Counter({k: v for k, v in per_loop.items() if k in picks})
 if not per_loop:
     sys.exit(f"no depth-{DEPTH} loop in this kernel")
-head = max(per_loop, key=per_loop.get)
+if TRACEBACK:
+    head = max(per_loop, key=per_loop.get)
+else:  # the sweep's step loops hold hundreds of vector instructions; an interior step is a boundary step less its guards
+    steps = {k: v for k, v in per_loop.items() if v >= 100}
+    head = min(steps, key=steps.get) if steps else max(per_loop, key=per_loop.get)
 print(f"{'column' if TRACEBACK else 'interior step'} loop: {head}  ({per_loop[head]} vector instructions in its blocks; depth-{DEPTH} loops: {dict(per_loop)})")
 inside = {n for n in order if blocks[n].loop == (head, DEPTH)}
 HEAD = ".L" + head
@@ -127,7 +136,7 @@ is_steady_dma = lambda o: is_dma(o) and re.search(r"v\d+, s\[", o) is not None
 is_wait = lambda o: o.startswith("s_waitcnt vmcnt(") and "lgkmcnt" not in o
 
 
-def find_path(forbid, need):
+def find_path(forbid, need, taken_first=False):
     """First path header -> header (depth first, in the order above) whose blocks hold no forbidden
     instruction and that holds at least one instruction of every kind in `need`."""
     dead = set()
@@ -145,7 +154,7 @@ def find_path(forbid, need):
         succ = list(b.succ)
         if last == "s_cbranch_execnz" and len(succ) == 2:
             succ = [succ[0], succ[1]]   # some lane is active as a rule: into the guarded block first
-        elif len(succ) == 2:
+        elif len(succ) == 2 and not (taken_first and last.startswith(("s_cbranch_scc", "s_cbranch_vcc"))):
             succ = [succ[1], succ[0]]   # fall-through first (for s_cbranch_execz: into the guarded block)
         for s in succ:
             if s == HEAD:
@@ -176,6 +185,8 @@ def report(title, path, sections):
         print(f"  {c:4d} {o}")
     mul = collections.Counter(n for n in names if n.startswith(("v_mad_u64", "v_mad_i64", "v_mul_")))
     print("  multiplies on the path:", dict(mul) if mul else "none")  # (a boundary path holds the step's own as well)
+    if DUMP and not sections:
+        print("\n".join("    | " + o for o in ops))
     if sections:
         rd = [i for i, n in enumerate(names) if n == "ds_read_b128"]
         wr = [i for i, n in enumerate(names) if n == "ds_write_b128"]
@@ -198,7 +209,11 @@ if TRACEBACK:
     path = find_path(lambda o: rare(o) or wide(o) or flush(o), need) or find_path(lambda o: rare(o) or flush(o), need)
     report("per-column common path", path, False)
     sys.exit(0)
-report("per-step hot path", find_path(lambda o: rare(o) or is_dma(o) or is_wait(o), {}), False)
+# (the skip around the block-boundary work is a scalar branch either way round: both orders are tried, the shorter path
+#  through a step's body -- its stores and its exchange -- is the step that does none of it)
+step_body = {"store": lambda o: o.startswith("global_store"), "exchange": lambda o: o.startswith("ds_bpermute")}
+hot = [p for p in (find_path(lambda o: rare(o) or is_dma(o) or is_wait(o), step_body, tf) for tf in (False, True)) if p]
+report("per-step hot path", min(hot, key=lambda p: sum(len(blocks[n].ops) for n in p)) if hot else None, False)
 loop_ops = [o for n in inside | {HEAD} for o in blocks[n].ops]
 if any(is_steady_dma(o) for o in loop_ops):
     report("block-boundary path, steady block",
