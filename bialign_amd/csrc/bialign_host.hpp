@@ -7,9 +7,9 @@
 // traceback_exists), and one ladder per recurrence picks the launch for a team shape.
 //   The launchers are templates on max_shift; each (max_shift, kind) is instantiated in its own translation unit
 // (bialign_inst.hip, compiled once per -DBIALIGN_TU_S / -DBIALIGN_TU_KIND) so that the kernels build in parallel;
-// bialign_capi.hip only dispatches.
+// bialign_capi.hip only dispatches.  What a batch IS on the host -- its plan -- lives in bialign_plan.hpp (BatchPlan).
 #pragma once
-#include "bialign_kernels.hpp"
+#include "bialign_plan.hpp"
 
 #include <algorithm>
 #include <cstdarg>
@@ -23,13 +23,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "../../include/bialign.h"
-
-#define BIALIGN_MAX_SHIFT_PACKED 3  // packed layer records (Pack<S>) are instantiated for max_shift 1..3
-
 namespace bialign {
-
-int fail(int code, const char* fmt, ...);  // records the message bialign_last_error() returns
 
 #define HIP_TRY(expr)                                                                 \
   do {                                                                                \
@@ -88,22 +82,8 @@ struct bialign_engine {
   DevBuf<int32_t> tab_cache;     // FEATURE-form batches: the per-chunk mu2 table buffer of the last one, kept likewise
 };
 
-struct bialign_batch {
+struct bialign_batch : bialign::BatchPlan {  // the plan (bialign_plan.hpp), and what lives on the device
   bialign_engine* eng = nullptr;
-  bialign_params prm{};
-  int affine = 0, NL = 1, S = 0;
-  int npairs = 0;
-  std::vector<PairDesc> pairs;      // host mirror (layer_off valid for the pair's chunk)
-  std::vector<int32_t> order;       // chunk-by-chunk launch order
-  std::vector<int> chunk_begin;     // index into order, size nchunks+1
-  int64_t cells = 0, trace_bytes = 0, max_chunk_dwords = 0;
-  size_t lds_bytes = 0;                   // dynamic LDS of a one-wave workgroup
-  size_t lds_base = 0, lds_per_wave = 0;  // team launches: lds_base + T * lds_per_wave
-  size_t lds_diet8 = 0;                   // eight-wave workgroups of the s=2 affine kernel (DIET layout)
-  // fill_affine_slim_kernel (bialign_fill_slim.hpp): twelve ghost rings + tables, and per pair of the workgroup its codes
-  size_t lds_slim_base = 0, lds_slim_codes = 0;
-  size_t lds_slim(int tw) const { return lds_slim_base + (size_t)(12 / tw) * lds_slim_codes; }
-  size_t lds_trace = 0;                   // tracebacks: score tables + sequence codes
   DevBuf<PairDesc> d_pairs;
   DevBuf<int32_t> d_order, d_s1, d_s2, d_layers, d_scores, d_tlen, d_complete, d_err, d_prog;
   int last_team = 1;  // waves per pair of the last fill launch (negative: cross-CU team)
@@ -117,70 +97,42 @@ struct bialign_batch {
   int recovered = 0;       // runs repeated after a hand-off timeout
   int xcu_spin_limit = 1 << 20;  // polls before a cross-CU wave gives up (~1 s); BIALIGN_XCU_SPIN_LIMIT: tests
   uint32_t pending_flags = 0;
-  // Packed records (Pack<S>, bialign_types.hpp): decided per batch at creation (affine, max_shift 1 or 2, LOOKUP,
-  // full storage, beta <= 0, every pair long enough that most steps are interior); dropped for good when a sweep
-  // meets an offset that does not fit 16 bits (device flag bit 2 -> the run is repeated with full records).
-  bool pack = false, pack_failed = false;
-  bool used_pack = false;       // a fill launch of the pending / last run stored packed records
+  bool used_pack = false;       // a fill launch of the pending / last run stored packed records (BatchPlan::pack)
   bool packed_layers = false;   // ... and so did the launch whose layers are in the buffer now
-  bool pack_now() const { return pack && !pack_failed; }
-  bool packed_sizing = false;          // chunks and pair offsets were planned with the packed sizes
-  std::vector<int64_t> full_dwords;    // per pair: dwords of its full-record form (for the fallback's re-plan)
   DevBuf<uint8_t> d_seq_a, d_cls_a, d_seq_b, d_cls_b, d_trace;
   DevBuf<int32_t> d_tab;  // dense forms: all pairs' n x m tables (per pair mu2's, then mu1's; PairDesc::tab_off)
   DevBuf<int32_t> d_wide_ring;  // wide-band affine sweep: derived values of the last levels (bialign_wide.hpp)
   DevBuf<int64_t> d_wide_off;   // ... per pair of a launch: offset of its ring
-  bool dense = false;       // mu2 in DENSE form (also set for the FEATURE form: its consumers are the DENSE ones)
   // FEATURE form of mu2 (bialign_batch_create_features, bialign_mu2_build.hpp): per-residue doubles in HBM, d_tab is
   // per-chunk scratch the builder kernel fills ahead of each chunk's sweep; PairDesc::tab_off is chunk-relative.
-  bool feat = false;
-  int32_t feat_sw = 0;
   DevBuf<double> d_feat_a, d_feat_b;   // three planes each (up, down, unp), feat_tot_a / feat_tot_b doubles per plane
   int64_t feat_tot_a = 0, feat_tot_b = 0;
-  std::vector<int64_t> tab_dwords;     // per pair: table dwords in the chunk buffer (n*m; twice with a dense mu1 riding along)
-  int64_t max_chunk_tab_dwords = 0;    // table dwords of the largest chunk
   DevBuf<int32_t> d_mu1;               // a dense mu1 next to feature mu2: its tables stay resident here, pair after pair,
   DevBuf<int64_t> d_mu1_off;           // ... and the builder copies a chunk's behind the mu2 tables it writes
   std::vector<hipEvent_t> build_evs;   // two per chunk, around the builder's launch
   double build_ms = 0;                 // HIP-event time of the builder launches of the last run (not part of fill_ms)
   int build_launches = 0;
-  // Null batch (bialign_batch_create_null, bialign_null.hpp): npairs above counts the VIRTUAL pairs, null_npairs real pairs x
-  // null_R replicas, pair-major; d_seq_b / d_cls_b are the replica buffers the shuffle kernel fills ahead of a run's sweeps
-  // from the uploaded B codes kept in d_null_seq / d_null_cls (real pair p's at d_null_off[p]).
-  int null_R = 0, null_npairs = 0;  // null_R == 0: not a null batch
-  uint32_t null_seed = 0;
+  // Null batch (bialign_batch_create_null, bialign_null.hpp): d_seq_b / d_cls_b are the replica buffers the shuffle kernel
+  // fills ahead of a run's sweeps from the uploaded B codes kept in d_null_seq / d_null_cls (real pair p's at d_null_off[p]).
   DevBuf<uint8_t> d_null_seq, d_null_cls;
   DevBuf<int64_t> d_null_off;
   // FEATURE-form null batch (bialign_batch_create_null_features): d_feat_b holds the replica planes (feat_tot_b = R * sum of
   // len_b doubles per plane, indexed by the virtual pairs' seq_b like d_seq_b), shuffle_features_kernel fills them and
   // d_seq_b from the uploaded B features kept here, three planes of d_null_seq.n doubles; d_cls_b stays zero.
   DevBuf<double> d_null_feat;
-  int null_max_m = 0;                       // longest B of the batch: sizes the shuffle's index array in LDS
   // DENSE-form null batch (bialign_batch_create_null_dense): the real pairs' tables stay resident in d_null_tab (pair p's
   // at d_null_tab_off[p]: mu2's, then mu1's), d_null_perm holds every replica's permutation (uint16, indexed by the virtual
   // pairs' seq_b like d_seq_b; shuffle_index_kernel fills it), and d_tab is per-chunk scratch as in FEATURE form:
   // permute_tables_kernel writes each chunk's tables there ahead of its sweep; tab_dwords, max_chunk_tab_dwords, build_evs,
-  // build_ms and build_launches above serve it likewise.
-  bool null_dense = false;
+  // build_ms and build_launches serve it likewise.
   DevBuf<int32_t> d_null_tab;
   DevBuf<int64_t> d_null_tab_off;
   DevBuf<uint16_t> d_null_perm;
-  bool tab_scratch() const { return feat || null_dense; }  // d_tab is per-chunk scratch inside the chunk plan
   DevBuf<int32_t> d_null_obs;               // observed scores of the last bialign_batch_get_null_stats
   DevBuf<bialign_null_stats> d_null_stats;  // ... and its result
   hipEvent_t null_evs[4] = {nullptr, nullptr, nullptr, nullptr};  // around the shuffle launch of a run, around the reduction
   double shuffle_ms = 0, stats_ms = 0;      // HIP-event times (not part of fill_ms)
-  bool dense1 = false;      // mu1 in DENSE form (kernels with DENSE1 / D1 set; no packed records, no slim or diet sweeps)
-  bool wide = false;        // max_shift above the tiled kernels: anti-diagonal path (bialign_wide.hpp), reference-order layers
-  bool lean = false;        // LEAN records: the sweep keeps only the strip-bottom rows
-  bool lean_trace = false;  // ... and tracebacks re-sweep one strip at a time into a scratch area
-  // Level-checkpointed traceback of the wide-band path (BIALIGN_BATCH_LEVEL_TRACE, bialign_wide.hpp): `lean` is set too
-  // (no full layers); a pair's region holds checkpoints, the scratch of one segment of wide_seg levels, and the ring.
-  bool level_trace = false;
-  int wide_seg = 0;
   DevBuf<TraceState> d_tstate;
-  int resw_k = 1;           // strips re-swept and walked per round (more when the batch has few pairs)
-  int k1 = 0, k2 = 0;
   bialign_timing timing{};
   bool ran = false, ran_trace = false;
   bool pending = false, pending_trace = false;  // an enqueued run not yet waited for
@@ -224,25 +176,6 @@ struct bialign_batch {
 
 namespace bialign {
 
-// One launch shape: TW waves per workgroup, GW workgroups per pair (GW > 1 = cross-CU team).
-struct TeamShape {
-  int tw = 1, gw = 1;
-  bool slim = false;  // the three-waves-per-SIMD kernel (fill_affine_slim_kernel), teams of tw = 2, 3, 6 or 12 waves
-  int waves() const { return tw * gw; }
-};
-// fill_affine_slim_kernel exists for this batch: affine, max_shift 1, LOOKUP scores, beta <= 0, packed records, full storage
-inline bool slim_available(const bialign_batch* b) {
-  const char* sw = getenv("BIALIGN_SLIM");  // "0": tests / A-B, the two-wave kernels only
-  const bool off = sw && atoi(sw) == 0;
-  return !off && b->affine && b->S == 1 && !b->dense && !b->dense1 && !b->wide && b->prm.gap_opening_cost <= 0 && (b->lean || b->pack_now());
-}
-
-// xcu_resident: one-wave workgroups of the cross-CU kernel the device holds at once (0: no such kernel);
-// xcu8_resident: likewise its eight-wave workgroups (s=2 affine sweep only, else 0)
-TeamShape team_shape(const bialign_batch* b, int first, int count, int xcu_resident, int xcu8_resident = 0);
-inline bool diet8_available(const bialign_batch* b) {  // the eight-wave s=2 affine kernel and its LDS layout
-  return b->affine && b->S == 2 && !b->dense && !b->dense1 && b->lds_diet8 <= 160 * 1024;
-}
 // Cross-CU launches of all engines of this process on one device run one after the other (each needs
 // the whole device's wave slots): the stream waits for the previous such launch, the new one is recorded.
 int xcu_serial_begin(bialign_engine* e);
@@ -254,8 +187,6 @@ int launch_build_mu2(bialign_batch* b, int first, int count);
 
 // Null batch (bialign_null.hip): write the replicas of virtual pairs first .. first + count into the replica buffers, and
 // reduce every real pair's replica scores (d_scores) into d_null_stats; both on the engine's stream.
-// (FEATURE- and DENSE-form null batches: the shuffle's index array in LDS is uint16, so len_b <= NULL_FEAT_MAX_M)
-constexpr int NULL_FEAT_MAX_M = 65535;
 int launch_shuffle_null(bialign_batch* b, int first, int count);
 // DENSE-form null batch: permute the real tables' columns into the chunk's table buffer for virtual pairs
 // order[first .. first+count), on the engine's stream; launch_shuffle_null must have written their permutations.
@@ -462,7 +393,7 @@ template <int S, int TW, unsigned F>
 int xcu_resident_affine(bialign_batch* b) {
   constexpr unsigned Q = (F & ~F_PACK) | F_XCU;
   if constexpr (fill_affine_exists(S, TW, Q)) {
-    if (TW == 8 && !diet8_available(b)) return 0;
+    if (TW == 8 && !diet8_available(*b)) return 0;
     return xcu_resident_cached(b, ((F & F_LEAN) ? 1 : 0) + (TW == 8 ? 2 : 0), fill_affine_of<S, TW, Q>(), 64 * TW, fill_lds<S, TW>(b, true));
   } else {
     return 0;
@@ -494,7 +425,7 @@ int launch_fill_affine(bialign_batch* b, const DeviceBatch& v, int first, int co
       return fail(BIALIGN_E_UNSUPPORTED, "no affine sweep for max_shift %d in form %u", S, F);
     } else {
       TeamShape ts;  // general beta: one wave per pair
-      if constexpr (!(F & F_BETA_ANY)) ts = team_shape(b, first, count, xcu_resident_affine<S, 1, F>(b), xcu_resident_affine<S, 8, F>(b));
+      if constexpr (!(F & F_BETA_ANY)) ts = team_shape(*b, first, count, b->eng->num_cu, xcu_resident_affine<S, 1, F>(b), xcu_resident_affine<S, 8, F>(b));
       if constexpr (fill_slim_exists(S, F)) {
         if (ts.slim) return launch_fill_affine_slim<S, (F & F_LEAN) != 0>(b, v, first, count, ts.tw);
       }
@@ -617,7 +548,7 @@ int launch_fill_linear(bialign_batch* b, const DeviceBatch& v, int first, int co
   return with_flags<F_DENSE | F_LEAN | F_DENSE1>(fill_flags(b), [&](auto flags) -> int {
     constexpr unsigned F = decltype(flags)::value;
     const int resident = xcu_resident_cached(b, (F & F_LEAN) ? 1 : 0, fill_linear_of<S, 1, F | F_XCU>(), 64, fill_lds<S, 1>(b, false));
-    const TeamShape ts = team_shape(b, first, count, resident);
+    const TeamShape ts = team_shape(*b, first, count, b->eng->num_cu, resident);
     int rc = BIALIGN_OK;
     (void)(fill_linear_rung<S, 1, F | F_XCU>(b, v, first, count, ts, &rc) || fill_linear_rung<S, 8, F>(b, v, first, count, ts, &rc) ||
            fill_linear_rung<S, 4, F>(b, v, first, count, ts, &rc) || fill_linear_rung<S, 2, F>(b, v, first, count, ts, &rc) ||
@@ -680,7 +611,6 @@ int launch_dump_wide(const bialign_batch* b, const DeviceBatch& v, int pid, int3
   X template int launch_traceback_linear_strip<S>(const bialign_batch*, const DeviceBatch&, int, int);  \
   X template int launch_dump<S, 9>(const bialign_batch*, const DeviceBatch&, int, int32_t*);            \
   X template int launch_dump<S, 1>(const bialign_batch*, const DeviceBatch&, int, int32_t*);
-#define BIALIGN_FOR_EACH_S(M, X) M(0, X) M(1, X) M(2, X) M(3, X) M(4, X) M(5, X)
 
 #ifndef BIALIGN_TU_S  // every other unit: the instantiations live elsewhere
 BIALIGN_FOR_EACH_S(BIALIGN_INST_KIND0, extern)

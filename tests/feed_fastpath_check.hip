@@ -24,7 +24,7 @@ static void run_case(int T, int n, int m) {
   using GF = GhostFeed<S, 9, false, BLKO>;
   using G = Geo<S>;
   using PK = Pack<S>;
-  // the host's sweep geometry (sweep_geometry in bialign_capi.hip)
+  // the host's sweep geometry (sweep_geometry in bialign_plan.hpp)
   const int NS = (n + 1 + G::RR - 1) / G::RR;
   const int P = std::max(m + 2, 2 * (G::R - 1) + GF::MIN_GOFF);
   const int Gsteps = (NS - 1) * P + m + G::MAXOFF + 1;

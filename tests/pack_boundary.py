@@ -30,9 +30,9 @@ class Geometry:
         self.HI = m - s                                      # bialign_types.hpp:171 Pack<S>::hi
         self.BLK = 8 if s <= 1 else 4                        # bialign_feed.hpp:30   GhostFeed<S,9>::BLK
         min_goff = 2 * self.BLK + 8                          # bialign_feed.hpp:45   GhostFeed::MIN_GOFF
-        self.NS = (n + 1 + self.RR - 1) // self.RR           # bialign_capi.hip:256  sweep_geometry
-        self.P = max(m + 2, 2 * (self.R - 1) + min_goff)     # bialign_capi.hip:258
-        self.G = (self.NS - 1) * self.P + m + self.MAXOFF + 1  # bialign_capi.hip:259
+        self.NS = (n + 1 + self.RR - 1) // self.RR           # bialign_plan.hpp  sweep_geometry
+        self.P = max(m + 2, 2 * (self.R - 1) + min_goff)     # (sweep_geometry)
+        self.G = (self.NS - 1) * self.P + m + self.MAXOFF + 1  # (sweep_geometry)
         self.CHECK = 16                                      # bialign_types.hpp:180 Pack<S>::CHECK
 
     def place(self, i, j, aa):

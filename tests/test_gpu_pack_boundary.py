@@ -4,8 +4,8 @@ either side of it, at the edges of the interior region and at chosen distances f
 Every case: score, trace, ``complete`` and every in-band cell of all nine dumped layers equal the oracle; the batch
 falls back to full records exactly when the verdict says a record of an interior step does not fit.
 
-Dense mu1 is the exception the engine makes on purpose: a batch with mu1 tables is never packed (bialign_capi.hip,
-``!b->dense1`` in the packing policy; fill_affine_kernel: static_assert(!DENSE1 || !PACK)).  Its cases run the same
+Dense mu1 is the exception the engine makes on purpose: a batch with mu1 tables is never packed (bialign_plan.hpp, decide_pack:
+``!b.dense1`` in the packing policy; fill_affine_kernel: static_assert(!DENSE1 || !PACK)).  Its cases run the same
 spikes through full records: results equal the oracle, nothing is packed and nothing needs recovering."""
 import functools
 

@@ -1,6 +1,6 @@
 """Reduced-storage modes against the CPU ORACLE (not against the default GPU path): score-only
 sweeps, memory-lean traceback and the automatic switch to it under a tiny HBM budget -- modes the
-engine may select by itself (bialign_capi.hip, "served from reduced storage instead of failing").
+engine may select by itself (bialign_plan.hpp, plan_storage: "served from reduced storage instead of failing").
 Seeded and bounded: 72 batches of multi-strip shapes, max_shift 0..5, re-sweep widths 1 / 3 / 32,
 LOOKUP and DENSE mu2, both recurrences, beta of either sign."""
 import numpy as np

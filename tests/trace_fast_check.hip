@@ -95,7 +95,7 @@ static void run_case(int n, int m, bool cells) {
   constexpr int W = TF::W, RR = TF::RR;
   PairDesc pd{};
   pd.n = n, pd.m = m;
-  pd.NS = (n + 1 + G::RR - 1) / G::RR;  // the host's sweep geometry (sweep_geometry in bialign_capi.hip)
+  pd.NS = (n + 1 + G::RR - 1) / G::RR;  // the host's sweep geometry (sweep_geometry in bialign_plan.hpp)
   pd.P = std::max(m + 2, 2 * (G::R - 1) + GF::MIN_GOFF);
   pd.G = (pd.NS - 1) * pd.P + m + G::MAXOFF + 1;
   pd.layer_off = 0;

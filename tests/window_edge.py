@@ -2,7 +2,7 @@
 Shared by test_window_edge_host.py (no GPU: every case is what it claims to be, from the oracle alone) and
 test_gpu_window_edge.py (every DP path, bit-exact against the oracle, at that scale).
 
-The contract (bialign_capi.hip, "int32 safety window"): a batch is refused unless every pair has
+The contract (bialign_plan.hpp, score_bound and plan_pairs, "int32 safety window"): a batch is refused unless every pair has
     (2 (n + m) + 8) * colmax < 2^28,   colmax = max|mu1| + max|mu2| + 2 (|gamma| + |beta|) + 2 |delta|
 with the maxima taken over the S1 / S2 tables (LOOKUP form), the dense tables, or -- FEATURE form --
 ceil(|sw| (sqrt(max upA max upB) + sqrt(max downA max downB) + sqrt(max unpA max unpB))).  The kernels then assume that
@@ -61,7 +61,8 @@ KEYS = ("up", "down", "unp")
 # ---- the mirror ----------------------------------------------------------------------------------------------------
 
 def window(n, m, amax, bmax, beta, gamma, delta):
-    """-> (colmax, product): bialign_capi.hip, create_batch, ``colmax`` and the left side of the per-pair check."""
+    """-> (colmax, product): bialign_plan.hpp: score_bound's ``colmax`` and the left side of plan_pairs' per-pair check
+    (tests/test_plan_host.py holds this mirror against that code)."""
     colmax = int(amax) + int(bmax) + 2 * (abs(int(gamma)) + abs(int(beta))) + 2 * abs(int(delta))
     return colmax, (2 * (int(n) + int(m)) + 8) * colmax
 
