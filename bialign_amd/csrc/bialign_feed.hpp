@@ -232,7 +232,7 @@ struct GhostFeed {
   }
 };
 
-// Ghost source of fill_affine_slim_kernel's interior steps (BIALIGN_STEP_SCALAR): the LDS byte address a lane reads its
+// Ghost source of fill_affine_slim_kernel's interior steps: the LDS byte address a lane reads its
 // stored layers from is  factor(lane) * ring_step_byte(g) + lane_byte(lane)  relative to the wave's ring for live lanes
 // (their (step, a) entry), and the sentinel block for the others.  `sent_rel` is that block's address, ring-relative
 // or absolute as long as ring_step_byte's base is of the same kind.
@@ -254,7 +254,7 @@ struct GhostSrc {
 // LDS dwords of fill_affine_slim_kernel's table of steady-block lane offsets (one per workgroup; the LEAN form leaves
 // it unused).  The host sizes the workgroup's LDS with it (sweep_info_of).
 template <int S>
-constexpr int slim_offtab_dw() { return BIALIGN_FEED_FAST ? GhostFeed<S, 9>::OFFTAB_DW : 0; }
+constexpr int slim_offtab_dw() { return GhostFeed<S, 9>::OFFTAB_DW; }
 
 // ---------------------------------------------------------------------------
 // Dense-mu2 feed (structure similarities that are not a

@@ -79,7 +79,7 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
   int32_t* sentblk = smem + NW * PERW;
   volatile int32_t* prog_lds = smem + NW * PERW + SENTBLK + pw * TW;  // [16]: this team's words
   // the ghost feed's lane offsets of a steady block (GhostFeed::issue_steady), [round][lane]; one table per workgroup
-  constexpr bool FEED_FAST = BIALIGN_FEED_FAST && !LEAN;
+  // (packed records only: the LEAN form leaves it unused)
   int32_t* offtab = smem + NW * PERW + SENTBLK + LDS_PROG_WORDS;
   int32_t* s1 = offtab + slim_offtab_dw<S>();                         // [k1*k1]
   int32_t* s2 = s1 + k1 * k1;                                         // [k2*k2]
@@ -92,7 +92,7 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
 
   for (int t = threadIdx.x; t < NW * PERW + SENTBLK; t += 64 * NW) smem[t] = SENT;
   if (threadIdx.x < LDS_PROG_WORDS) smem[NW * PERW + SENTBLK + threadIdx.x] = 0;
-  if (FEED_FAST)
+  if (!LEAN)
     for (int t = threadIdx.x; t < GF::OFFTAB_DW; t += 64 * NW) offtab[t] = (int32_t)GF::lane_offset(t >> 6, t & 63);
   for (int t = threadIdx.x; t < k1 * k1; t += 64 * NW) s1[t] = A.s1[t];
   for (int t = threadIdx.x; t < k2 * k2; t += 64 * NW) s2[t] = A.s2[t];
@@ -117,8 +117,6 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
   // the band -- lane 63, whose derived values are all sentinels.  Ghost lanes and lane 63 read whatever: nobody uses it.
   const int addrA = ((L - W) & 63) * 4;
   const int addrB = (live && aa < W - 1 ? ((L - W + 1) & 63) : 63) * 4;
-  // lane L-1 = (i, a-1), or lane 63 (sentinels) where a-1 leaves the band
-  const int addrC = ((live && aa > 0) ? L - 1 : 63) * 4;
   const bool a_first = (aa == 0);
   const int lane_cap = a_first ? SENT : 0x7fffffff;  // min() with it = "sentinel where a-1 leaves the band"
   int32_t* const lay = A.layers + pd.layer_off;
@@ -148,8 +146,8 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
   int dB[4][W];              // GMY, H3M[0..2] from (i-1,a+1): age 2
   int dC[2][W];              // GYM, GYX from (i,a-1): age 2
   int selfv[4][W];           // GYY, H3Y[0..2] of this lane's previous column
-  int pubC[W][8];            // GYM, GYX, H2M[0..2], H2X[0..2] of the previous column, for lane L+1 (DPP form only)
-  int inC[W][8];             // ... as received from lane L-1 (bpermute form: loop-carried, exchanged at the end of a step)
+  int pubC[W][8];            // GYM, GYX, H2M[0..2], H2X[0..2] of the previous column, for lane L+1
+  int inC[W][8];             // ... as received from lane L-1 (dpp_from_left)
   int inA[W][4], inB[W][8];  // what (i-1,a) and (i-1,a+1) derived one step ago (loop-carried: exchanged at the end of a step)
 #pragma unroll
   for (int bb = 0; bb < W; ++bb) {
@@ -163,25 +161,23 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
   const uint32_t ring_lds = __builtin_amdgcn_readfirstlane(
       (uint32_t)(uintptr_t)(__attribute__((address_space(3))) int32_t*)smem) + wv * GF::RING_DW * 4;
 
-  // ---- interior steps (BIALIGN_STEP_SCALAR): what is wave-uniform there stays in scalar registers.  Every lane of an
+  // ---- interior steps: what is wave-uniform there stays in scalar registers.  Every lane of an
   // interior step is in lane 0's strip, so the step's record is one scalar base (StepAddr: + RECB per step) and a store
   // goes to base + lane constant + immediate; the ghost source is the ring offset of (half, step in block) times a 0/1
   // lane factor plus a lane constant (GhostSrc); lane 0's phase and strip have scalar mirrors for the interior test.
-  constexpr bool STEP_SCALAR = BIALIGN_STEP_SCALAR;
+  // (The per-lane form -- record and ring addresses from each lane's own jj and strip, clamped code fetches, the interior
+  //  test read out of lane 0 -- took 452 instead of 434 instructions on the step's hot path, 313 instead of 303 VALU, and
+  //  44.43 instead of 43.86 ms of fill on the headline workload: profiles/r06a_step_scalar.)
   using SA = StepAddr<S, LEAN>;
   using GS = GhostSrc<S, LEAN>;
   typedef const __attribute__((address_space(3))) int32_t* lds_cptr;
   typedef __attribute__((address_space(1))) char* gbl_ptr;  // (global, said outright: the base passes through integers)
   typedef __attribute__((address_space(1))) v4i* gbl_v4i;
   typedef __attribute__((address_space(1))) int32_t* gbl_i32;
-  uint32_t st_off = 0, st_toff = 0, gs_fac = 0, gs_lane = 0;  // (laundered like the predicates above: never re-derived)
-  if (STEP_SCALAR) {
-    st_off = SA::chunk_off(L);
-    st_toff = SA::tail_off(L);
-    gs_fac = GS::factor(L);
-    gs_lane = GS::lane_byte(L, ring_lds + (NW - wv) * GF::RING_DW * 4);  // (the sentinel block follows the last wave's ring)
-    asm volatile("" : "+v"(st_off), "+v"(st_toff), "+v"(gs_fac), "+v"(gs_lane));
-  }
+  // (laundered like the predicates above: never re-derived)
+  uint32_t st_off = SA::chunk_off(L), st_toff = SA::tail_off(L), gs_fac = GS::factor(L);
+  uint32_t gs_lane = GS::lane_byte(L, ring_lds + (NW - wv) * GF::RING_DW * 4);  // (the sentinel block follows the last wave's ring)
+  asm volatile("" : "+v"(st_off), "+v"(st_toff), "+v"(gs_fac), "+v"(gs_lane));
   int s_ph = 0, s_q = 0;   // lane 0's column and local strip (it starts at column 0: il = aa = 0), advanced with jj / strip
   int s_adv = 0;           // interior steps since the last boundary step: jj waits at the run's first column meanwhile
   uint32_t ring_u = 0;     // LDS byte address of this step's ghost entries of band row 0: set per block, + STEPB per step
@@ -209,13 +205,15 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
   bool blk_steady = false;
   auto prefetch_block = [&](int h0, int half) __attribute__((always_inline)) {
     wait_partner(h0 + GF::BLK - 1);
-    if (FEED_FAST) blk_steady = GF::steady(blk_q, blk_rem, P, T, w, m, rec_last);
+    // (recomputing the 3 x 64 source addresses of every block, steady or not, cost 1.07 ms = 2.3 % of the headline fill:
+    //  profiles/r04a_feed_fastpath)
+    if (!LEAN) blk_steady = GF::steady(blk_q, blk_rem, P, T, w, m, rec_last);
     // (the lane number is laundered: everything the feed derives from it -- piece, band row, chunk, 64-bit source bases
     //  for three rounds; the table address of a steady block -- would otherwise be hoisted out of the sweep and sit in a
     //  dozen registers the step needs)
     int Lv = L;
     asm volatile("" : "+v"(Lv));
-    if (FEED_FAST && blk_steady)  // nine blocks in ten at len 1024: a scalar base + the lane's offsets from the LDS table
+    if (!LEAN && blk_steady)  // nine blocks in ten at len 1024: a scalar base + the lane's offsets from the LDS table
       GF::issue_steady(lay, blk_q, blk_rem, P, T, w, offtab, Lv, ring_lds + half * GF::SLOTS * 16);
     else if (LEAN) GF::issue(lay, h0, blk_q, blk_rem, P, T, w, P - 2 * (R - 1), rec_last, Lv, ring_lds + half * GF::SLOTS * 16);
     else GF::issue_packed(lay, pk_bnd_off, m, h0, blk_q, blk_rem, P, T, w, rec_last, Lv, ring_lds + half * GF::SLOTS * 16);
@@ -251,7 +249,7 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
 
   auto step = [&](auto interior_tag, int g) __attribute__((always_inline)) {
     constexpr bool INTERIOR = decltype(interior_tag)::value;
-    if (STEP_SCALAR && !INTERIOR) {  // the columns of the interior run that has just ended
+    if (!INTERIOR) {  // the columns of the interior run that has just ended
       jj += s_adv;
       s_adv = 0;
     }
@@ -268,10 +266,8 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
       if (!LEAN) {  // the block that has just landed: lane t*W + a unpacks its entry in place (fill_affine_kernel, PK_COOP)
         if (L < GF::BLK * W) {
           bool packed = true;  // a steady block: every entry is a packed record
-          if (!(FEED_FAST && blk_steady)) {
-            const int c0 = STEP_SCALAR ? s_ph : __builtin_amdgcn_readfirstlane(jj);
-            const int q0 = STEP_SCALAR ? s_q : __builtin_amdgcn_readfirstlane(strip);
-            int ph = c0 + L / W, qst = q0 * T + w;
+          if (!blk_steady) {
+            int ph = s_ph + L / W, qst = s_q * T + w;  // lane 0's phase and strip at this entry's step
             if (ph >= P) { ph -= P; qst += T; }
             const int ts = ph + 2 * (R - 1), over = ts >= P ? 1 : 0;
             packed = PK_::interior(qst - 1 + over, ts - over * P, m);
@@ -303,7 +299,7 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
       }
       prefetch_block(g + GF::BLK, ghalf ^ 1);
       vm_younger = 0;
-      if (STEP_SCALAR) ring_u = ring_lds + ghalf * GS::HALFB;
+      ring_u = ring_lds + ghalf * GS::HALFB;
       if (A.prio_mode) {  // rotate four priority levels over the workgroups of a CU by age (fill_affine_kernel)
         const int lvl = ((g >> 7) + (wv >> 2)) & 3;  // (waves wv, wv + 4, wv + 8 share a SIMD)
         if (lvl == 0) __builtin_amdgcn_s_setprio(0);
@@ -312,14 +308,15 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
         else __builtin_amdgcn_s_setprio(3);
       }
     }
-    // where this lane's stored layers lie in LDS: its (step, a) entry of the ring, or the sentinel block (lane 63)
+    // where this lane's stored layers lie in LDS: its (step, a) entry of the ring, or the sentinel block (lane 63).
+    // Per lane for the boundary steps ...
     const int32_t* const gsrc = live ? reinterpret_cast<const int32_t*>(ring + ghalf * GF::SLOTS + (gt * W + aa) * GF::NP)
                                      : sentblk;
-    // ... in an interior step (BIALIGN_STEP_SCALAR) as one VALU: the step's scalar ring address through the lane's 0/1
-    // factor, plus the lane constant (a * NP * 16, or the sentinel block's address)
+    // ... in an interior step as one VALU: the step's scalar ring address through the lane's 0/1 factor, plus the lane
+    // constant (a * NP * 16, or the sentinel block's address)
     // (written out: left to itself hipcc multiplies up here and adds inside the ring-fed lanes' branch)
     uint32_t gaddr = 0;
-    if (STEP_SCALAR && INTERIOR) asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(gaddr) : "v"(gs_fac), "s"(ring_u), "v"(gs_lane));
+    if (INTERIOR) asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(gaddr) : "v"(gs_fac), "s"(ring_u), "v"(gs_lane));
     const lds_cptr gsrc_s = (lds_cptr)(uintptr_t)gaddr;
     // a store's lane offset, laundered at the store (in place: a laundered copy costs a move): extended to 64 bits
     // anywhere else -- outside the loop, or in another block of the step -- it is added to the base per lane instead of
@@ -329,36 +326,8 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
       return off;
     };
 
-    // ---- 1. lane L-1 = (i, a-1) hands its values over in registers: DPP wave shift fused with the cap (s_nop 1: the
-    //         wait states a DPP read needs, see fill_affine_kernel)
-    auto read_dpp = [&](int r) __attribute__((always_inline)) {
-      if (!BIALIGN_SLIM_DPP) return;
-      if (r + 1 < W) {
-        asm("s_nop 1\n\t"
-            "v_min_i32_dpp %0, %8, %16 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-            "v_min_i32_dpp %1, %9, %16 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-            "v_min_i32_dpp %2, %10, %16 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-            "v_min_i32_dpp %3, %11, %16 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-            "v_min_i32_dpp %4, %12, %16 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-            "v_min_i32_dpp %5, %13, %16 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-            "v_min_i32_dpp %6, %14, %16 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-            "v_min_i32_dpp %7, %15, %16 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1"
-            : "=&v"(inC[r][0]), "=&v"(inC[r][1]), "=&v"(inC[r][2]), "=&v"(inC[r][3]), "=&v"(inC[r][4]),
-              "=&v"(inC[r][5]), "=&v"(inC[r][6]), "=&v"(inC[r][7])
-            : "v"(pubC[r][0]), "v"(pubC[r][1]), "v"(pubC[r][2]), "v"(pubC[r][3]), "v"(pubC[r][4]),
-              "v"(pubC[r][5]), "v"(pubC[r][6]), "v"(pubC[r][7]), "v"(lane_cap));
-      } else {
-        asm("s_nop 1\n\t"
-            "v_min_i32_dpp %0, %5, %10 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-            "v_min_i32_dpp %1, %6, %10 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-            "v_min_i32_dpp %2, %7, %10 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-            "v_min_i32_dpp %3, %8, %10 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-            "v_min_i32_dpp %4, %9, %10 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1"
-            : "=&v"(inC[r][0]), "=&v"(inC[r][1]), "=&v"(inC[r][5]), "=&v"(inC[r][6]), "=&v"(inC[r][7])
-            : "v"(pubC[r][0]), "v"(pubC[r][1]), "v"(pubC[r][5]), "v"(pubC[r][6]), "v"(pubC[r][7]), "v"(lane_cap));
-        inC[r][2] = inC[r][3] = inC[r][4] = SENT;
-      }
-    };
+    // ---- 1. lane L-1 = (i, a-1) hands its values over in registers: DPP wave shift fused with the cap
+    auto read_dpp = [&](int r) __attribute__((always_inline)) { dpp_from_left<W>(r, inC, pubC, lane_cap); };
     read_dpp(0);
 
     // ---- 2. score inputs of this column
@@ -383,8 +352,9 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
     const int slot_ = LEAN ? aa : (pad_lane ? R_::SL + pad_idx : L - W);
     if (INTERIOR) vm_younger += PACKED ? PK_::NPC : GF::STORES_PER_STEP;  // (an interior step always stores)
     else if (__builtin_amdgcn_ballot_w64(do_store) != 0) vm_younger += GF::STORES_PER_STEP;
-    int32_t* dst = lay + (int64_t)rec * RECDW;  // LEAN: the one region; else (boundary steps) the full record in the pair's second region
-    int32_t* const dstp = lay + (int64_t)rec * PK_::RECDW;  // interior steps: the packed record
+    // boundary steps, per lane (interior steps store through sbase).  LEAN: the one region; else the full record in the
+    // pair's second region
+    int32_t* dst = lay + (int64_t)rec * RECDW;
     if (!INTERIOR && !LEAN) {
       const int tl = jj + 2 * il + aa;
       const int over = tl >= P ? 1 : 0;
@@ -396,7 +366,6 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
     int pk_base = 0, pk_min = 0, pk_max = 0, pk_e[PACKED ? ND : 1];  // packed records: base, running extremes, the values
     int h2y[3] = {SENT, SENT, SENT};
     int defer[3] = {SENT, SENT, SENT};  // GXM, GXX, GXY of the previous point: their registers are busy for one more point
-    int deferC[3] = {SENT, SENT, SENT}; // H2M[0..2] of the previous point, likewise
 #pragma unroll
     for (int bb = 0; bb < W; ++bb) {
       if (bb + 1 < W) read_dpp(bb + 1 < W ? bb + 1 : 0);
@@ -405,51 +374,7 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
       const int mu2v = mu2[bb];
       const int c_MM = mu1 + mu2v, c_gM = mu2v + gD, c2M = mu2v + dd;
 
-      auto cases = [&](int (&Tv)[9]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int hU = 0; hU < 3; ++hU) {
-#pragma unroll
-          for (int hV = 0; hV < 3; ++hV) {
-            int gin = SENT;
-            bool ok1 = true;
-            if (hU == 2 && hV == 2) gin = dA2[0][bb];
-            if (hU == 2 && hV == 1) { ok1 = bb + 1 < W; if (ok1) gin = dA2[1][bb + 1 < W ? bb + 1 : 0]; }
-            if (hU == 2 && hV == 0) gin = dB[0][bb];
-            if (hU == 1 && hV == 2) { ok1 = bb >= 1; if (ok1) gin = dAx[0][bb >= 1 ? bb - 1 : 0]; }
-            if (hU == 1 && hV == 1) gin = dAx[1][bb];
-            if (hU == 1 && hV == 0) { ok1 = bb >= 1; if (ok1) gin = inB[bb >= 1 ? bb - 1 : 0][1]; }
-            if (hU == 0 && hV == 2) gin = dC[0][bb];
-            if (hU == 0 && hV == 1) { ok1 = bb + 1 < W; if (ok1) gin = dC[1][bb + 1 < W ? bb + 1 : 0]; }
-            if (hU == 0 && hV == 0) gin = selfv[0][bb];
-            const int c1 = (hU == 2 && hV == 2) ? c_MM : (hU == 2) ? c_Mg : (hV == 2) ? c_gM : (hU == hV) ? gg : ggdd;
-            int h2in = SENT;
-            bool ok2 = true;
-            if (hV == 2) { ok2 = bb >= 1; if (ok2) h2in = inC[bb >= 1 ? bb - 1 : 0][2 + hU]; }
-            if (hV == 1) h2in = inC[bb][5 + hU];
-            if (hV == 0) { ok2 = bb >= 1; if (ok2) h2in = h2y[hU]; }
-            const int c2 = (hV == 2) ? c2M : gD;
-            int h3in = SENT;
-            bool ok3 = true;
-            if (hU == 2) { ok3 = bb + 1 < W; if (ok3) h3in = dB[1 + hV][bb + 1 < W ? bb + 1 : 0]; }
-            if (hU == 1) h3in = inB[bb][5 + hV];
-            if (hU == 0) { ok3 = bb + 1 < W; if (ok3) h3in = selfv[1 + hV][bb + 1 < W ? bb + 1 : 0]; }
-            const int c3 = (hU == 2) ? c3M : gD;
-            int t = SENT;
-            bool any = false;
-            if (hU < 2 && hV < 2 && ok2 && ok3) {
-              // both gap-gap groups cost gamma + Delta: max(c1 + g, gD + h2, gD + h3) = gD + max(g + (c1 - gD), h2, h3),
-              // exact in integers, one add less (c1 - gD is wave-uniform: gamma - Delta or gamma + Delta)
-              const int inner = ok1 ? imax(imax(gin + (c1 - gD), h2in), h3in) : imax(h2in, h3in);
-              t = gD + inner;
-            } else {
-              if (ok1) { t = c1 + gin; any = true; }
-              if (ok2) { t = any ? imax(t, c2 + h2in) : c2 + h2in; any = true; }
-              if (ok3) { t = any ? imax(t, c3 + h3in) : c3 + h3in; any = true; }
-            }
-            Tv[3 * hU + hV] = t;
-          }
-        }
-      };
+      const AffineCases<W> cases{dA2, bb, dB, dAx, inB, dC, selfv, c_MM, c_Mg, c_gM, gg, ggdd, inC, h2y, c2M, gD, c3M};
       // finalise: ring-fed lanes (ghost row; lane 63) take their stored layers -- nine values, fetched inside the
       // branch only they take -- the others compute; "no valid case" -> -2^30 (pyx:299-303)
       int M[9];
@@ -457,7 +382,7 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
       if (INTERIOR) {
         if (ringfed) {
 #pragma unroll
-          for (int q = 0; q < 9; ++q) M[q] = STEP_SCALAR ? gsrc_s[bb * 9 + q] : gsrc[bb * 9 + q];
+          for (int q = 0; q < 9; ++q) M[q] = gsrc_s[bb * 9 + q];
         } else {
           int Tv[9];
           cases(Tv);
@@ -495,8 +420,8 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
         for (int q = 0; q < 9; ++q) outv[PACKED ? 0 : bb * 9 + q] = M[q];
       }
       if (LEAN && bb == S) {  // score-only: the end cell (n,m,n,m) is all the host wants (pyx:509)
-        // (an interior step is never at column m; under BIALIGN_STEP_SCALAR its jj is not the column either)
-        if (!(STEP_SCALAR && INTERIOR) && live && !ghost && aa == S && i == n && jj == m) {
+        // (an interior step is never at column m; its jj is not the column either: see s_adv)
+        if (!INTERIOR && live && !ghost && aa == S && i == n && jj == m) {
           int best = M[0];
 #pragma unroll
           for (int q = 1; q < 9; ++q) best = imax(best, M[q]);
@@ -550,16 +475,11 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
               if (c < PK_::NCH) {
                 v4i v;
                 v.x = dw[0]; v.y = dw[1]; v.z = dw[2]; v.w = dw[3];
-                if (STEP_SCALAR) *reinterpret_cast<gbl_v4i>(sbase + SA::chunk_imm(c) + at_store(st_off)) = v;
-                else *reinterpret_cast<v4i*>(dstp + c * R_::CH + slot_ * 4) = v;
+                *reinterpret_cast<gbl_v4i>(sbase + SA::chunk_imm(c) + at_store(st_off)) = v;
               } else if (slot_ < PK_::TSLOTS) {  // the tail piece: TAILDW dwords per lane
-                int32_t* tp = dstp + PK_::NCH * R_::CH + slot_ * PK_::TAILDW;
-                const gbl_i32 tps = STEP_SCALAR ? reinterpret_cast<gbl_i32>(sbase + SA::TAIL_IMM + at_store(st_toff)) : nullptr;
+                const gbl_i32 tp = reinterpret_cast<gbl_i32>(sbase + SA::TAIL_IMM + at_store(st_toff));
 #pragma unroll
-                for (int x = 0; x < PK_::TAILDW; ++x) {
-                  if (STEP_SCALAR) tps[x] = dw[x];
-                  else tp[x] = dw[x];
-                }
+                for (int x = 0; x < PK_::TAILDW; ++x) tp[x] = dw[x];
               }
             }
           }
@@ -572,15 +492,15 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
               v4i v;
               v.x = outv[PACKED ? 0 : 4 * c]; v.y = outv[PACKED ? 0 : 4 * c + 1];
               v.z = outv[PACKED ? 0 : 4 * c + 2]; v.w = outv[PACKED ? 0 : 4 * c + 3];
-              if (STEP_SCALAR && INTERIOR) *reinterpret_cast<gbl_v4i>(sbase + SA::chunk_imm(c) + at_store(st_off)) = v;
+              if (INTERIOR) *reinterpret_cast<gbl_v4i>(sbase + SA::chunk_imm(c) + at_store(st_off)) = v;
               else *reinterpret_cast<v4i*>(dst + c * R_::CH + slot_ * 4) = v;
             }
           }
           if (LEAN && bb == W - 1) {
-            const gbl_i32 tp = (STEP_SCALAR && INTERIOR) ? reinterpret_cast<gbl_i32>(sbase + SA::TAIL_IMM + at_store(st_toff)) : nullptr;
+            const gbl_i32 tp = INTERIOR ? reinterpret_cast<gbl_i32>(sbase + SA::TAIL_IMM + at_store(st_toff)) : nullptr;
 #pragma unroll
             for (int t = 0; t < TAIL; ++t) {
-              if (STEP_SCALAR && INTERIOR) tp[t] = outv[PACKED ? 0 : 4 * NCH4 + t];
+              if (INTERIOR) tp[t] = outv[PACKED ? 0 : 4 * NCH4 + t];
               else dst[NCH4 * R_::CH + slot_ * TAIL + t] = outv[PACKED ? 0 : 4 * NCH4 + t];
             }
           }
@@ -621,14 +541,12 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
           pk_all = act_row ? acc : 0;
         }
       }
-      if (BIALIGN_SLIM_DPP) {
       pubC[bb][0] = Gd[0][2];
       pubC[bb][1] = Gd[0][1];
 #pragma unroll
       for (int u = 0; u < 3; ++u) {
         pubC[bb][2 + u] = H2[u][2];
         pubC[bb][5 + u] = H2[u][1];
-      }
       }
       selfv[0][bb] = Gd[0][0];
 #pragma unroll
@@ -644,26 +562,11 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
       dmov(dB[0][bb], inB[bb][0]);
 #pragma unroll
       for (int v = 0; v < 3; ++v) dmov(dB[1 + v][bb], inB[bb][2 + v]);
-      if (BIALIGN_SLIM_DPP) {
-        dC[0][bb] = inC[bb][0];
-        dC[1][bb] = inC[bb][1];
-      } else {
-        // BIALIGN_SLIM_DPP=0 (measured, not shipped: 48.7 against 46.6 ms -- the LDS pipe has no room for 21 more
-        // instructions per step): lane L-1's values travel like the rows'.  GYM, GYX wait one more step in dC; H2X is
-        // used in this point only; H2M still serves the next point of this step and follows one point later
-        dmov(dC[0][bb], inC[bb][0]);
-        dmov(dC[1][bb], inC[bb][1]);
-        inC[bb][0] = bperm(addrC, Gd[0][2]);
-        inC[bb][1] = bperm(addrC, Gd[0][1]);
-#pragma unroll
-        for (int u = 0; u < 3; ++u) inC[bb][5 + u] = bperm(addrC, H2[u][1]);
-        if (bb >= 1) {
-#pragma unroll
-          for (int u = 0; u < 3; ++u) inC[bb >= 1 ? bb - 1 : 0][2 + u] = bperm(addrC, deferC[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < 3; ++u) deferC[u] = H2[u][2];
-      }
+      // (lane L-1's values do not travel like the rows', by ds_bpermute at the end of the point: 21 VALU less and 21 LDS
+      //  instructions more per step measured 48.7 against 46.6 ms -- the LDS pipe has no room for 21 more instructions
+      //  per step, profiles/r03d_slim)
+      dC[0][bb] = inC[bb][0];
+      dC[1][bb] = inC[bb][1];
       // exchange (for the next step): what lanes (i-1, a) and (i-1, a+1) derived for this band column.  The registers
       // of GXM, GXX (inA[.][2..3]) and GXY (inB[.][1]) still serve the NEXT point of this step: those three follow
       // one point later.
@@ -693,7 +596,7 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
     inB[W - 1][1] = bperm(addrB, defer[2]);
 
     // ---- advance
-    if (STEP_SCALAR && INTERIOR) ++s_adv;  // (every lane's column is jj + s_adv: one scalar add instead of one per lane)
+    if (INTERIOR) ++s_adv;  // (every lane's column is jj + s_adv: one scalar add instead of one per lane)
     else ++jj;
     if (!INTERIOR && jj == P) {  // (an interior step never ends a strip: its phase is at most m - S)
       jj = 0;
@@ -701,20 +604,19 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
       rec_base += (T - 1) * P;
       set_row(strip);
     }
-    if (STEP_SCALAR) {  // the scalar mirrors of lane 0's column and strip; the next step's ghost entries; the next record
-      ++s_ph;
-      if (!INTERIOR && s_ph == P) {
-        s_ph = 0;
-        ++s_q;
-      }
-      ring_u += GS::STEPB;
-      if (INTERIOR) {
-        sbase += SA::RECB;
-      } else {  // an interior run may begin with the next step: its record, as a scalar (lane 0's strip is every lane's there)
-        const uint64_t b = (uint64_t)(uintptr_t)(reinterpret_cast<char*>(lay) + SA::record_byte(g + 1, s_q, T, w, P));
-        sbase = reinterpret_cast<gbl_ptr>((uintptr_t)((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32 |
-                                                      (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)b)));
-      }
+    // the scalar mirrors of lane 0's column and strip; the next step's ghost entries; the next record
+    ++s_ph;
+    if (!INTERIOR && s_ph == P) {
+      s_ph = 0;
+      ++s_q;
+    }
+    ring_u += GS::STEPB;
+    if (INTERIOR) {
+      sbase += SA::RECB;
+    } else {  // an interior run may begin with the next step: its record, as a scalar (lane 0's strip is every lane's there)
+      const uint64_t b = (uint64_t)(uintptr_t)(reinterpret_cast<char*>(lay) + SA::record_byte(g + 1, s_q, T, w, P));
+      sbase = reinterpret_cast<gbl_ptr>((uintptr_t)((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32 |
+                                                    (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)b)));
     }
     if (INTERIOR) {  // same row, next column, inside the molecule: the window slides by one
       mu1n = s1[s1row + sbn];
@@ -725,14 +627,18 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
       lookup_mu();
     }
     // (an interior step leaves every lane at a column 1 <= jj + 1 <= m + 1: phase <= m - S, see Pack<S>::hi)
-    if (STEP_SCALAR && INTERIOR) fetch_codes(BoolTag<false>{});
+    if (INTERIOR) fetch_codes(BoolTag<false>{});
     else fetch_codes(BoolTag<true>{});
   };
 
+  // the interior test, on the scalar mirrors (no readfirstlane of jj and strip per step)
   auto all_interior = [&]() __attribute__((always_inline)) {
-    if (STEP_SCALAR) return PK_::interior(s_q * T + w, s_ph, m);
-    const int c0 = __builtin_amdgcn_readfirstlane(jj), q0 = __builtin_amdgcn_readfirstlane(strip);
-    return PK_::interior(q0 * T + w, c0, m);
+    // (jj and strip are named, not read: this closure is the first one hipcc takes apart, and the order in which it lists
+    //  the sweep's variables decides how the loop's registers are numbered.  Without the two names strip lands in another
+    //  register and all eight instantiations come out as a permutation of the measured code: same instructions, other
+    //  VGPR banks)
+    (void)jj, (void)strip;
+    return PK_::interior(s_q * T + w, s_ph, m);
   };
   int g = 0;  // local step of this wave
   while (g < H) {

@@ -42,27 +42,10 @@
 // interior step variant, 4 = always take it, 8 = the wide-band affine sweep stamps the phases of a level (tools/wide_phases.py)
 #define BIALIGN_EXP 0
 #endif
-#ifndef BIALIGN_PADMAX
-#define BIALIGN_PADMAX 2
-#endif
-#ifndef BIALIGN_SLIM_DPP  // fill_affine_slim_kernel: 1 = lane L-1's values by DPP (as fill_affine_kernel), 0 = by ds_bpermute
-#define BIALIGN_SLIM_DPP 1  // like the rows': 21 VALU less, 21 LDS instructions more per step -- and 4.5 % slower (48.7 vs 46.6 ms)
-#endif
-#ifndef BIALIGN_FEED_FAST  // fill_affine_slim_kernel: 1 = steady ghost blocks take GhostFeed::issue_steady (scalar base + lane
-#define BIALIGN_FEED_FAST 1  // constants), 0 = every block recomputes its 3 x 64 source addresses (A/B builds only)
-#endif
-#ifndef BIALIGN_STEP_SCALAR  // fill_affine_slim_kernel, interior steps: 1 = stores go to a scalar record base + lane constants
-#define BIALIGN_STEP_SCALAR 1  // (StepAddr), the ghost source is one v_mad_u32_u24 (GhostSrc), the codes are fetched unclamped
-#endif                         // and the interior test reads scalar mirrors of lane 0's phase and strip; 0 = per lane (A/B builds)
-
-#ifdef BIALIGN_WPE  // experiment: cap the affine sweep's registers so that this many waves fit a SIMD
-#define BIALIGN_WPE_ATTR __attribute__((amdgpu_waves_per_eu(BIALIGN_WPE, BIALIGN_WPE)))
-#else
-#define BIALIGN_WPE_ATTR
-#endif
 
 #include "bialign_types.hpp"
 #include "bialign_feed.hpp"
+#include "bialign_affine_point.hpp"
 #include "bialign_fill_affine.hpp"
 #include "bialign_fill_slim.hpp"
 #include "bialign_fill_linear.hpp"

@@ -103,7 +103,8 @@ struct Rec {
   static constexpr int TAIL = ND % 4;
   // A chunk holds SLP >= SL slots: where rounding SL up to a multiple of 8 costs at most two slots (s=2: 55 -> 56,
   // s=4: 54 -> 56) the spare lanes write them too and every chunk store covers whole 128-byte lines (-1..2 %).
-  static constexpr int SLP = (!LEAN && (SL + 7) / 8 * 8 - SL <= BIALIGN_PADMAX) ? (SL + 7) / 8 * 8 : SL;
+  static constexpr int PADMAX = 2;  // the most pad slots a chunk takes on
+  static constexpr int SLP = (!LEAN && (SL + 7) / 8 * 8 - SL <= PADMAX) ? (SL + 7) / 8 * 8 : SL;
   static constexpr int CH = SLP * 4;           // dwords per chunk
   // The tail has 64 slots, not SL: the spare lanes (ghost row, idle lanes) store don't-care values into the
   // last ones, so that a record ends on a 64-lane boundary -- at s=1 (6 x 960 + 768 B) it is 51 whole
@@ -229,7 +230,7 @@ struct Pack {
   }
 };
 
-// Store addresses of an INTERIOR step of fill_affine_slim_kernel (BIALIGN_STEP_SCALAR), factored so that host code can
+// Store addresses of an INTERIOR step of fill_affine_slim_kernel, factored so that host code can
 // call both halves (tests/step_addr_check.hip proves them against the sweep's per-lane bookkeeping).  In an interior
 // step every lane of the wave is in the same strip, so the step's record is wave-uniform:
 //     byte address of a store = pair's storage + record_byte(g, q, T, w, P)   -- scalar, + RECB per step

@@ -1,4 +1,4 @@
-// Host-side proof that the scalar addressing of fill_affine_slim_kernel's interior steps (BIALIGN_STEP_SCALAR) addresses
+// Host-side proof that the scalar addressing of fill_affine_slim_kernel's interior steps addresses
 // exactly what the per-lane bookkeeping addresses.  Stand-alone program (tests/test_step_addr_host.py compiles and runs
 // it, host code only).  It walks every wave of a team through its sweep the way the kernel does -- per-lane column, strip
 // and record base beside the scalar mirrors, the scalar record base, the ring address and the frozen column of an

@@ -1,4 +1,4 @@
-"""The scalar addressing of fill_affine_slim_kernel's interior steps (BIALIGN_STEP_SCALAR: a scalar record base plus lane
+"""The scalar addressing of fill_affine_slim_kernel's interior steps (a scalar record base plus lane
 constants for the stores, a one-instruction ghost source, unclamped code fetches, scalar mirrors of lane 0's column and
 strip) computes what the per-lane form computed: score, trace, completeness flag and every dumped layer cell against the
 oracle, and the same against the two-wave kernel (BIALIGN_SLIM=0), which keeps the per-lane form.

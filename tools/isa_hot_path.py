@@ -5,7 +5,7 @@
 k.s is hipcc's -S output (--cuda-device-only) of a translation unit; the kernel is the first one whose symbol contains
 the substring (default: fill_affine_slim_kernelILi1ELi3ELi4ELb0E, the headline's).  The interior-step loop is a depth-2
 loop of that kernel with at least 100 vector instructions (the others are the spin loops of the team hand-off); where the
-boundary steps form a depth-2 loop of their own (BIALIGN_STEP_SCALAR builds) it is the one with fewer of them.
+boundary steps form a depth-2 loop of their own (fill_affine_slim_kernel) it is the one with fewer of them.
 
 Two kinds of path from the loop header back to it are printed:
   * the per-step hot path: no ghost-block boundary work (no counted vmcnt wait, no DMA), no rare work;
