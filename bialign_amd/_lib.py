@@ -35,6 +35,7 @@ class Params(ctypes.Structure):
 BATCH_SCORE_ONLY = 1  # BIALIGN_BATCH_SCORE_ONLY
 BATCH_LEAN_TRACE = 2  # BIALIGN_BATCH_LEAN_TRACE
 BATCH_LEVEL_TRACE = 4  # BIALIGN_BATCH_LEVEL_TRACE
+BATCH_FIT = 8  # BIALIGN_BATCH_FIT: fit alignments, free end gaps in B
 
 
 class Scoring(ctypes.Structure):
@@ -118,6 +119,7 @@ SYMBOLS = [
     ("bialign_batch_get_timing", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Timing)]),
     ("bialign_batch_get_scores", ctypes.c_int, [ctypes.c_void_p, c_i32p]),
     ("bialign_batch_get_traces", ctypes.c_int, [ctypes.c_void_p, c_u8p, c_i64p, c_i32p, c_i32p]),
+    ("bialign_batch_get_fit_spans", ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p]),
     ("bialign_batch_dump_layers", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_i32p]),
     ("bialign_batch_create_null", ctypes.c_int,
      [ctypes.c_void_p, ctypes.POINTER(Params), ctypes.POINTER(Scoring), ctypes.POINTER(Pairs),

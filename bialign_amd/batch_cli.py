@@ -13,6 +13,11 @@ own pairs, rank 0 additionally a ``#scores`` line with all gathered scores.
 ``--zscore R`` adds one line behind each pair's block: where the score lies among the scores of A against R shuffles
 of B (``bialign_amd.significance``; the shuffles are made and scored on the GPU),
 ``ZSCORE: <z> (mean <mean>, sd <sd>, <n_ge>/<R> shuffles >= score)``.  Without the option the output is unchanged.
+
+``--fit`` aligns every pair's molecule A with the best-scoring substring of its molecule B (fit alignments, free end
+gaps in B: include/bialign.h, BIALIGN_BATCH_FIT).  The alignment is decoded on that substring, one extra line
+``B span\t <start_b+1>..<end_b>`` (1-based, inclusive) follows ``SCORE:``, ``--score_only`` lines gain the 1-based end
+as a fourth column, and ``--zscore`` scores the shuffles in the same mode.
 """
 import argparse
 import sys
@@ -51,6 +56,9 @@ def build_parser():
     p.add_argument("--zscore", type=int, default=0, metavar="R",
                    help="Also print each pair's z-score against R shuffles of molecule B (1..65535), as a "
                         "'ZSCORE:' line behind the pair's block.")
+    p.add_argument("--fit", action="store_true",
+                   help="Fit alignments: molecule A against the best substring of molecule B (B's end gaps are free); "
+                        "prints the substring as a 'B span' line behind 'SCORE:'.")
     p.add_argument("--zscore_seed", type=int, default=0, metavar="N",
                    help="Seed of the shuffles (default 0); shuffle r of a pair is a function of the seed, r and the "
                         "pair's position among the pairs its process aligns.")
@@ -63,8 +71,34 @@ def zscore_line(z, t):
             f"{int(z['n_ge'][t])}/{int(z['replicas'][t])} shuffles >= score)")
 
 
-def pair_block(idx, rec, params, score, trace, complete, verbose):
-    """Output lines of one pair, framed like the reference CLI (bialign.py:109-124)."""
+def span_line(start_b, end_b):
+    """The line behind ``SCORE:`` of a ``--fit`` pair: the aligned part of B, 1-based and inclusive (an empty part, where
+    all of A is gapped, reads start_b+1..start_b)."""
+    return f"B span\t {int(start_b) + 1}..{int(end_b)}"
+
+
+def fit_window(seq_b, str_b, start_b, end_b, rna):
+    """``B[start_b:end_b]`` as the decoder takes it.  RNA: a bracket whose partner lies outside the window becomes
+    ``.``, so that the window's structure is a balanced dot-bracket string again."""
+    seq, struct = seq_b[start_b:end_b], list(str_b[start_b:end_b])
+    if rna:
+        stack = []
+        for x, ch in enumerate(struct):
+            if ch == "(":
+                stack.append(x)
+            elif ch == ")":
+                if stack:
+                    stack.pop()
+                else:
+                    struct[x] = "."
+        for x in stack:
+            struct[x] = "."
+    return seq, "".join(struct)
+
+
+def pair_block(idx, rec, params, score, trace, complete, verbose, span=None):
+    """Output lines of one pair, framed like the reference CLI (bialign.py:109-124).  ``span``: ``(start_b, end_b)`` of
+    a ``--fit`` pair, whose alignment is decoded on that part of B."""
     name_a, seq_a, str_a, name_b, seq_b, str_b = rec
     yield f">pair {idx}\t{name_a}\t{name_b}"
     yield "Input:"
@@ -73,6 +107,9 @@ def pair_block(idx, rec, params, score, trace, complete, verbose):
     yield "strA\t " + str_a
     yield "strB\t " + str_b
     yield "SCORE: " + str(score)
+    if span is not None:
+        yield span_line(*span)
+        seq_b, str_b = fit_window(seq_b, str_b, int(span[0]), int(span[1]), params.get("type") == "RNA")
     yield ""
     aligner = bialignment.BiAligner(seq_a, seq_b, str_a, str_b, **dict(params, nameA=name_a, nameB=name_b))
     if not complete:
@@ -95,7 +132,7 @@ def main(argv=None):
 
 def _main(argv=None):
     args = build_parser().parse_args(argv)
-    params = {k: v for k, v in vars(args).items() if k not in ("pairs", "verbose", "score_only", "zscore", "zscore_seed")}
+    params = {k: v for k, v in vars(args).items() if k not in ("pairs", "verbose", "score_only", "zscore", "zscore_seed", "fit")}
     if args.zscore:
         from .significance import check_null
         check_null((args.zscore, args.zscore_seed))
@@ -109,24 +146,26 @@ def _main(argv=None):
     scores = []
     if len(mine):
         batch = make_batch([(r[1], r[4], r[2], r[5]) for r in (records[p] for p in mine)], params,
-                           engine=default_engine(local_rank), score_only=args.score_only)
+                           engine=default_engine(local_rank), score_only=args.score_only, fit=args.fit)
         batch.run()
         scores = batch.scores()
+        start_b, end_b = batch.fit_spans() if args.fit else (None, None)
         z = None
         if args.zscore:
             from .significance import zscores
             z = zscores([(r[1], r[4], r[2], r[5]) for r in (records[p] for p in mine)], params, replicas=args.zscore,
-                        seed=args.zscore_seed, observed=scores, engine=default_engine(local_rank))
+                        seed=args.zscore_seed, observed=scores, engine=default_engine(local_rank), fit=args.fit)
         if args.score_only:
             for t, p in enumerate(mine):
-                print(f"pair {p}\t{records[p][0]}\t{records[p][3]}\t{int(scores[t])}")
+                print(f"pair {p}\t{records[p][0]}\t{records[p][3]}\t{int(scores[t])}" + (f"\t{int(end_b[t])}" if args.fit else ""))
                 if z:
                     print(zscore_line(z, t))
         else:
             traces, complete = batch.traces()
             for t, p in enumerate(mine):
                 trace = trace_codes_to_columns(traces[t], as_tuples=not batch.affine)
-                for line in pair_block(p, records[p], params, int(scores[t]), trace, bool(complete[t]), args.verbose):
+                span = (int(start_b[t]), int(end_b[t])) if args.fit and complete[t] else None
+                for line in pair_block(p, records[p], params, int(scores[t]), trace, bool(complete[t]), args.verbose, span):
                     print(line)
                 if z:
                     print(zscore_line(z, t))

@@ -321,6 +321,7 @@ int upload_inputs(bialign_batch* b, const bialign_scoring* sc, const bialign_pai
     fprintf(stderr, "[bialign] layers %p (%.1f GiB) memset %.0f GB/s\n", (void*)b->d_layers.p, layer_dw * 4.0 / (1 << 30), gbps);
   }
   HIP_TRY(b->d_scores.alloc(pr->npairs));
+  if (b->fit) HIP_TRY(b->d_fit.alloc(2 * (size_t)pr->npairs));
   if (b->lean_trace || b->level_trace) HIP_TRY(b->d_tstate.alloc(pr->npairs));
   HIP_TRY(b->d_tlen.alloc(pr->npairs));
   HIP_TRY(b->d_complete.alloc(pr->npairs));
@@ -589,6 +590,7 @@ static int enqueue_run(bialign_batch* b, uint32_t flags) {
   b->build_launches = 0;
   HIP_TRY(hipStreamWaitEvent(st, b->uploaded, 0));
   HIP_TRY(hipMemsetAsync(b->d_err.p, 0, sizeof(int32_t), st));  // the flag is per run
+  if (b->fit) HIP_TRY(hipMemsetAsync(b->d_fit.p, 0xff, 2 * sizeof(int32_t) * b->npairs, st));  // spans: -1 until a kernel writes them
   if (b->null_R) {  // null batch: the replicas' B codes, all of them ahead of the first sweep (timed on its own, outside fill_ms)
     HIP_TRY(hipEventRecord(b->null_evs[0], st));
     if (int rc = launch_shuffle_null(b, 0, b->npairs)) return rc;
@@ -709,6 +711,19 @@ int bialign_batch_get_scores(const bialign_batch* b, int32_t* scores) {
   if (!b->ran) return fail(BIALIGN_E_INVALID, "bialign_batch_run has not been called");
   HIP_TRY(hipSetDevice(b->eng->device));
   HIP_TRY(hipMemcpy(scores, b->d_scores.p, sizeof(int32_t) * b->npairs, hipMemcpyDeviceToHost));
+  return BIALIGN_OK;
+}
+
+int bialign_batch_get_fit_spans(const bialign_batch* b, int32_t* start_b, int32_t* end_b) {
+  if (!b || !start_b || !end_b) return fail(BIALIGN_E_INVALID, "NULL argument");
+  if (!b->fit) return fail(BIALIGN_E_INVALID, "batch was created without BIALIGN_BATCH_FIT: it has no spans");
+  if (b->null_R) return fail(BIALIGN_E_INVALID, "a null batch has no observed alignments: no spans");
+  if (int rc = bialign_batch_wait(const_cast<bialign_batch*>(b))) return rc;
+  if (!b->ran) return fail(BIALIGN_E_INVALID, "bialign_batch_run has not been called");
+  HIP_TRY(hipSetDevice(b->eng->device));
+  std::vector<int32_t> span(2 * (size_t)b->npairs);
+  HIP_TRY(hipMemcpy(span.data(), b->d_fit.p, sizeof(int32_t) * span.size(), hipMemcpyDeviceToHost));
+  for (int p = 0; p < b->npairs; ++p) start_b[p] = span[2 * p], end_b[p] = span[2 * p + 1];
   return BIALIGN_OK;
 }
 

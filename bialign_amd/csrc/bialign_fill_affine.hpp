@@ -118,7 +118,7 @@ __global__ void __launch_bounds__(64 * TW) fill_affine_kernel(const DeviceBatch 
   uint8_t* cb = sb + (DENSE1 ? 0 : mpad);                   // cls B,       [l-1+PADB]
 
   for (int t = threadIdx.x; t < TW * PERW; t += 64 * TW) smem[t] = SENT;
-  if (threadIdx.x < LDS_PROG_WORDS) prog_lds[threadIdx.x] = 0;
+  if (threadIdx.x < LDS_PROG_WORDS) prog_lds[threadIdx.x] = (threadIdx.x == FIT_FLOOR_WORD && !A.fit) ? SENT : 0;
   for (int t = threadIdx.x; t < k1 * k1; t += 64 * TW) s1[t] = A.s1[t];
   for (int t = threadIdx.x; t < k2 * k2; t += 64 * TW) s2[t] = A.s2[t];
   if (!DIET)
@@ -325,6 +325,7 @@ __global__ void __launch_bounds__(64 * TW) fill_affine_kernel(const DeviceBatch 
     lookup_mu();
     fetch_codes();
   }
+  int fit_best = SENT, fit_j = 0;  // LEAN fit batches: the best end cell of row n so far and its column
 
   // One step of the sweep.  INTERIOR steps (every lane's lattice points have all
   // four coordinates >= 1 and lie inside the molecule columns; ~90 % of the
@@ -454,6 +455,7 @@ __global__ void __launch_bounds__(64 * TW) fill_affine_kernel(const DeviceBatch 
 
     const bool tile_act = INTERIOR ? true : (act_row && jj >= 0 && jj <= m);
     const bool is_origin = INTERIOR ? false : (tile_act && i == 0 && jj == 0 && aa == S);
+    const bool row0_diag = INTERIOR ? false : (tile_act && i == 0 && aa == S);  // lattice points (0, j, 0, j): a fit batch's paths may start there
     const int c3M = mu1 + dd, c_Mg = mu1 + gD;
 
     // Layer stores (pyx:504: M[state][idx] = ...).  Every real lane owns a 16-byte slot in
@@ -527,15 +529,29 @@ __global__ void __launch_bounds__(64 * TW) fill_affine_kernel(const DeviceBatch 
           M[q] = bad ? low : tv;
         }
         if (bb == S) M[8] = is_origin ? 0 : M[8];  // pyx:483-485
+        if (bb == S && row0_diag) M[8] = imax(M[8], prog_lds[FIT_FLOOR_WORD]);
       }
 #pragma unroll
       for (int q = 0; q < 9; ++q) outv[bb * 9 + q] = M[q];
       if (LEAN && bb == S) {  // score-only: the end cell (n,m,n,m) is all the host wants (pyx:509)
-        if (live && !ghost && aa == S && i == n && jj == m) {
+        if (!A.fit) {
+          if (live && !ghost && aa == S && i == n && jj == m) {
+            int best = M[0];
+#pragma unroll
+            for (int q = 1; q < 9; ++q) best = imax(best, M[q]);
+            A.scores[pid] = best;
+          }
+        } else if (live && !ghost && aa == S && i == n && (INTERIOR || (jj >= 0 && jj <= m))) {
+          // fit: row n has one owner, the lane of (n, j, n, j), which passes over the columns in order (interior steps
+          // included): the best end cell and the smallest column that attains it stay in its registers
           int best = M[0];
 #pragma unroll
           for (int q = 1; q < 9; ++q) best = imax(best, M[q]);
-          A.scores[pid] = best;
+          if (best > fit_best) fit_best = best, fit_j = jj;
+          if (jj == m) {
+            A.scores[pid] = fit_best;
+            A.fit_span[2 * pid + 1] = fit_j;
+          }
         }
       }
       if (PACK && INTERIOR) {

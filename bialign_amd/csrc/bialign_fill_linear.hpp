@@ -66,7 +66,7 @@ __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch 
   uint8_t* cb = sb + (DENSE1 ? 0 : mpad);
 
   for (int t = threadIdx.x; t < TW * PERW; t += 64 * TW) smem[t] = SENT;
-  if (threadIdx.x < LDS_PROG_WORDS) prog[threadIdx.x] = 0;
+  if (threadIdx.x < LDS_PROG_WORDS) prog[threadIdx.x] = (threadIdx.x == FIT_FLOOR_WORD && !A.fit) ? SENT : 0;
   for (int t = threadIdx.x; t < k1 * k1; t += 64 * TW) s1[t] = A.s1[t];
   for (int t = threadIdx.x; t < k2 * k2; t += 64 * TW) s2[t] = A.s2[t];
   for (int t = threadIdx.x; t < n; t += 64 * TW) {
@@ -166,6 +166,7 @@ __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch 
   prefetch_block(0, 0, jj);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   int vm_younger = 0;  // see the affine kernel
+  int fit_best = SENT, fit_j = 0;  // LEAN fit batches: the best end cell of row n so far and its column
 
   for (int g = 0; g < H; ++g) {
     const int gt = g & (GF::BLK - 1), ghalf = (g / GF::BLK) & 1;
@@ -206,6 +207,7 @@ __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch 
 
     const bool tile_act = act_row && jj >= 0 && jj <= m;
     const bool is_origin = tile_act && i == 0 && jj == 0 && aa == S;
+    const bool row0_diag = tile_act && i == 0 && aa == S;  // lattice points (0, j, 0, j): a fit batch's paths may start there
     const int c4 = mu1 + delta, c12 = mu1 + gD;
 
     int outv[ND];
@@ -235,6 +237,7 @@ __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch 
       const bool bad = (tv < THRESH) | !act;
       int M = bad ? (act ? NEG : SENT) : tv;             // pyx:299-303
       if (bb == S) M = is_origin ? 0 : M;                // np.zeros origin (pyx:27, 464-465)
+      if (bb == S && row0_diag) M = imax(M, prog[FIT_FLOOR_WORD]);
       outv[bb] = M;
       prev = M;
     }
@@ -249,7 +252,16 @@ __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch 
     }
 
     const int rec = g + rec_base;
-    if (LEAN && live && !ghost && aa == S && i == n && jj == m) A.scores[pid] = outv[S];  // pyx:471
+    if (LEAN && !A.fit && live && !ghost && aa == S && i == n && jj == m) A.scores[pid] = outv[S];  // pyx:471
+    if (LEAN && A.fit && live && !ghost && aa == S && i == n && jj >= 0 && jj <= m) {
+      // fit: row n has one owner, the lane of (n, j, n, j), which passes over the columns in order: the best end cell
+      // and the smallest column that attains it stay in its registers
+      if (outv[S] > fit_best) fit_best = outv[S], fit_j = jj;
+      if (jj == m) {
+        A.scores[pid] = fit_best;
+        A.fit_span[2 * pid + 1] = fit_j;
+      }
+    }
     const int pad_idx = L < W ? L : (L >= R * W ? W + (L - R * W) : 64);
     const bool pad_lane = !LEAN && pad_idx < R_::SLP - R_::SL;  // spare lanes owning a pad slot (Rec::SLP)
     const bool do_store = __builtin_amdgcn_ballot_w64(tile_act && !ghost) != 0 &&

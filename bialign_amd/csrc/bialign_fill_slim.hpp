@@ -78,6 +78,7 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
   v4i* ring = reinterpret_cast<v4i*>(smem + wv * GF::RING_DW);        // ghost-row ring, two halves
   int32_t* sentblk = smem + NW * PERW;
   volatile int32_t* prog_lds = smem + NW * PERW + SENTBLK + pw * TW;  // [16]: this team's words
+  const volatile int32_t* const fit_floor = smem + NW * PERW + SENTBLK + FIT_FLOOR_WORD;  // (a constant LDS address)
   // the ghost feed's lane offsets of a steady block (GhostFeed::issue_steady), [round][lane]; one table per workgroup
   // (packed records only: the LEAN form leaves it unused)
   int32_t* offtab = smem + NW * PERW + SENTBLK + LDS_PROG_WORDS;
@@ -91,7 +92,7 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
   uint8_t* cb = sb + mpad;                                  // cls B,       [l-1+PADB]
 
   for (int t = threadIdx.x; t < NW * PERW + SENTBLK; t += 64 * NW) smem[t] = SENT;
-  if (threadIdx.x < LDS_PROG_WORDS) smem[NW * PERW + SENTBLK + threadIdx.x] = 0;
+  if (threadIdx.x < LDS_PROG_WORDS) smem[NW * PERW + SENTBLK + threadIdx.x] = (threadIdx.x == FIT_FLOOR_WORD && !A.fit) ? SENT : 0;
   if (!LEAN)
     for (int t = threadIdx.x; t < GF::OFFTAB_DW; t += 64 * NW) offtab[t] = (int32_t)GF::lane_offset(t >> 6, t & 63);
   for (int t = threadIdx.x; t < k1 * k1; t += 64 * NW) s1[t] = A.s1[t];
@@ -246,6 +247,7 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
   };
   lookup_mu();
   fetch_codes(BoolTag<true>{});
+  int fit_best = SENT, fit_j = 0;  // LEAN fit batches: the best end cell of row n so far and its column
 
   auto step = [&](auto interior_tag, int g) __attribute__((always_inline)) {
     constexpr bool INTERIOR = decltype(interior_tag)::value;
@@ -338,6 +340,7 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
 
     const bool tile_act = INTERIOR ? true : (act_row && jj >= 0 && jj <= m);
     const bool is_origin = INTERIOR ? false : (tile_act && i == 0 && jj == 0 && aa == S);
+    const bool row0_diag = INTERIOR ? false : (tile_act && i == 0 && aa == S);  // lattice points (0, j, 0, j): a fit batch's paths may start there
     const int c3M = mu1 + dd, c_Mg = mu1 + gD;
 
     // ---- layer stores (as fill_affine_kernel: every real lane stores every active step, spare lanes fill the pad slots)
@@ -414,6 +417,7 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
           M[q] = bad ? low : tv;
         }
         if (bb == S) M[8] = is_origin ? 0 : M[8];  // pyx:483-485
+        if (bb == S && row0_diag) M[8] = imax(M[8], fit_floor[0]);
       }
       if (!PACKED) {
 #pragma unroll
@@ -421,11 +425,26 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
       }
       if (LEAN && bb == S) {  // score-only: the end cell (n,m,n,m) is all the host wants (pyx:509)
         // (an interior step is never at column m; its jj is not the column either: see s_adv)
-        if (!INTERIOR && live && !ghost && aa == S && i == n && jj == m) {
+        if (!INTERIOR && live && !ghost && aa == S && i == n && jj == m && !A.fit) {
           int best = M[0];
 #pragma unroll
           for (int q = 1; q < 9; ++q) best = imax(best, M[q]);
           A.scores[pid] = best;
+        }
+        if (A.fit) {
+          // fit: row n has one owner, the lane of (n, j, n, j), which passes over the columns in order (interior steps
+          // included): the best end cell and the smallest column that attains it stay in its registers
+          const int col = INTERIOR ? jj + s_adv : jj;
+          if (live && !ghost && aa == S && i == n && (INTERIOR || (col >= 0 && col <= m))) {
+            int best = M[0];
+#pragma unroll
+            for (int q = 1; q < 9; ++q) best = imax(best, M[q]);
+            if (best > fit_best) fit_best = best, fit_j = col;
+            if (!INTERIOR && col == m) {
+              A.scores[pid] = fit_best;
+              A.fit_span[2 * pid + 1] = fit_j;
+            }
+          }
         }
       }
       if (PACKED) {

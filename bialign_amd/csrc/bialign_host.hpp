@@ -86,6 +86,7 @@ struct bialign_batch : bialign::BatchPlan {  // the plan (bialign_plan.hpp), and
   bialign_engine* eng = nullptr;
   DevBuf<PairDesc> d_pairs;
   DevBuf<int32_t> d_order, d_s1, d_s2, d_layers, d_scores, d_tlen, d_complete, d_err, d_prog;
+  DevBuf<int32_t> d_fit;  // fit alignments (BatchPlan::fit): [npairs][2] = (start_b, end_b), -1 ahead of every run
   int last_team = 1;  // waves per pair of the last fill launch (negative: cross-CU team)
   // Cross-CU teams need every workgroup of the launch resident at once.  The grid is sized from the
   // occupancy the runtime reports for the actual kernel (xcu_resident, cached per LEAN flavour) and
@@ -170,6 +171,8 @@ struct bialign_batch : bialign::BatchPlan {  // the plan (bialign_plan.hpp), and
     v.wide_s = S;
     v.prio_mode = getenv("BIALIGN_PRIO") ? atoi(getenv("BIALIGN_PRIO")) : 1;
     v.spin_limit = 1 << 20;  // waves of one workgroup are co-resident by construction: a timeout there is a bug
+    v.fit = fit ? 1 : 0;
+    v.fit_span = d_fit.p;
     return v;
   }
 };
@@ -473,12 +476,13 @@ bool trace_fast_admits(const PairDesc& d) {
 }
 // LDS of a launch of the fast kernel: the staged inputs, the candidate table, and the trace buffer -- the longest trace
 // of the launch if the workgroup can spare it (BIALIGN_TRACE_LDS: tests, a smaller buffer), else flushed in pieces.
-// 0: the generic kernel serves (BIALIGN_TRACE_FAST=0: tests / A-B; dense mu2; a pair not admitted).
+// 0: the generic kernel serves (BIALIGN_TRACE_FAST=0: tests / A-B; dense mu2; a FIT batch; a pair not admitted).
 constexpr int TRACE_FAST_TBUF_MAX = 16 * 1024;
 template <int S>
 size_t trace_fast_lds(const bialign_batch* b, int first, int count, int* tbuf) {
   const char* sw = getenv("BIALIGN_TRACE_FAST");  // "0": tests / A-B, the generic kernel only
   if ((sw && atoi(sw) == 0) || b->dense || b->dense1 || b->wide || b->lean) return 0;
+  if (b->fit) return 0;  // fit alignments take the generic walk: the short-chain kernel has neither the end scan nor the stop rule
   int cap = 0;
   for (int t = first; t < first + count; ++t) {
     const PairDesc& d = b->pairs[b->order[t]];

@@ -72,6 +72,9 @@ struct BatchPlan {
   bool level_trace = false;
   int wide_seg = 0;
   int resw_k = 1;           // strips re-swept and walked per round (more when the batch has few pairs)
+  // Fit alignments (BIALIGN_BATCH_FIT): free end gaps in B.  Tiled bands, full storage or SCORE_ONLY; the generic
+  // tracebacks only (host: trace_fast_lds); never the storage ladder's LEAN_TRACE rung (plan_storage: BIALIGN_E_NOMEM).
+  bool fit = false;
 };
 
 // What the host needs of the kernels' compile-time geometry, for a run-time (max_shift, recurrence): read from the types
@@ -464,6 +467,13 @@ inline int check_inputs(const bialign_params* prm, const bialign_scoring* sc, co
   b.lean_trace = (prm->flags & BIALIGN_BATCH_LEAN_TRACE) != 0;
   b.lean = b.lean_trace || (prm->flags & BIALIGN_BATCH_SCORE_ONLY) != 0;
   b.wide = prm->max_shift > BIALIGN_MAX_SHIFT_TILED;  // bialign_wide.hpp: anti-diagonal path, all layers in HBM
+  constexpr uint32_t KNOWN_FLAGS = BIALIGN_BATCH_SCORE_ONLY | BIALIGN_BATCH_LEAN_TRACE | BIALIGN_BATCH_LEVEL_TRACE | BIALIGN_BATCH_FIT;
+  if (prm->flags & ~KNOWN_FLAGS) return fail(BIALIGN_E_INVALID, "unknown bits 0x%x in bialign_params.flags", prm->flags & ~KNOWN_FLAGS);
+  b.fit = (prm->flags & BIALIGN_BATCH_FIT) != 0;
+  if (b.fit && (prm->flags & (BIALIGN_BATCH_LEAN_TRACE | BIALIGN_BATCH_LEVEL_TRACE)))
+    return fail(BIALIGN_E_UNSUPPORTED, "FIT exists in full storage and in SCORE_ONLY: not with LEAN_TRACE or LEVEL_TRACE");
+  if (b.fit && b.wide)
+    return fail(BIALIGN_E_UNSUPPORTED, "FIT exists for max_shift <= %d only (the tiled sweeps)", BIALIGN_MAX_SHIFT_TILED);
   if (prm->flags & BIALIGN_BATCH_LEVEL_TRACE) {
     if (b.lean) return fail(BIALIGN_E_INVALID, "LEVEL_TRACE excludes SCORE_ONLY and LEAN_TRACE");
     if (!b.wide)
@@ -713,6 +723,9 @@ inline int plan_storage(BatchPlan& b, int64_t budget_dw) {
     }
   }
   if (!b.lean && !b.wide && max_need() > budget_dw) {
+    if (b.fit)  // no silent change of mode: the memory-lean traceback has no FIT form
+      return fail(BIALIGN_E_NOMEM, "a pair needs %lld bytes of layers, budget is %lld: a FIT batch does not fall back to LEAN_TRACE",
+                  (long long)max_need() * 4, (long long)budget_dw * 4);
     b.lean = b.lean_trace = true;
     b.pack = false;
     pick_resw_k();
@@ -778,7 +791,9 @@ inline int expand_null_pairs(const bialign_params* prm, const bialign_pairs* pr,
   if (!mu1_off.empty()) vp.mu1_off = mu1_off.data();
   if (!mu2_off.empty()) vp.mu2_off = mu2_off.data();
   plan.vprm = *prm;
-  plan.vprm.flags = BIALIGN_BATCH_SCORE_ONLY;
+  // SCORE_ONLY is forced (the caller refused LEAN_TRACE / LEVEL_TRACE); FIT passes through -- the replicas are scored in
+  // the observed batch's mode -- and so do unknown bits, for check_inputs to refuse
+  plan.vprm.flags = BIALIGN_BATCH_SCORE_ONLY | (prm->flags & ~(uint32_t)(BIALIGN_BATCH_LEAN_TRACE | BIALIGN_BATCH_LEVEL_TRACE));
   return BIALIGN_OK;
 }
 

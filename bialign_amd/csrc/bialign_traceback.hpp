@@ -56,6 +56,25 @@ __device__ __forceinline__ int wave_min16(int v) {  // min over lanes 0..15, val
   v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x121 /* row_ror:1 */, 0xf, 0xf, false));
   return v;
 }
+__device__ __forceinline__ int wave_min64(int v) {  // min over the wave's 64 lanes (all active), wave-uniform
+  v = wave_min16(v);  // every row of 16 lanes reduces by itself
+  return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
+             min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+// Fit alignments (DeviceBatch::fit), end rule of the full-storage tracebacks: the wave's lanes stride over the end cells
+// (n, j, n, j), j = 0..m, whose value end_cell(j) reads through the kernel's own cell addressing, and reduce to the best
+// one and the smallest column that attains it.
+template <typename EndCell>
+__device__ __forceinline__ void fit_end_scan(int m, int lane, EndCell&& end_cell, int* best, int* end_b) {
+  constexpr int BIG = 0x7fffffff;
+  int bv = -BIG, bj = 0;
+  for (int x = lane; x <= m; x += 64) {
+    const int e = end_cell(x);
+    if (e > bv) bv = e, bj = x;
+  }
+  *best = -wave_min64(-bv);
+  *end_b = wave_min64(bv == *best ? bj : BIG);
+}
 
 //   STRIP (lean traceback): the walk continues from the pair's
 //   TraceState through ONE strip -- the one fill_affine_kernel<.., RESW> has just re-swept into
@@ -114,9 +133,24 @@ __global__ void __launch_bounds__(64) traceback_affine_kernel(const DeviceBatch 
 
   int i = n, j = m, k = n, l = m, d0 = 0, d1 = 0, len = 0, complete = 0;
   int st = 0, cur = 0;
+  constexpr bool FIT_FORM = !STRIP && !WIDE && !LEVEL;  // fit alignments: the tiled full-storage forms
+  const bool fit = FIT_FORM && A.fit;
   if (!(STRIP || LEVEL) || !ts.started) {
+    if (fit) {  // the walk starts at the best end cell (n, end_b, n, end_b)
+      int fbest, fend;
+      fit_end_scan(m, c, [&](int x) {
+        int e = cell(n, x, SR, SR, 0);
+        for (int q = 1; q < 9; ++q) e = max(e, cell(n, x, SR, SR, q));
+        return e;
+      }, &fbest, &fend);
+      j = l = fend;
+      if (c == 0) {
+        A.fit_span[2 * pid] = -1;
+        A.fit_span[2 * pid + 1] = fend;
+      }
+    }
     // pyx:573-582: best end layer, first one with the least shift
-    const int endv = c < 9 ? cell(n, m, SR, SR, c) : -BIG;
+    const int endv = c < 9 ? cell(n, j, SR, SR, c) : -BIG;
     const int best = __builtin_amdgcn_readfirstlane(-wave_min16(-endv));
     if (c == 0) A.scores[pid] = best;
     if (!DO_TRACE) return;
@@ -137,6 +171,7 @@ __global__ void __launch_bounds__(64) traceback_affine_kernel(const DeviceBatch 
   const int hfree = grp == 2 ? 2 - (c - 9) : 2 - (c - 12);  // h = M, X, Y in the generator's order
   while (true) {
     if (i == 0 && j == 0 && k == 0 && l == 0 && st == 8) { complete = 1; break; }
+    if (fit && i == 0 && k == 0 && j == l && st == 8 && cur == 0) { complete = 1; break; }  // fit: a free start, start_b = j
     if (STRIP && i < Qlo * RR) { finished = false; break; }  // above the re-swept strips: next round
     if (LEVEL && seg > 0 && i + j + k + l < seg_base + WIDE_SEG_OVERLAP) { finished = false; break; }  // a candidate may lie below the scratch
     const int hU = st / 3, hV = st - 3 * hU;
@@ -201,6 +236,7 @@ __global__ void __launch_bounds__(64) traceback_affine_kernel(const DeviceBatch 
   if (c == 0) {
     A.trace_len[pid] = len;
     A.complete[pid] = complete;
+    if (fit && complete) A.fit_span[2 * pid] = j;
     if (STRIP || LEVEL) {
       ts.done = 1;
       ts.started = 1;
@@ -248,7 +284,18 @@ __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch 
       return A.scratch[pd.scratch_off + (Q - sp) * sstride + Rec<S, 1>::dword(pj + 2 * ilp + a, (ilp - 1) * W + a, b)];
     return lay[pd.layer_off + Rec<S, 1, true>::dword((int64_t)sp * pd.P + pj + 2 * ilp + a, a, b)];
   };
-  int cur = (CONT && ts.started) ? ts.cur : cell(n, m, SR, SR);
+  constexpr bool FIT_FORM = !STRIP && !WIDE && !LEVEL;  // fit alignments: the tiled full-storage forms
+  const bool fit = FIT_FORM && A.fit;
+  int jend = m;
+  if (fit) {  // the walk starts at the best end cell (n, end_b, n, end_b)
+    int fbest;
+    fit_end_scan(m, c, [&](int x) { return cell(n, x, SR, SR); }, &fbest, &jend);
+    if (c == 0) {
+      A.fit_span[2 * pid] = -1;
+      A.fit_span[2 * pid + 1] = jend;
+    }
+  }
+  int cur = (CONT && ts.started) ? ts.cur : cell(n, jend, SR, SR);
   if (c == 0 && !(CONT && ts.started)) A.scores[pid] = cur;  // pyx:471
   if (!DO_TRACE) return;
   const TraceInputs in = stage_trace_inputs<D1>(A, pd, smem);
@@ -268,10 +315,11 @@ __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch 
   const int kconst = c == 0 ? 0 : (c <= 2 ? 2 * gamma : (c <= 4 ? delta : gD));
 
   uint8_t* out = A.trace + pd.trace_off;
-  int i = n, j = m, k = n, l = m, len = 0;
+  int i = n, j = jend, k = n, l = jend, len = 0;
   if (CONT && ts.started) { i = ts.i; j = ts.j; k = ts.k; l = ts.l; len = ts.len; }
   bool finished = true;
   while (true) {
+    if (fit && i == 0 && k == 0 && j == l && cur == 0) break;  // fit: a free start, start_b = j
     if (STRIP && i < Qlo * RR) { finished = false; break; }
     if (LEVEL && seg > 0 && i + j + k + l < seg_base + WIDE_SEG_OVERLAP) { finished = false; break; }
     const int mu1 = (i >= 1 && j >= 1)
@@ -315,6 +363,7 @@ __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch 
   if (c == 0) {
     A.trace_len[pid] = len;
     A.complete[pid] = 1;
+    if (fit) A.fit_span[2 * pid] = j;
     if (CONT) {
       ts.done = 1;
       ts.started = 1;

@@ -9,6 +9,11 @@ constexpr int32_t THRESH = -(1 << 30) - (1 << 28);  // below: no valid case
 constexpr int NCOL = 65;                            // 64 lanes + 1 sentinel column
 constexpr int PROG_WORDS = 256;                     // cross-CU teams: progress words per pair = largest team
 constexpr int LDS_PROG_WORDS = 16;                  // in-workgroup teams: progress words of a workgroup, in LDS
+// The last of them (teams have at most twelve waves) holds the floor under the value at the lattice points (0, j, 0, j):
+// 0 in a fit batch (DeviceBatch::fit: a path may start there), else the sentinel, under which no value of a lattice point
+// lies.  The sweeps' prologue writes it; boundary steps read it back where row 0 is computed, so the mode costs the
+// interior loops neither a register nor an instruction.
+constexpr int FIT_FLOOR_WORD = LDS_PROG_WORDS - 1;
 constexpr int XCH_ROWS = 12;                        // affine sweeps: exchange rows per lattice point that go through LDS
 // Bytes one array of a molecule's codes takes in LDS: whole dwords, `guard` bytes around (B's codes in the sweeps: Geo<S>::PADB)
 __host__ __device__ constexpr int code_pad(int len, int guard = 0) { return (len + 2 * guard + 3) & ~3; }
@@ -68,8 +73,14 @@ struct DeviceBatch {
   // dense_tab (non-null = dense mu2); those built for a dense mu1 read the bits.  (It fills what was the struct's
   // tail padding: the kernel argument block of the existing kernels keeps its size.)
   int32_t dense_forms;
+  // Fit alignments (BIALIGN_BATCH_FIT, DESIGN.md "Fit alignments"): free end gaps in B.  Wave-uniform; the sweeps read it
+  // in their prologue (FIT_FLOOR_WORD, applied in boundary steps where is_origin is tested) and, LEAN forms, where the
+  // end cell's score is written; the generic tracebacks in their prologue and stop test.
+  // fit_span: [npairs][2] = (start_b, end_b), -1 until written.
+  int32_t fit;
+  int32_t* fit_span;
 };
-static_assert(sizeof(DeviceBatch) == 224, "DeviceBatch grew: the kernels' argument blocks would change");
+static_assert(sizeof(DeviceBatch) == 240, "DeviceBatch grew: the kernels' argument blocks would change");
 
 // Dense mu1 (DeviceBatch::dense_forms bit 1): pair pd's n x m table, mu1(i,j) at [(i-1)*m + (j-1)].  It follows the
 // pair's mu2 table when that one is dense too.

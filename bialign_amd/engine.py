@@ -101,11 +101,16 @@ class Batch:
     table, and the GPU permutes the columns of the one uploaded copy of the tables per replica, chunk by chunk.  The other
     of mu1 / mu2 may stay in LOOKUP form.  Excludes ``null``, ``mu2_features``, ``lean_trace`` and ``level_trace``; the
     tables must be of an integer dtype.  Results as for ``null``; ``null_tables()`` shows a replica's tables.
+    ``fit``: fit alignments (BIALIGN_BATCH_FIT): A inside a longer B, B's end gaps free.  ``scores()`` is the best
+    global score of A against any substring of B, ``traces()`` that alignment, ``fit_spans()`` the substring.  Bands
+    up to ``_lib.MAX_SHIFT_TILED``, full storage or ``score_only`` (and so null batches: the replicas are scored in
+    the same mode); not with ``lean_trace`` / ``level_trace``.
     """
 
     def __init__(self, engine, mols_a, mols_b, s1, s2, gap_opening_cost, gap_cost, shift_cost,
                  max_shift, hbm_budget_bytes=0, recurrence=0, mu2_dense=None, score_only=False,
-                 lean_trace=False, mu1_dense=None, mu2_features=None, level_trace=False, null=None, null_dense=None):
+                 lean_trace=False, mu1_dense=None, mu2_features=None, level_trace=False, null=None, null_dense=None,
+                 fit=False):
         null_kind = "dense" if null_dense is not None else ("lookup" if null is not None else None)
         if null_dense is not None:
             if mu1_dense is None and mu2_dense is None:
@@ -172,7 +177,7 @@ class Batch:
         prm = _lib.Params(int(gap_opening_cost), int(gap_cost), int(shift_cost), int(max_shift),
                           int(recurrence), (_lib.BATCH_SCORE_ONLY if score_only else 0) |
                           (_lib.BATCH_LEAN_TRACE if lean_trace else 0) |
-                          (_lib.BATCH_LEVEL_TRACE if level_trace else 0))
+                          (_lib.BATCH_LEVEL_TRACE if level_trace else 0) | (_lib.BATCH_FIT if fit else 0))
         sc = _lib.Scoring(s1.shape[0], _ptr(s1, ctypes.c_int32), s2.shape[0], _ptr(s2, ctypes.c_int32))
         pr = _lib.Pairs(self.npairs, _ptr(self.len_a, ctypes.c_int32), _ptr(self.len_b, ctypes.c_int32),
                         _ptr(off_a, ctypes.c_int64), _ptr(off_b, ctypes.c_int64),
@@ -181,6 +186,7 @@ class Batch:
                         mu1_ptr, mu1_off_ptr)
         self._h = ctypes.c_void_p()
         self.replicas = None
+        self.fit = bool(fit)
         self._null_forms = (mu1_flat is not None, mu2_flat is not None) if null_dense is not None else None
         args = [engine._h, ctypes.byref(prm), ctypes.byref(sc), ctypes.byref(pr)]
         if feat is not None:
@@ -367,6 +373,13 @@ class Batch:
         check(lib.bialign_batch_get_traces(self._h, _ptr(buf, ctypes.c_uint8), _ptr(off, ctypes.c_int64),
                                            _ptr(ln, ctypes.c_int32), _ptr(ok, ctypes.c_int32)))
         return [buf[off[p]:off[p] + ln[p]].copy() for p in range(self.npairs)], ok.astype(bool)
+
+    def fit_spans(self):
+        """Fit batch: ``(start_b, end_b)`` as int32 arrays -- pair p's alignment is that of A with
+        ``B[start_b[p]:end_b[p]]``.  After a score-only or fill-only run ``start_b`` is -1."""
+        start, end = np.empty(self.npairs, dtype=np.int32), np.empty(self.npairs, dtype=np.int32)
+        check(lib.bialign_batch_get_fit_spans(self._h, _ptr(start, ctypes.c_int32), _ptr(end, ctypes.c_int32)))
+        return start, end
 
     def dump_layers(self, pair):
         """Layers of one pair in the reference layout [layer][i][j][k-i+s][l-j+s]."""

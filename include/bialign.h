@@ -91,6 +91,35 @@ extern "C" {
  * bialign_batch_dump_layers fails with BIALIGN_E_INVALID.  The engine takes this mode by itself when a wide-band
  * pair's full layers exceed the HBM budget (bialign_batch_info.storage says so). */
 #define BIALIGN_BATCH_LEVEL_TRACE 4u
+/* FIT (new in ABI 10 as added symbols: no existing struct or function changes): fit alignments -- molecule A inside a
+ * longer molecule B, with free end gaps in B (a domain in a whole protein, a motif in a transcript).  The recurrence,
+ * the guards and the band are unchanged.  The mode makes the following changes.
+ *   Start.  At every lattice point (0, j, 0, j) with j >= 1, the value that the origin's 0 occupies today becomes
+ *     max(recurrence value, 0).  In the affine recurrence that value is state 8, (M,M).  In the one-layer recurrence it
+ *     is the cell's one value.  The origin stays 0.  All other states and cells are computed as before.
+ *   End.  score = max over j in 0..m of E(j).  In the affine recurrence E(j) is the maximum of the nine states at
+ *     (n, j, n, j).  In the one-layer recurrence it is that cell's value.  end_b is the smallest j that attains the maximum.
+ *   Walk.  The traceback starts at (n, end_b, n, end_b).  In the affine recurrence it starts in the best state there,
+ *     with ties between states broken as today at (n, m, n, m).  It applies the existing tie-breaks, unchanged.  It
+ *     stops, complete, the first time it stands on a point (0, j, 0, j) whose stored value is exactly 0.  In the affine
+ *     recurrence the walk must also be in state 8.  The walk is checked once on arrival, before it picks a predecessor.
+ *     So start_b = j.  The origin satisfies this stop rule as it does today.  The trace describes the global alignment
+ *     of A with B[start_b:end_b], in the existing byte code.
+ *   Equivalence.  Write `global` for the reference's optimize() score.  For costs that keep the int32 safety window
+ *     (unchanged, as the per-column bound is unchanged), the fit score is
+ *     max over 0 <= j0 <= j1 <= m of global(A, B[j0:j1]).  The empty substring is included.  Its value is the layer
+ *     value at (n, 0, n, 0).
+ * Only B's ends are free and A is consumed whole.  A caller who wants the other direction swaps the molecules.
+ * Accepted for max_shift <= BIALIGN_MAX_SHIFT_TILED, both recurrences, every form of mu1 and mu2, in full storage and
+ * with SCORE_ONLY (so in all three bialign_batch_create_null* entry points, which pass it through: the replicas are
+ * scored in the same mode).  With LEAN_TRACE or LEVEL_TRACE, or beyond the tiled band: BIALIGN_E_UNSUPPORTED.  A FIT
+ * batch never changes its storage mode by itself: where a pair's full layers exceed the HBM budget the engine's
+ * fallback to LEAN_TRACE is BIALIGN_E_NOMEM instead.  bialign_batch_get_scores returns the fit score,
+ * bialign_batch_get_traces the walk above (complete keeps its meaning), bialign_batch_dump_layers the FIT layers,
+ * bialign_batch_get_fit_spans the spans.  A BIALIGN_RUN_FILL_ONLY run of a full-storage FIT batch leaves the fit scores
+ * and end_b (as such a run of any full-storage batch leaves the scores: the traceback kernel's prologue writes them). */
+#define BIALIGN_BATCH_FIT 8u
+/* Bits of bialign_params.flags beyond the ones above: BIALIGN_E_INVALID. */
 
 typedef struct bialign_engine bialign_engine; /* one per (process, device) */
 typedef struct bialign_batch bialign_batch;   /* inputs resident in HBM */
@@ -329,6 +358,12 @@ int bialign_batch_get_scores(const bialign_batch* b, int32_t* scores /* [npairs]
  * bialign_batch_info.trace_bytes bytes. */
 int bialign_batch_get_traces(const bialign_batch* b, uint8_t* trace, int64_t* trace_off,
                              int32_t* trace_len, int32_t* complete);
+
+/* Fit alignments (BIALIGN_BATCH_FIT, new in ABI 10 as an added symbol): pair p's alignment is that of A with B[start_b[p]:end_b[p]] (0-based,
+ * half open).  Both arrays are [npairs].  A batch created without FIT, or a null batch (it has no observed alignments):
+ * BIALIGN_E_INVALID.  After a SCORE_ONLY or
+ * BIALIGN_RUN_FILL_ONLY run end_b is valid and start_b[p] = -1 (so it is for a pair whose traceback is incomplete). */
+int bialign_batch_get_fit_spans(const bialign_batch* b, int32_t* start_b, int32_t* end_b);
 
 /* Test / introspection hooks.
  * dump_layers re-runs the fill of one pair and writes its layers in the
