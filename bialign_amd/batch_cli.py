@@ -18,6 +18,12 @@ of B (``bialign_amd.significance``; the shuffles are made and scored on the GPU)
 gaps in B: include/bialign.h, BIALIGN_BATCH_FIT).  The alignment is decoded on that substring, one extra line
 ``B span\t <start_b+1>..<end_b>`` (1-based, inclusive) follows ``SCORE:``, ``--score_only`` lines gain the 1-based end
 as a fourth column, and ``--zscore`` scores the shuffles in the same mode.
+
+``--local`` aligns the best-scoring part of every pair's molecule A with the best-scoring part of its molecule B (local
+alignments, the ends of both molecules free: include/bialign.h, BIALIGN_BATCH_LOCAL; not with ``--fit``).  Two extra
+lines ``A span\t <start_a+1>..<end_a>`` and ``B span\t <start_b+1>..<end_b>`` (1-based, inclusive) follow ``SCORE:``,
+the alignment is decoded on the two windows, ``--score_only`` lines gain the 1-based ends of A and B as a fourth and
+fifth column, and ``--zscore`` scores the shuffles in the same mode.
 """
 import argparse
 import sys
@@ -59,6 +65,10 @@ def build_parser():
     p.add_argument("--fit", action="store_true",
                    help="Fit alignments: molecule A against the best substring of molecule B (B's end gaps are free); "
                         "prints the substring as a 'B span' line behind 'SCORE:'.")
+    p.add_argument("--local", action="store_true",
+                   help="Local alignments: the best-scoring part of molecule A against the best-scoring part of molecule "
+                        "B (the ends of both are free); prints the parts as 'A span' and 'B span' lines behind 'SCORE:'. "
+                        "Not with --fit.")
     p.add_argument("--zscore_seed", type=int, default=0, metavar="N",
                    help="Seed of the shuffles (default 0); shuffle r of a pair is a function of the seed, r and the "
                         "pair's position among the pairs its process aligns.")
@@ -75,6 +85,12 @@ def span_line(start_b, end_b):
     """The line behind ``SCORE:`` of a ``--fit`` pair: the aligned part of B, 1-based and inclusive (an empty part, where
     all of A is gapped, reads start_b+1..start_b)."""
     return f"B span\t {int(start_b) + 1}..{int(end_b)}"
+
+
+def local_span_lines(start_a, end_a, start_b, end_b):
+    """The lines behind ``SCORE:`` of a ``--local`` pair: the aligned parts of A and B, 1-based and inclusive (an empty
+    part reads start+1..start)."""
+    return [f"A span\t {int(start_a) + 1}..{int(end_a)}", span_line(start_b, end_b)]
 
 
 def fit_window(seq_b, str_b, start_b, end_b, rna):
@@ -96,9 +112,10 @@ def fit_window(seq_b, str_b, start_b, end_b, rna):
     return seq, "".join(struct)
 
 
-def pair_block(idx, rec, params, score, trace, complete, verbose, span=None):
+def pair_block(idx, rec, params, score, trace, complete, verbose, span=None, local_span=None):
     """Output lines of one pair, framed like the reference CLI (bialign.py:109-124).  ``span``: ``(start_b, end_b)`` of
-    a ``--fit`` pair, whose alignment is decoded on that part of B."""
+    a ``--fit`` pair, whose alignment is decoded on that part of B.  ``local_span``: ``(start_a, end_a, start_b, end_b)``
+    of a ``--local`` pair, whose alignment is decoded on those parts of A and B."""
     name_a, seq_a, str_a, name_b, seq_b, str_b = rec
     yield f">pair {idx}\t{name_a}\t{name_b}"
     yield "Input:"
@@ -110,6 +127,11 @@ def pair_block(idx, rec, params, score, trace, complete, verbose, span=None):
     if span is not None:
         yield span_line(*span)
         seq_b, str_b = fit_window(seq_b, str_b, int(span[0]), int(span[1]), params.get("type") == "RNA")
+    if local_span is not None:
+        yield from local_span_lines(*local_span)
+        rna = params.get("type") == "RNA"
+        seq_a, str_a = fit_window(seq_a, str_a, int(local_span[0]), int(local_span[1]), rna)
+        seq_b, str_b = fit_window(seq_b, str_b, int(local_span[2]), int(local_span[3]), rna)
     yield ""
     aligner = bialignment.BiAligner(seq_a, seq_b, str_a, str_b, **dict(params, nameA=name_a, nameB=name_b))
     if not complete:
@@ -131,8 +153,12 @@ def main(argv=None):
 
 
 def _main(argv=None):
-    args = build_parser().parse_args(argv)
-    params = {k: v for k, v in vars(args).items() if k not in ("pairs", "verbose", "score_only", "zscore", "zscore_seed", "fit")}
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.fit and args.local:
+        parser.error("--fit and --local exclude each other")
+    params = {k: v for k, v in vars(args).items()
+              if k not in ("pairs", "verbose", "score_only", "zscore", "zscore_seed", "fit", "local")}
     if args.zscore:
         from .significance import check_null
         check_null((args.zscore, args.zscore_seed))
@@ -146,18 +172,21 @@ def _main(argv=None):
     scores = []
     if len(mine):
         batch = make_batch([(r[1], r[4], r[2], r[5]) for r in (records[p] for p in mine)], params,
-                           engine=default_engine(local_rank), score_only=args.score_only, fit=args.fit)
+                           engine=default_engine(local_rank), score_only=args.score_only, fit=args.fit,
+                           local=args.local)
         batch.run()
         scores = batch.scores()
         start_b, end_b = batch.fit_spans() if args.fit else (None, None)
+        lspans = batch.local_spans() if args.local else None
         z = None
         if args.zscore:
             from .significance import zscores
             z = zscores([(r[1], r[4], r[2], r[5]) for r in (records[p] for p in mine)], params, replicas=args.zscore,
-                        seed=args.zscore_seed, observed=scores, engine=default_engine(local_rank), fit=args.fit)
+                        seed=args.zscore_seed, observed=scores, engine=default_engine(local_rank), fit=args.fit, local=args.local)
         if args.score_only:
             for t, p in enumerate(mine):
-                print(f"pair {p}\t{records[p][0]}\t{records[p][3]}\t{int(scores[t])}" + (f"\t{int(end_b[t])}" if args.fit else ""))
+                print(f"pair {p}\t{records[p][0]}\t{records[p][3]}\t{int(scores[t])}" + (f"\t{int(end_b[t])}" if args.fit else "") +
+                      (f"\t{int(lspans[1][t])}\t{int(lspans[3][t])}" if args.local else ""))
                 if z:
                     print(zscore_line(z, t))
         else:
@@ -165,7 +194,8 @@ def _main(argv=None):
             for t, p in enumerate(mine):
                 trace = trace_codes_to_columns(traces[t], as_tuples=not batch.affine)
                 span = (int(start_b[t]), int(end_b[t])) if args.fit and complete[t] else None
-                for line in pair_block(p, records[p], params, int(scores[t]), trace, bool(complete[t]), args.verbose, span):
+                lspan = tuple(int(x[t]) for x in lspans) if args.local and complete[t] else None
+                for line in pair_block(p, records[p], params, int(scores[t]), trace, bool(complete[t]), args.verbose, span, lspan):
                     print(line)
                 if z:
                     print(zscore_line(z, t))

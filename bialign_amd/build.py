@@ -33,6 +33,9 @@ def units():
     """(object name, source, extra flags), the slow ones (affine fill, wide bands) first."""
     out = [(f"inst_s{s}_k0.o", "bialign_inst.hip", [f"-DBIALIGN_TU_S={s}", "-DBIALIGN_TU_KIND=0"])
            for s in range(MAX_SHIFT, -1, -1)]
+    # the LOCAL sweeps (local alignments), beside the ones they are instantiated from
+    out += [(f"inst_s{s}_k2.o", "bialign_inst.hip", [f"-DBIALIGN_TU_S={s}", "-DBIALIGN_TU_KIND=2"])
+            for s in range(MAX_SHIFT, -1, -1)]
     out += [(f"inst_s{s}_k1.o", "bialign_inst.hip", [f"-DBIALIGN_TU_S={s}", "-DBIALIGN_TU_KIND=1"])
             for s in range(MAX_SHIFT, -1, -1)]
     out.append(("wide.o", "bialign_wide.hip", []))

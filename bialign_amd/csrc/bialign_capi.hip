@@ -70,8 +70,17 @@ int launch_fill(bialign_batch* b, const DeviceBatch& v, int first, int count) {
   if (b->wide) return launch_fill_wide(b, v, first, count);
   return with_shift(b, "fill", [&](auto s) {
     constexpr int S = decltype(s)::value;
+    if (b->local) return b->affine ? launch_fill_affine_local<S>(b, v, first, count) : launch_fill_linear_local<S>(b, v, first, count);
     return b->affine ? launch_fill_affine<S>(b, v, first, count) : launch_fill_linear<S>(b, v, first, count);
   });
+}
+
+// Local alignments: behind a sweep, the pairs' keys become their scores and ends (bialign_local.hpp)
+int launch_local_finish(const bialign_batch* b, const DeviceBatch& v, int first, int count) {
+  constexpr int BLOCK = 256;
+  DeviceBatch w = v;
+  w.order = v.order + first;
+  return launch(local_finish_kernel<BLOCK>, dim3((count + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, b->eng->stream, w, count);
 }
 
 // Lean traceback of one chunk: as many (re-sweep, walk) rounds as its longest pair has strips.
@@ -322,6 +331,10 @@ int upload_inputs(bialign_batch* b, const bialign_scoring* sc, const bialign_pai
   }
   HIP_TRY(b->d_scores.alloc(pr->npairs));
   if (b->fit) HIP_TRY(b->d_fit.alloc(2 * (size_t)pr->npairs));
+  if (b->local) {
+    HIP_TRY(b->d_local_key.alloc((size_t)pr->npairs));
+    HIP_TRY(b->d_local_span.alloc(4 * (size_t)pr->npairs));
+  }
   if (b->lean_trace || b->level_trace) HIP_TRY(b->d_tstate.alloc(pr->npairs));
   HIP_TRY(b->d_tlen.alloc(pr->npairs));
   HIP_TRY(b->d_complete.alloc(pr->npairs));
@@ -591,6 +604,10 @@ static int enqueue_run(bialign_batch* b, uint32_t flags) {
   HIP_TRY(hipStreamWaitEvent(st, b->uploaded, 0));
   HIP_TRY(hipMemsetAsync(b->d_err.p, 0, sizeof(int32_t), st));  // the flag is per run
   if (b->fit) HIP_TRY(hipMemsetAsync(b->d_fit.p, 0xff, 2 * sizeof(int32_t) * b->npairs, st));  // spans: -1 until a kernel writes them
+  if (b->local) {  // keys: zero, below every key a sweep folds in; spans: -1 until a kernel writes them
+    HIP_TRY(hipMemsetAsync(b->d_local_key.p, 0, sizeof(unsigned long long) * b->npairs, st));
+    HIP_TRY(hipMemsetAsync(b->d_local_span.p, 0xff, 4 * sizeof(int32_t) * b->npairs, st));
+  }
   if (b->null_R) {  // null batch: the replicas' B codes, all of them ahead of the first sweep (timed on its own, outside fill_ms)
     HIP_TRY(hipEventRecord(b->null_evs[0], st));
     if (int rc = launch_shuffle_null(b, 0, b->npairs)) return rc;
@@ -610,6 +627,7 @@ static int enqueue_run(bialign_batch* b, uint32_t flags) {
     }
     HIP_TRY(hipEventRecord(b->evs[3 * c], st));
     int rc = launch_fill(b, v, first, count);
+    if (rc == BIALIGN_OK && b->local) rc = launch_local_finish(b, v, first, count);  // in every storage mode: scores and ends
     if (rc) return rc;
     HIP_TRY(hipEventRecord(b->evs[3 * c + 1], st));
     if (!b->lean) {  // (with LEAN records the sweep itself wrote the scores)
@@ -724,6 +742,20 @@ int bialign_batch_get_fit_spans(const bialign_batch* b, int32_t* start_b, int32_
   std::vector<int32_t> span(2 * (size_t)b->npairs);
   HIP_TRY(hipMemcpy(span.data(), b->d_fit.p, sizeof(int32_t) * span.size(), hipMemcpyDeviceToHost));
   for (int p = 0; p < b->npairs; ++p) start_b[p] = span[2 * p], end_b[p] = span[2 * p + 1];
+  return BIALIGN_OK;
+}
+
+int bialign_batch_get_local_spans(const bialign_batch* b, int32_t* start_a, int32_t* end_a, int32_t* start_b, int32_t* end_b) {
+  if (!b || !start_a || !end_a || !start_b || !end_b) return fail(BIALIGN_E_INVALID, "NULL argument");
+  if (!b->local) return fail(BIALIGN_E_INVALID, "batch was created without BIALIGN_BATCH_LOCAL: it has no local spans");
+  if (b->null_R) return fail(BIALIGN_E_INVALID, "a null batch has no observed alignments: no spans");
+  if (int rc = bialign_batch_wait(const_cast<bialign_batch*>(b))) return rc;
+  if (!b->ran) return fail(BIALIGN_E_INVALID, "bialign_batch_run has not been called");
+  HIP_TRY(hipSetDevice(b->eng->device));
+  std::vector<int32_t> span(4 * (size_t)b->npairs);
+  HIP_TRY(hipMemcpy(span.data(), b->d_local_span.p, sizeof(int32_t) * span.size(), hipMemcpyDeviceToHost));
+  for (int p = 0; p < b->npairs; ++p)
+    start_a[p] = span[4 * p], end_a[p] = span[4 * p + 1], start_b[p] = span[4 * p + 2], end_b[p] = span[4 * p + 3];
   return BIALIGN_OK;
 }
 

@@ -44,9 +44,13 @@ __device__ __forceinline__ void store_chunk(int32_t* p, v4i v, bool wt) {
 //   strip the walk stands in is swept only up to the walk's column.  One wave per strip.
 //   PACK: interior steps store packed records, the others full records in the pair's second region (Pack<S>).
 //   DENSE1: mu1(i,j) from the pair's dense table (Mu1Feed) instead of s1 and the sequence codes, which are then not staged.
+//   LOCAL (local alignments, BIALIGN_BATCH_LOCAL): the lanes with a = 0 floor state 8 of their b = 0 point -- the lattice
+//   point (i, j, i, j) -- against 0 in every step, keep the best E of their row in registers (LocalBest) and fold it into
+//   the pair's key when they change strip and at the end.  Every line of it sits behind `if constexpr (LOCAL)`.
 template <int S, bool BETA_NONPOS, int TW, bool XCU, bool DENSE = false, bool LEAN = false, bool RESW = false,
-          bool PACK = false, bool DENSE1 = false>
+          bool PACK = false, bool DENSE1 = false, bool LOCAL = false>
 __global__ void __launch_bounds__(64 * TW) fill_affine_kernel(const DeviceBatch A) {
+  static_assert(!LOCAL || (BETA_NONPOS && !XCU && !RESW && !PACK), "local alignments: in-workgroup sweeps with full or LEAN records, beta <= 0");
   static_assert(!PACK || (!LEAN && !RESW && S >= 1), "packed records: full-storage sweeps with a band");
   using PK_ = Pack<S>;
   // Ghost rows of packed records: unpacked once per block by BLK*W lanes (s=1: 24 lanes every 8 steps, -4 % fill
@@ -326,6 +330,8 @@ __global__ void __launch_bounds__(64 * TW) fill_affine_kernel(const DeviceBatch 
     fetch_codes();
   }
   int fit_best = SENT, fit_j = 0;  // LEAN fit batches: the best end cell of row n so far and its column
+  LocalBest loc;                                    // LOCAL: this lane's row (i, ., i, .)
+  const bool loc_lane = live && !ghost && aa == S;  // ... if it holds one
 
   // One step of the sweep.  INTERIOR steps (every lane's lattice points have all
   // four coordinates >= 1 and lie inside the molecule columns; ~90 % of the
@@ -530,10 +536,16 @@ __global__ void __launch_bounds__(64 * TW) fill_affine_kernel(const DeviceBatch 
         }
         if (bb == S) M[8] = is_origin ? 0 : M[8];  // pyx:483-485
         if (bb == S && row0_diag) M[8] = imax(M[8], prog_lds[FIT_FLOOR_WORD]);
+        if constexpr (LOCAL) {  // a path may start at any (i, j, i, j); ghost lanes replay values that are floored already
+          if (bb == S) M[8] = (aa == S && act) ? imax(M[8], 0) : M[8];
+        }
+      }
+      if constexpr (LOCAL) {
+        if (INTERIOR && bb == S) M[8] = (aa == S && computing) ? imax(M[8], 0) : M[8];
       }
 #pragma unroll
       for (int q = 0; q < 9; ++q) outv[bb * 9 + q] = M[q];
-      if (LEAN && bb == S) {  // score-only: the end cell (n,m,n,m) is all the host wants (pyx:509)
+      if (LEAN && !LOCAL && bb == S) {  // score-only: the end cell (n,m,n,m) is all the host wants (pyx:509)
         if (!A.fit) {
           if (live && !ghost && aa == S && i == n && jj == m) {
             int best = M[0];
@@ -684,6 +696,9 @@ __global__ void __launch_bounds__(64 * TW) fill_affine_kernel(const DeviceBatch 
           Gd[1][v] = fX(H2[0][v], H2[1][v], H2[2][v], beta);
         }
       }
+      if constexpr (LOCAL) {  // E(i, j) = the maximum of the point's nine states = G[M][M], computed above anyway
+        if (bb == S) loc.see(loc_lane && act_row && (INTERIOR || (jj >= 0 && jj <= m)), Gd[2][2], jj);
+      }
       if (PACK && INTERIOR) {
         pk_max = imax(pk_max, Gd[2][2]);
         if (bb == W - 1) {  // rows outside the lattice hold don't-care values; the OR runs on across steps, tested every 16
@@ -728,6 +743,7 @@ __global__ void __launch_bounds__(64 * TW) fill_affine_kernel(const DeviceBatch 
     ++jj;
     if (!RESW && !INTERIOR && jj == P) {  // a re-sweep ends inside its one strip; an interior step never ends a strip (phase <= m - S)
       jj = 0;
+      if constexpr (LOCAL) loc.fold(A.local_key + pid, i, m);
       ++strip;
       rec_base += (T - 1) * P;
       set_row(strip);
@@ -769,6 +785,7 @@ __global__ void __launch_bounds__(64 * TW) fill_affine_kernel(const DeviceBatch 
       ++g;
     }
   }
+  if constexpr (LOCAL) loc.fold(A.local_key + pid, i, m);
   if (PACK && __builtin_amdgcn_ballot_w64(live && !ghost && (unsigned)pk_all > 0xffffu) != 0 && L == 0) atomicOr(A.errflag, 2);
   if (XCU || TW > 1) {  // everything this wave wrote is acknowledged: release the partner for good
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

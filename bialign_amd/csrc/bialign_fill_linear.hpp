@@ -13,8 +13,12 @@ namespace bialign {
 //   XCU: the team is A.team one-wave workgroups on any CUs (progress words in HBM, write-through
 //   stores), as in fill_affine_kernel -- for a handful of long pairs, e.g. one pair from the CLI.
 //   DENSE1: mu1(i,j) from the pair's dense table (Mu1Feed), as in fill_affine_kernel.
-template <int S, int TW, bool DENSE = false, bool LEAN = false, bool RESW = false, bool XCU = false, bool DENSE1 = false>
+//   LOCAL: local alignments, as in fill_affine_kernel -- the floor under the value of (i, j, i, j), the row's best in
+//   registers, the fold into the pair's key; every line of it behind `if constexpr (LOCAL)`.
+template <int S, int TW, bool DENSE = false, bool LEAN = false, bool RESW = false, bool XCU = false, bool DENSE1 = false,
+          bool LOCAL = false>
 __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch A) {
+  static_assert(!LOCAL || (!XCU && !RESW), "local alignments: in-workgroup sweeps with full or LEAN records");
   static_assert(!XCU || (TW == 1 && !RESW), "cross-CU teams are built from one-wave workgroups");
   using G_ = Geo<S>;
   using R_ = Rec<S, 1, LEAN>;
@@ -167,6 +171,8 @@ __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   int vm_younger = 0;  // see the affine kernel
   int fit_best = SENT, fit_j = 0;  // LEAN fit batches: the best end cell of row n so far and its column
+  LocalBest loc;                                    // LOCAL: this lane's row (i, ., i, .)
+  const bool loc_lane = live && !ghost && aa == S;  // ... if it holds one
 
   for (int g = 0; g < H; ++g) {
     const int gt = g & (GF::BLK - 1), ghalf = (g / GF::BLK) & 1;
@@ -238,6 +244,9 @@ __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch 
       int M = bad ? (act ? NEG : SENT) : tv;             // pyx:299-303
       if (bb == S) M = is_origin ? 0 : M;                // np.zeros origin (pyx:27, 464-465)
       if (bb == S && row0_diag) M = imax(M, prog[FIT_FLOOR_WORD]);
+      if constexpr (LOCAL) {  // a path may start at any (i, j, i, j); ghost lanes replay values that are floored already
+        if (bb == S) M = (aa == S && act) ? imax(M, 0) : M;
+      }
       outv[bb] = M;
       prev = M;
     }
@@ -252,8 +261,9 @@ __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch 
     }
 
     const int rec = g + rec_base;
-    if (LEAN && !A.fit && live && !ghost && aa == S && i == n && jj == m) A.scores[pid] = outv[S];  // pyx:471
-    if (LEAN && A.fit && live && !ghost && aa == S && i == n && jj >= 0 && jj <= m) {
+    if constexpr (LOCAL) loc.see(loc_lane && tile_act, outv[S], jj);  // E(i, j) = the value of (i, j, i, j)
+    if (LEAN && !LOCAL && !A.fit && live && !ghost && aa == S && i == n && jj == m) A.scores[pid] = outv[S];  // pyx:471
+    if (LEAN && !LOCAL && A.fit && live && !ghost && aa == S && i == n && jj >= 0 && jj <= m) {
       // fit: row n has one owner, the lane of (n, j, n, j), which passes over the columns in order: the best end cell
       // and the smallest column that attains it stay in its registers
       if (outv[S] > fit_best) fit_best = outv[S], fit_j = jj;
@@ -302,11 +312,13 @@ __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch 
     ++jj;
     if (!RESW && jj == P) {
       jj = 0;
+      if constexpr (LOCAL) loc.fold(A.local_key + pid, i, m);
       ++strip;
       rec_base += (T - 1) * P;
       set_row(strip);
     }
   }
+  if constexpr (LOCAL) loc.fold(A.local_key + pid, i, m);
   if (T > 1) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (L == 0) prog_put(0x7fffffff);

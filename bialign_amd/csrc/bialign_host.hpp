@@ -87,6 +87,10 @@ struct bialign_batch : bialign::BatchPlan {  // the plan (bialign_plan.hpp), and
   DevBuf<PairDesc> d_pairs;
   DevBuf<int32_t> d_order, d_s1, d_s2, d_layers, d_scores, d_tlen, d_complete, d_err, d_prog;
   DevBuf<int32_t> d_fit;  // fit alignments (BatchPlan::fit): [npairs][2] = (start_b, end_b), -1 ahead of every run
+  // local alignments (BatchPlan::local): [npairs] best-end keys, zeroed ahead of every run, and
+  // [npairs][4] = (start_a, end_a, start_b, end_b), -1 ahead of every run
+  DevBuf<unsigned long long> d_local_key;
+  DevBuf<int32_t> d_local_span;
   int last_team = 1;  // waves per pair of the last fill launch (negative: cross-CU team)
   // Cross-CU teams need every workgroup of the launch resident at once.  The grid is sized from the
   // occupancy the runtime reports for the actual kernel (xcu_resident, cached per LEAN flavour) and
@@ -173,6 +177,9 @@ struct bialign_batch : bialign::BatchPlan {  // the plan (bialign_plan.hpp), and
     v.spin_limit = 1 << 20;  // waves of one workgroup are co-resident by construction: a timeout there is a bug
     v.fit = fit ? 1 : 0;
     v.fit_span = d_fit.p;
+    v.local = local ? 1 : 0;
+    v.local_key = d_local_key.p;
+    v.local_span = d_local_span.p;
     return v;
   }
 };
@@ -280,6 +287,7 @@ enum FillFlags : unsigned {
   F_PACK = 16,      // packed records (Pack<S>)
   F_DENSE1 = 32,    // mu1 from dense tables
   F_BETA_ANY = 64,  // affine: gap_opening_cost > 0, the general-beta algebra
+  F_LOCAL = 128,    // local alignments (BIALIGN_BATCH_LOCAL)
 };
 enum TraceFlags : unsigned {
   T_TRACE = 1,   // walk back and write the trace (else: the score only)
@@ -293,6 +301,8 @@ enum TraceFlags : unsigned {
 // The instantiation plan: which sweeps exist, as (max_shift, waves per workgroup, flags).
 constexpr bool fill_affine_exists(int S, int TW, unsigned F) {
   const bool xcu = F & F_XCU, dense = F & (F_DENSE | F_DENSE1), pack = F & F_PACK;
+  // local alignments: in-workgroup sweeps of one wave, and of four up to s=3, in all four dense/lookup forms, full and LEAN
+  if (F & F_LOCAL) return !(F & (F_XCU | F_PACK | F_RESW | F_BETA_ANY)) && (TW == 1 || (TW == 4 && S <= 3));
   // packed records: max_shift 1..BIALIGN_MAX_SHIFT_PACKED, full storage, not with dense mu1
   if (pack && (S < 1 || S > BIALIGN_MAX_SHIFT_PACKED || (F & (F_LEAN | F_DENSE1)))) return false;
   // re-sweeps and the (rare) general-beta algebra: one wave per pair, full (re-sweeps) or any (beta) records
@@ -303,6 +313,8 @@ constexpr bool fill_affine_exists(int S, int TW, unsigned F) {
 }
 constexpr bool fill_linear_exists(int TW, unsigned F) {
   if (F & (F_PACK | F_BETA_ANY)) return false;
+  // local alignments, the analogous cut: one wave, and four in LOOKUP form
+  if (F & F_LOCAL) return !(F & (F_XCU | F_RESW)) && (TW == 1 || (TW == 4 && !(F & (F_DENSE | F_DENSE1))));
   if (F & (F_RESW | F_XCU)) return TW == 1 && (F & (F_RESW | F_XCU)) != (F_RESW | F_XCU) && !((F & F_RESW) && (F & F_LEAN));
   return TW == 1 || TW == 2 || (!(F & (F_DENSE | F_DENSE1)) && (TW == 4 || TW == 8));  // dense forms: up to two waves
 }
@@ -319,12 +331,13 @@ template <int S, int TW, unsigned F>
 auto fill_affine_of() {
   static_assert(fill_affine_exists(S, TW, F), "not in the instantiation plan");
   return fill_affine_kernel<S, !(F & F_BETA_ANY), TW, (F & F_XCU) != 0, (F & F_DENSE) != 0, (F & F_LEAN) != 0, (F & F_RESW) != 0,
-                            (F & F_PACK) != 0, (F & F_DENSE1) != 0>;
+                            (F & F_PACK) != 0, (F & F_DENSE1) != 0, (F & F_LOCAL) != 0>;
 }
 template <int S, int TW, unsigned F>
 auto fill_linear_of() {
   static_assert(fill_linear_exists(TW, F), "not in the instantiation plan");
-  return fill_linear_kernel<S, TW, (F & F_DENSE) != 0, (F & F_LEAN) != 0, (F & F_RESW) != 0, (F & F_XCU) != 0, (F & F_DENSE1) != 0>;
+  return fill_linear_kernel<S, TW, (F & F_DENSE) != 0, (F & F_LEAN) != 0, (F & F_RESW) != 0, (F & F_XCU) != 0, (F & F_DENSE1) != 0,
+                            (F & F_LOCAL) != 0>;
 }
 template <int S, unsigned F>
 auto traceback_affine_of() {
@@ -441,6 +454,19 @@ int launch_fill_affine(bialign_batch* b, const DeviceBatch& v, int first, int co
   });
 }
 
+// Local alignments (BatchPlan::local): the LOCAL instantiations, in translation units of their own (kind 2).  The team
+// shape comes without cross-CU teams, slim sweeps and packed records (team_shape, decide_pack); the ladder is "4, 1".
+template <int S>
+int launch_fill_affine_local(bialign_batch* b, const DeviceBatch& v, int first, int count) {
+  return with_flags<F_DENSE | F_LEAN | F_DENSE1>(fill_flags(b) & ~(unsigned)(F_PACK | F_BETA_ANY), [&](auto flags) -> int {
+    constexpr unsigned F = decltype(flags)::value | F_LOCAL;
+    const TeamShape ts = team_shape(*b, first, count, b->eng->num_cu, 0);
+    int rc = BIALIGN_OK;
+    (void)(fill_affine_rung<S, 4, F>(b, v, first, count, ts, &rc) || fill_affine_rung<S, 1, F>(b, v, first, count, ts, &rc));
+    return rc;
+  });
+}
+
 // Lean traceback, one round: re-sweep the strip every unfinished pair's walk stands in ...
 template <int S>
 int launch_resweep_affine(bialign_batch* b, const DeviceBatch& v, int first, int count) {
@@ -476,13 +502,13 @@ bool trace_fast_admits(const PairDesc& d) {
 }
 // LDS of a launch of the fast kernel: the staged inputs, the candidate table, and the trace buffer -- the longest trace
 // of the launch if the workgroup can spare it (BIALIGN_TRACE_LDS: tests, a smaller buffer), else flushed in pieces.
-// 0: the generic kernel serves (BIALIGN_TRACE_FAST=0: tests / A-B; dense mu2; a FIT batch; a pair not admitted).
+// 0: the generic kernel serves (BIALIGN_TRACE_FAST=0: tests / A-B; dense mu2; a FIT or LOCAL batch; a pair not admitted).
 constexpr int TRACE_FAST_TBUF_MAX = 16 * 1024;
 template <int S>
 size_t trace_fast_lds(const bialign_batch* b, int first, int count, int* tbuf) {
   const char* sw = getenv("BIALIGN_TRACE_FAST");  // "0": tests / A-B, the generic kernel only
   if ((sw && atoi(sw) == 0) || b->dense || b->dense1 || b->wide || b->lean) return 0;
-  if (b->fit) return 0;  // fit alignments take the generic walk: the short-chain kernel has neither the end scan nor the stop rule
+  if (b->fit || b->local) return 0;  // fit and local alignments take the generic walk: the short-chain kernel has neither the end rules nor the stop rules
   int cap = 0;
   for (int t = first; t < first + count; ++t) {
     const PairDesc& d = b->pairs[b->order[t]];
@@ -561,6 +587,18 @@ int launch_fill_linear(bialign_batch* b, const DeviceBatch& v, int first, int co
   });
 }
 
+// local alignments, as launch_fill_affine_local: 4, 1
+template <int S>
+int launch_fill_linear_local(bialign_batch* b, const DeviceBatch& v, int first, int count) {
+  return with_flags<F_DENSE | F_LEAN | F_DENSE1>(fill_flags(b), [&](auto flags) -> int {
+    constexpr unsigned F = decltype(flags)::value | F_LOCAL;
+    const TeamShape ts = team_shape(*b, first, count, b->eng->num_cu, 0);
+    int rc = BIALIGN_OK;
+    (void)(fill_linear_rung<S, 4, F>(b, v, first, count, ts, &rc) || fill_linear_rung<S, 1, F>(b, v, first, count, ts, &rc));
+    return rc;
+  });
+}
+
 template <int S>
 int launch_resweep_linear(bialign_batch* b, const DeviceBatch& v, int first, int count) {
   DeviceBatch w = v;
@@ -602,7 +640,7 @@ int launch_segment_wide(bialign_batch* b, const DeviceBatch& v, int first, int c
 int launch_traceback_level(const bialign_batch* b, const DeviceBatch& v, int first, int count);
 int launch_dump_wide(const bialign_batch* b, const DeviceBatch& v, int pid, int32_t* d_out);
 
-// ---- instantiation plan: kind 0 = affine fill (the big kernels), kind 1 = everything else
+// ---- instantiation plan: kind 0 = affine fill (the big kernels), kind 1 = everything else, kind 2 = the LOCAL sweeps
 #define BIALIGN_INST_KIND0(S, X)                                                                \
   X template int launch_fill_affine<S>(bialign_batch*, const DeviceBatch&, int, int);          \
   X template int launch_resweep_affine<S>(bialign_batch*, const DeviceBatch&, int, int);
@@ -616,9 +654,14 @@ int launch_dump_wide(const bialign_batch* b, const DeviceBatch& v, int pid, int3
   X template int launch_dump<S, 9>(const bialign_batch*, const DeviceBatch&, int, int32_t*);            \
   X template int launch_dump<S, 1>(const bialign_batch*, const DeviceBatch&, int, int32_t*);
 
+#define BIALIGN_INST_KIND2(S, X)                                                                \
+  X template int launch_fill_affine_local<S>(bialign_batch*, const DeviceBatch&, int, int);    \
+  X template int launch_fill_linear_local<S>(bialign_batch*, const DeviceBatch&, int, int);
+
 #ifndef BIALIGN_TU_S  // every other unit: the instantiations live elsewhere
 BIALIGN_FOR_EACH_S(BIALIGN_INST_KIND0, extern)
 BIALIGN_FOR_EACH_S(BIALIGN_INST_KIND1, extern)
+BIALIGN_FOR_EACH_S(BIALIGN_INST_KIND2, extern)
 #endif
 
 }  // namespace bialign

@@ -46,6 +46,7 @@
 #include "bialign_types.hpp"
 #include "bialign_feed.hpp"
 #include "bialign_affine_point.hpp"
+#include "bialign_local.hpp"
 #include "bialign_fill_affine.hpp"
 #include "bialign_fill_slim.hpp"
 #include "bialign_fill_linear.hpp"

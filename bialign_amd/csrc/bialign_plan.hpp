@@ -75,6 +75,10 @@ struct BatchPlan {
   // Fit alignments (BIALIGN_BATCH_FIT): free end gaps in B.  Tiled bands, full storage or SCORE_ONLY; the generic
   // tracebacks only (host: trace_fast_lds); never the storage ladder's LEAN_TRACE rung (plan_storage: BIALIGN_E_NOMEM).
   bool fit = false;
+  // Local alignments (BIALIGN_BATCH_LOCAL): free ends in both molecules.  Tiled bands, beta <= 0 in the affine recurrence,
+  // full storage or SCORE_ONLY; sweeps of their own (launch_fill_*_local) that never pack, never take the slim kernel or a
+  // cross-CU team (decide_pack, slim_available, team_shape); the generic tracebacks only; no LEAN_TRACE rung either.
+  bool local = false;
 };
 
 // What the host needs of the kernels' compile-time geometry, for a run-time (max_shift, recurrence): read from the types
@@ -129,7 +133,7 @@ struct TeamShape {
 inline bool slim_available(const BatchPlan& b) {
   const char* sw = getenv("BIALIGN_SLIM");  // "0": tests / A-B, the two-wave kernels only
   const bool off = sw && atoi(sw) == 0;
-  return !off && b.affine && b.S == 1 && !b.dense && !b.dense1 && !b.wide && b.prm.gap_opening_cost <= 0 && (b.lean || b.pack_now());
+  return !off && !b.local && b.affine && b.S == 1 && !b.dense && !b.dense1 && !b.wide && b.prm.gap_opening_cost <= 0 && (b.lean || b.pack_now());
 }
 inline bool diet8_available(const BatchPlan& b) {  // the eight-wave s=2 affine kernel and its LDS layout
   return b.affine && b.S == 2 && !b.dense && !b.dense1 && b.lds_diet8 <= 160 * 1024;
@@ -150,6 +154,7 @@ inline bool diet8_available(const BatchPlan& b) {  // the eight-wave s=2 affine 
 // xcu8_resident: likewise its eight-wave workgroups (s=2 affine sweep only, else 0); num_cu: the device's compute units
 inline TeamShape team_shape(const BatchPlan& b, int first, int count, int num_cu, int xcu_resident, int xcu8_resident = 0) {
   TeamShape ts;
+  if (b.local) xcu_resident = xcu8_resident = 0;  // local alignments: in-workgroup teams only
   const SweepInfo& geo = sweep_info(b);
   const int lag = 2 * (geo.R - 1) + 2 * geo.blk + 16;
   int fit_exact = PROG_WORDS;  // largest team the pairs of this launch allow: T*lag + 64 <= P (P >= 256), two strips per wave
@@ -467,13 +472,22 @@ inline int check_inputs(const bialign_params* prm, const bialign_scoring* sc, co
   b.lean_trace = (prm->flags & BIALIGN_BATCH_LEAN_TRACE) != 0;
   b.lean = b.lean_trace || (prm->flags & BIALIGN_BATCH_SCORE_ONLY) != 0;
   b.wide = prm->max_shift > BIALIGN_MAX_SHIFT_TILED;  // bialign_wide.hpp: anti-diagonal path, all layers in HBM
-  constexpr uint32_t KNOWN_FLAGS = BIALIGN_BATCH_SCORE_ONLY | BIALIGN_BATCH_LEAN_TRACE | BIALIGN_BATCH_LEVEL_TRACE | BIALIGN_BATCH_FIT;
+  constexpr uint32_t KNOWN_FLAGS =
+      BIALIGN_BATCH_SCORE_ONLY | BIALIGN_BATCH_LEAN_TRACE | BIALIGN_BATCH_LEVEL_TRACE | BIALIGN_BATCH_FIT | BIALIGN_BATCH_LOCAL;
   if (prm->flags & ~KNOWN_FLAGS) return fail(BIALIGN_E_INVALID, "unknown bits 0x%x in bialign_params.flags", prm->flags & ~KNOWN_FLAGS);
   b.fit = (prm->flags & BIALIGN_BATCH_FIT) != 0;
   if (b.fit && (prm->flags & (BIALIGN_BATCH_LEAN_TRACE | BIALIGN_BATCH_LEVEL_TRACE)))
     return fail(BIALIGN_E_UNSUPPORTED, "FIT exists in full storage and in SCORE_ONLY: not with LEAN_TRACE or LEVEL_TRACE");
   if (b.fit && b.wide)
     return fail(BIALIGN_E_UNSUPPORTED, "FIT exists for max_shift <= %d only (the tiled sweeps)", BIALIGN_MAX_SHIFT_TILED);
+  b.local = (prm->flags & BIALIGN_BATCH_LOCAL) != 0;
+  if (b.local && b.fit) return fail(BIALIGN_E_INVALID, "LOCAL and FIT exclude each other");
+  if (b.local && (prm->flags & (BIALIGN_BATCH_LEAN_TRACE | BIALIGN_BATCH_LEVEL_TRACE)))
+    return fail(BIALIGN_E_UNSUPPORTED, "LOCAL exists in full storage and in SCORE_ONLY: not with LEAN_TRACE or LEVEL_TRACE");
+  if (b.local && b.wide)
+    return fail(BIALIGN_E_UNSUPPORTED, "LOCAL exists for max_shift <= %d only (the tiled sweeps)", BIALIGN_MAX_SHIFT_TILED);
+  if (b.local && b.affine && prm->gap_opening_cost > 0)
+    return fail(BIALIGN_E_UNSUPPORTED, "LOCAL exists for gap_opening_cost <= 0 only in the affine recurrence (no general-beta sweep)");
   if (prm->flags & BIALIGN_BATCH_LEVEL_TRACE) {
     if (b.lean) return fail(BIALIGN_E_INVALID, "LEVEL_TRACE excludes SCORE_ONLY and LEAN_TRACE");
     if (!b.wide)
@@ -576,6 +590,8 @@ inline int plan_pairs(const bialign_pairs* pr, const NullPlan* nul, int64_t colm
     if ((2 * ((int64_t)n + m) + 8) * colmax >= (1 << 28))
       return fail(BIALIGN_E_RANGE, "pair %d: scores may leave the int32 safety window (n+m=%d, column bound %lld)", shown(p),
                   n + m, (long long)colmax);
+    if (b.local && n + m >= LOCAL_MAX_NM)  // the end's position in the pair's key is 32 bits (bialign_local.hpp)
+      return fail(BIALIGN_E_UNSUPPORTED, "pair %d: LOCAL takes n + m < %d (n+m=%d)", shown(p), LOCAL_MAX_NM, n + m);
     if (nul) {  // the reduction's int64 sum of squares: replicas * bound^2 with the window's bound on |score| (< 2^28)
       const int64_t bound = (2 * ((int64_t)n + m) + 8) * colmax;
       if (bound > 0 && bound * bound > INT64_MAX / nul->replicas)
@@ -624,7 +640,7 @@ inline void decide_pack(BatchPlan& b, int64_t colmax) {
   const SweepInfo& pki = sweep_info(b);
   const char* e = getenv("BIALIGN_PACK");  // "0" never, "1" wherever the layout allows (tests), unset: when it pays
   const bool force = e && e[0] == '1';
-  bool ok = b.affine && S >= 1 && S <= BIALIGN_MAX_SHIFT_PACKED && !b.lean && !b.dense1 && b.prm.gap_opening_cost <= 0 &&
+  bool ok = b.affine && S >= 1 && S <= BIALIGN_MAX_SHIFT_PACKED && !b.lean && !b.dense1 && !b.local && b.prm.gap_opening_cost <= 0 &&
             !(e && e[0] == '0') &&
             (force || colmax < 8192) &&  // offsets span a few column scores (measured: up to 2.5): beyond this they will not fit
             // s=3 runs one wave per SIMD and is bound by issue: packing pays where the device is full (512 pairs x len 512
@@ -723,9 +739,9 @@ inline int plan_storage(BatchPlan& b, int64_t budget_dw) {
     }
   }
   if (!b.lean && !b.wide && max_need() > budget_dw) {
-    if (b.fit)  // no silent change of mode: the memory-lean traceback has no FIT form
-      return fail(BIALIGN_E_NOMEM, "a pair needs %lld bytes of layers, budget is %lld: a FIT batch does not fall back to LEAN_TRACE",
-                  (long long)max_need() * 4, (long long)budget_dw * 4);
+    if (b.fit || b.local)  // no silent change of mode: the memory-lean traceback has no FIT or LOCAL form
+      return fail(BIALIGN_E_NOMEM, "a pair needs %lld bytes of layers, budget is %lld: a %s batch does not fall back to LEAN_TRACE",
+                  (long long)max_need() * 4, (long long)budget_dw * 4, b.fit ? "FIT" : "LOCAL");
     b.lean = b.lean_trace = true;
     b.pack = false;
     pick_resw_k();
@@ -791,8 +807,8 @@ inline int expand_null_pairs(const bialign_params* prm, const bialign_pairs* pr,
   if (!mu1_off.empty()) vp.mu1_off = mu1_off.data();
   if (!mu2_off.empty()) vp.mu2_off = mu2_off.data();
   plan.vprm = *prm;
-  // SCORE_ONLY is forced (the caller refused LEAN_TRACE / LEVEL_TRACE); FIT passes through -- the replicas are scored in
-  // the observed batch's mode -- and so do unknown bits, for check_inputs to refuse
+  // SCORE_ONLY is forced (the caller refused LEAN_TRACE / LEVEL_TRACE); FIT and LOCAL pass through -- the replicas are
+  // scored in the observed batch's mode -- and so do unknown bits, for check_inputs to refuse
   plan.vprm.flags = BIALIGN_BATCH_SCORE_ONLY | (prm->flags & ~(uint32_t)(BIALIGN_BATCH_LEAN_TRACE | BIALIGN_BATCH_LEVEL_TRACE));
   return BIALIGN_OK;
 }

@@ -135,7 +135,12 @@ __global__ void __launch_bounds__(64) traceback_affine_kernel(const DeviceBatch 
   int st = 0, cur = 0;
   constexpr bool FIT_FORM = !STRIP && !WIDE && !LEVEL;  // fit alignments: the tiled full-storage forms
   const bool fit = FIT_FORM && A.fit;
+  const bool local = FIT_FORM && A.local;  // local alignments: the same forms
   if (!(STRIP || LEVEL) || !ts.started) {
+    if (local) {  // the walk starts at the end local_finish_kernel decoded: (end_a, end_b, end_a, end_b)
+      i = k = A.local_span[4 * (int64_t)pid + 1];
+      j = l = A.local_span[4 * (int64_t)pid + 3];
+    }
     if (fit) {  // the walk starts at the best end cell (n, end_b, n, end_b)
       int fbest, fend;
       fit_end_scan(m, c, [&](int x) {
@@ -150,7 +155,7 @@ __global__ void __launch_bounds__(64) traceback_affine_kernel(const DeviceBatch 
       }
     }
     // pyx:573-582: best end layer, first one with the least shift
-    const int endv = c < 9 ? cell(n, j, SR, SR, c) : -BIG;
+    const int endv = c < 9 ? cell(i, j, SR, SR, c) : -BIG;
     const int best = __builtin_amdgcn_readfirstlane(-wave_min16(-endv));
     if (c == 0) A.scores[pid] = best;
     if (!DO_TRACE) return;
@@ -172,6 +177,7 @@ __global__ void __launch_bounds__(64) traceback_affine_kernel(const DeviceBatch 
   while (true) {
     if (i == 0 && j == 0 && k == 0 && l == 0 && st == 8) { complete = 1; break; }
     if (fit && i == 0 && k == 0 && j == l && st == 8 && cur == 0) { complete = 1; break; }  // fit: a free start, start_b = j
+    if (local && i == k && j == l && st == 8 && cur == 0) { complete = 1; break; }  // local: a free start, (start_a, start_b) = (i, j)
     if (STRIP && i < Qlo * RR) { finished = false; break; }  // above the re-swept strips: next round
     if (LEVEL && seg > 0 && i + j + k + l < seg_base + WIDE_SEG_OVERLAP) { finished = false; break; }  // a candidate may lie below the scratch
     const int hU = st / 3, hV = st - 3 * hU;
@@ -237,6 +243,7 @@ __global__ void __launch_bounds__(64) traceback_affine_kernel(const DeviceBatch 
     A.trace_len[pid] = len;
     A.complete[pid] = complete;
     if (fit && complete) A.fit_span[2 * pid] = j;
+    if (local && complete) A.local_span[4 * (int64_t)pid] = i, A.local_span[4 * (int64_t)pid + 2] = j;
     if (STRIP || LEVEL) {
       ts.done = 1;
       ts.started = 1;
@@ -286,7 +293,12 @@ __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch 
   };
   constexpr bool FIT_FORM = !STRIP && !WIDE && !LEVEL;  // fit alignments: the tiled full-storage forms
   const bool fit = FIT_FORM && A.fit;
-  int jend = m;
+  const bool local = FIT_FORM && A.local;  // local alignments: the same forms
+  int iend = n, jend = m;
+  if (local) {  // the walk starts at the end local_finish_kernel decoded: (end_a, end_b, end_a, end_b)
+    iend = A.local_span[4 * (int64_t)pid + 1];
+    jend = A.local_span[4 * (int64_t)pid + 3];
+  }
   if (fit) {  // the walk starts at the best end cell (n, end_b, n, end_b)
     int fbest;
     fit_end_scan(m, c, [&](int x) { return cell(n, x, SR, SR); }, &fbest, &jend);
@@ -295,7 +307,7 @@ __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch 
       A.fit_span[2 * pid + 1] = jend;
     }
   }
-  int cur = (CONT && ts.started) ? ts.cur : cell(n, jend, SR, SR);
+  int cur = (CONT && ts.started) ? ts.cur : cell(iend, jend, SR, SR);
   if (c == 0 && !(CONT && ts.started)) A.scores[pid] = cur;  // pyx:471
   if (!DO_TRACE) return;
   const TraceInputs in = stage_trace_inputs<D1>(A, pd, smem);
@@ -315,11 +327,12 @@ __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch 
   const int kconst = c == 0 ? 0 : (c <= 2 ? 2 * gamma : (c <= 4 ? delta : gD));
 
   uint8_t* out = A.trace + pd.trace_off;
-  int i = n, j = jend, k = n, l = jend, len = 0;
+  int i = iend, j = jend, k = iend, l = jend, len = 0;
   if (CONT && ts.started) { i = ts.i; j = ts.j; k = ts.k; l = ts.l; len = ts.len; }
   bool finished = true;
   while (true) {
     if (fit && i == 0 && k == 0 && j == l && cur == 0) break;  // fit: a free start, start_b = j
+    if (local && i == k && j == l && cur == 0) break;          // local: a free start, (start_a, start_b) = (i, j)
     if (STRIP && i < Qlo * RR) { finished = false; break; }
     if (LEVEL && seg > 0 && i + j + k + l < seg_base + WIDE_SEG_OVERLAP) { finished = false; break; }
     const int mu1 = (i >= 1 && j >= 1)
@@ -364,6 +377,7 @@ __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch 
     A.trace_len[pid] = len;
     A.complete[pid] = 1;
     if (fit) A.fit_span[2 * pid] = j;
+    if (local) A.local_span[4 * (int64_t)pid] = i, A.local_span[4 * (int64_t)pid + 2] = j;
     if (CONT) {
       ts.done = 1;
       ts.started = 1;

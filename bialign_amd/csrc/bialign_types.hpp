@@ -78,9 +78,18 @@ struct DeviceBatch {
   // end cell's score is written; the generic tracebacks in their prologue and stop test.
   // fit_span: [npairs][2] = (start_b, end_b), -1 until written.
   int32_t fit;
+  // Local alignments (BIALIGN_BATCH_LOCAL, DESIGN.md "Local alignments"): free ends in both molecules.  Wave-uniform; the
+  // sweeps built for it (template parameter LOCAL) do not read it, the generic tracebacks do, beside `fit`.  (It fills
+  // the padding behind `fit`.)
+  int32_t local;
   int32_t* fit_span;
+  // local_key: [npairs] the best end of a pair as a 64-bit key (bialign_local.hpp: local_key_of), zeroed ahead of every
+  // run, raised by the sweeps' lanes with atomicMax; local_span: [npairs][4] = (start_a, end_a, start_b, end_b), -1 until
+  // written (ends: local_finish_kernel, starts: the tracebacks).
+  unsigned long long* local_key;
+  int32_t* local_span;
 };
-static_assert(sizeof(DeviceBatch) == 240, "DeviceBatch grew: the kernels' argument blocks would change");
+static_assert(sizeof(DeviceBatch) == 256, "DeviceBatch grew: the kernels' argument blocks would change");
 
 // Dense mu1 (DeviceBatch::dense_forms bit 1): pair pd's n x m table, mu1(i,j) at [(i-1)*m + (j-1)].  It follows the
 // pair's mu2 table when that one is dense too.

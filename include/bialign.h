@@ -119,6 +119,34 @@ extern "C" {
  * bialign_batch_get_fit_spans the spans.  A BIALIGN_RUN_FILL_ONLY run of a full-storage FIT batch leaves the fit scores
  * and end_b (as such a run of any full-storage batch leaves the scores: the traceback kernel's prologue writes them). */
 #define BIALIGN_BATCH_FIT 8u
+/* LOCAL (new in ABI 10 as added symbols: no existing struct or function changes): local alignments -- the best-scoring
+ * parts of A and B, with the ends of both molecules free (two multi-domain proteins that share one domain, a structured
+ * motif two long transcripts have in common).  The recurrence, the guards, the band and the tie-breaks are unchanged.
+ * The mode makes the following changes.
+ *   Start.  At every lattice point (i, j, i, j), 0 <= i <= n, 0 <= j <= m, the value that the origin's 0 occupies today
+ *     becomes max(recurrence value, 0).  In the affine recurrence that value is state 8, (M,M).  In the one-layer
+ *     recurrence it is the cell's one value.  Every other state and cell is computed as before.
+ *   End.  score = max over 0 <= i <= n, 0 <= j <= m of E(i, j).  In the affine recurrence E is the maximum of the nine
+ *     states at (i, j, i, j).  In the one-layer recurrence it is the cell's value.  (end_a, end_b) is the smallest i, then
+ *     the smallest j, that attains the maximum.  score >= 0 always: the origin gives 0 with the empty alignment.
+ *   Walk.  The traceback starts at (end_a, end_b, end_a, end_b).  In the affine recurrence it starts in the best state
+ *     there, with ties broken as today at (n, m, n, m).  It applies the existing tie-breaks.  It stops, complete, the
+ *     first time it stands on a point (i, j, i, j) whose stored value is exactly 0.  In the affine recurrence it must
+ *     also be in state 8.  It is checked once on arrival, before it picks a predecessor.  That point is
+ *     (start_a, start_b).  The trace is the global alignment of A[start_a:end_a] with B[start_b:end_b], in the existing
+ *     byte code.
+ *   Equivalence.  For costs inside the int32 safety window, score = max over i0 <= i1, j0 <= j1 of
+ *     global(A[i0:i1], B[j0:j1]).  The per-column bound is unchanged: the floor only raises values towards 0.
+ * Accepted for max_shift <= BIALIGN_MAX_SHIFT_TILED, both recurrences, every form of mu1 and mu2, in full storage and
+ * with SCORE_ONLY (so in all three bialign_batch_create_null* entry points, which pass it through: the replicas are
+ * scored in the same mode), for pairs with n + m < 60000.  With FIT: BIALIGN_E_INVALID.  With LEAN_TRACE or LEVEL_TRACE,
+ * beyond the tiled band, or with gap_opening_cost > 0 in the affine recurrence: BIALIGN_E_UNSUPPORTED.  A LOCAL batch
+ * never changes its storage mode by itself: where a pair's full layers exceed the HBM budget the engine's fallback to
+ * LEAN_TRACE is BIALIGN_E_NOMEM instead.  bialign_batch_get_scores returns the local score,
+ * bialign_batch_get_traces the walk above (complete keeps its meaning), bialign_batch_dump_layers the LOCAL layers,
+ * bialign_batch_get_local_spans the spans.  Scores and ends are there after every run, SCORE_ONLY and
+ * BIALIGN_RUN_FILL_ONLY included; only the one best local hit of a pair is reported. */
+#define BIALIGN_BATCH_LOCAL 64u
 /* Bits of bialign_params.flags beyond the ones above: BIALIGN_E_INVALID. */
 
 typedef struct bialign_engine bialign_engine; /* one per (process, device) */
@@ -364,6 +392,13 @@ int bialign_batch_get_traces(const bialign_batch* b, uint8_t* trace, int64_t* tr
  * BIALIGN_E_INVALID.  After a SCORE_ONLY or
  * BIALIGN_RUN_FILL_ONLY run end_b is valid and start_b[p] = -1 (so it is for a pair whose traceback is incomplete). */
 int bialign_batch_get_fit_spans(const bialign_batch* b, int32_t* start_b, int32_t* end_b);
+
+/* Local alignments (BIALIGN_BATCH_LOCAL, new in ABI 10 as an added symbol): pair p's alignment is that of
+ * A[start_a[p]:end_a[p]] with B[start_b[p]:end_b[p]] (0-based, half open).  All four arrays are [npairs].  A batch created
+ * without LOCAL (a FIT batch included), or a null batch (it has no observed alignments): BIALIGN_E_INVALID.  After a
+ * SCORE_ONLY or BIALIGN_RUN_FILL_ONLY run the ends are valid and start_a[p] = start_b[p] = -1 (so they are for a pair
+ * whose traceback is incomplete). */
+int bialign_batch_get_local_spans(const bialign_batch* b, int32_t* start_a, int32_t* end_a, int32_t* start_b, int32_t* end_b);
 
 /* Test / introspection hooks.
  * dump_layers re-runs the fill of one pair and writes its layers in the
