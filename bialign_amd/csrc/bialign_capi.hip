@@ -70,7 +70,7 @@ int launch_fill(bialign_batch* b, const DeviceBatch& v, int first, int count) {
   if (b->wide) return launch_fill_wide(b, v, first, count);
   return with_shift(b, "fill", [&](auto s) {
     constexpr int S = decltype(s)::value;
-    if (b->local) return b->affine ? launch_fill_affine_local<S>(b, v, first, count) : launch_fill_linear_local<S>(b, v, first, count);
+    if (b->own_sweeps()) return b->affine ? launch_fill_affine_local<S>(b, v, first, count) : launch_fill_linear_local<S>(b, v, first, count);
     return b->affine ? launch_fill_affine<S>(b, v, first, count) : launch_fill_linear<S>(b, v, first, count);
   });
 }
@@ -330,11 +330,8 @@ int upload_inputs(bialign_batch* b, const bialign_scoring* sc, const bialign_pai
     fprintf(stderr, "[bialign] layers %p (%.1f GiB) memset %.0f GB/s\n", (void*)b->d_layers.p, layer_dw * 4.0 / (1 << 30), gbps);
   }
   HIP_TRY(b->d_scores.alloc(pr->npairs));
-  if (b->fit) HIP_TRY(b->d_fit.alloc(2 * (size_t)pr->npairs));
-  if (b->local) {
-    HIP_TRY(b->d_local_key.alloc((size_t)pr->npairs));
-    HIP_TRY(b->d_local_span.alloc(4 * (size_t)pr->npairs));
-  }
+  if (b->free_ends()) HIP_TRY(b->d_span.alloc(4 * (size_t)pr->npairs));
+  if (b->own_sweeps()) HIP_TRY(b->d_local_key.alloc((size_t)pr->npairs));
   if (b->lean_trace || b->level_trace) HIP_TRY(b->d_tstate.alloc(pr->npairs));
   HIP_TRY(b->d_tlen.alloc(pr->npairs));
   HIP_TRY(b->d_complete.alloc(pr->npairs));
@@ -603,11 +600,9 @@ static int enqueue_run(bialign_batch* b, uint32_t flags) {
   b->build_launches = 0;
   HIP_TRY(hipStreamWaitEvent(st, b->uploaded, 0));
   HIP_TRY(hipMemsetAsync(b->d_err.p, 0, sizeof(int32_t), st));  // the flag is per run
-  if (b->fit) HIP_TRY(hipMemsetAsync(b->d_fit.p, 0xff, 2 * sizeof(int32_t) * b->npairs, st));  // spans: -1 until a kernel writes them
-  if (b->local) {  // keys: zero, below every key a sweep folds in; spans: -1 until a kernel writes them
+  if (b->free_ends()) HIP_TRY(hipMemsetAsync(b->d_span.p, 0xff, sizeof(int32_t) * b->d_span.n, st));  // spans: -1 until a kernel writes them
+  if (b->own_sweeps())  // keys: zero, below every key a sweep folds in
     HIP_TRY(hipMemsetAsync(b->d_local_key.p, 0, sizeof(unsigned long long) * b->npairs, st));
-    HIP_TRY(hipMemsetAsync(b->d_local_span.p, 0xff, 4 * sizeof(int32_t) * b->npairs, st));
-  }
   if (b->null_R) {  // null batch: the replicas' B codes, all of them ahead of the first sweep (timed on its own, outside fill_ms)
     HIP_TRY(hipEventRecord(b->null_evs[0], st));
     if (int rc = launch_shuffle_null(b, 0, b->npairs)) return rc;
@@ -627,7 +622,7 @@ static int enqueue_run(bialign_batch* b, uint32_t flags) {
     }
     HIP_TRY(hipEventRecord(b->evs[3 * c], st));
     int rc = launch_fill(b, v, first, count);
-    if (rc == BIALIGN_OK && b->local) rc = launch_local_finish(b, v, first, count);  // in every storage mode: scores and ends
+    if (rc == BIALIGN_OK && b->own_sweeps()) rc = launch_local_finish(b, v, first, count);  // in every storage mode: scores and ends
     if (rc) return rc;
     HIP_TRY(hipEventRecord(b->evs[3 * c + 1], st));
     if (!b->lean) {  // (with LEAN records the sweep itself wrote the scores)
@@ -732,31 +727,28 @@ int bialign_batch_get_scores(const bialign_batch* b, int32_t* scores) {
   return BIALIGN_OK;
 }
 
-int bialign_batch_get_fit_spans(const bialign_batch* b, int32_t* start_b, int32_t* end_b) {
-  if (!b || !start_b || !end_b) return fail(BIALIGN_E_INVALID, "NULL argument");
-  if (!b->fit) return fail(BIALIGN_E_INVALID, "batch was created without BIALIGN_BATCH_FIT: it has no spans");
+// The spans of a batch of mode `mode`: the first `cols` columns of d_span's rows, scattered into out[0 .. cols)
+static int read_spans(const bialign_batch* b, bialign::AlignMode mode, const char* no_mode, int cols, int32_t* const* out) {
+  if (!b || std::count(out, out + cols, nullptr)) return fail(BIALIGN_E_INVALID, "NULL argument");
+  if (b->mode != mode) return fail(BIALIGN_E_INVALID, "%s", no_mode);
   if (b->null_R) return fail(BIALIGN_E_INVALID, "a null batch has no observed alignments: no spans");
   if (int rc = bialign_batch_wait(const_cast<bialign_batch*>(b))) return rc;
   if (!b->ran) return fail(BIALIGN_E_INVALID, "bialign_batch_run has not been called");
   HIP_TRY(hipSetDevice(b->eng->device));
-  std::vector<int32_t> span(2 * (size_t)b->npairs);
-  HIP_TRY(hipMemcpy(span.data(), b->d_fit.p, sizeof(int32_t) * span.size(), hipMemcpyDeviceToHost));
-  for (int p = 0; p < b->npairs; ++p) start_b[p] = span[2 * p], end_b[p] = span[2 * p + 1];
+  std::vector<int32_t> span((size_t)cols * b->npairs);
+  HIP_TRY(hipMemcpy(span.data(), b->d_span.p, sizeof(int32_t) * span.size(), hipMemcpyDeviceToHost));
+  for (size_t t = 0; t < span.size(); ++t) out[t % cols][t / cols] = span[t];
   return BIALIGN_OK;
 }
 
+int bialign_batch_get_fit_spans(const bialign_batch* b, int32_t* start_b, int32_t* end_b) {
+  int32_t* const out[] = {start_b, end_b};
+  return read_spans(b, bialign::AlignMode::Fit, "batch was created without BIALIGN_BATCH_FIT: it has no spans", 2, out);
+}
+
 int bialign_batch_get_local_spans(const bialign_batch* b, int32_t* start_a, int32_t* end_a, int32_t* start_b, int32_t* end_b) {
-  if (!b || !start_a || !end_a || !start_b || !end_b) return fail(BIALIGN_E_INVALID, "NULL argument");
-  if (!b->local) return fail(BIALIGN_E_INVALID, "batch was created without BIALIGN_BATCH_LOCAL: it has no local spans");
-  if (b->null_R) return fail(BIALIGN_E_INVALID, "a null batch has no observed alignments: no spans");
-  if (int rc = bialign_batch_wait(const_cast<bialign_batch*>(b))) return rc;
-  if (!b->ran) return fail(BIALIGN_E_INVALID, "bialign_batch_run has not been called");
-  HIP_TRY(hipSetDevice(b->eng->device));
-  std::vector<int32_t> span(4 * (size_t)b->npairs);
-  HIP_TRY(hipMemcpy(span.data(), b->d_local_span.p, sizeof(int32_t) * span.size(), hipMemcpyDeviceToHost));
-  for (int p = 0; p < b->npairs; ++p)
-    start_a[p] = span[4 * p], end_a[p] = span[4 * p + 1], start_b[p] = span[4 * p + 2], end_b[p] = span[4 * p + 3];
-  return BIALIGN_OK;
+  int32_t* const out[] = {start_a, end_a, start_b, end_b};
+  return read_spans(b, bialign::AlignMode::Local, "batch was created without BIALIGN_BATCH_LOCAL: it has no local spans", 4, out);
 }
 
 int bialign_batch_get_traces(const bialign_batch* b, uint8_t* trace, int64_t* trace_off, int32_t* trace_len,

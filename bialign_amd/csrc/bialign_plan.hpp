@@ -21,6 +21,7 @@
 namespace bialign {
 
 int fail(int code, const char* fmt, ...);  // records the message bialign_last_error() returns (bialign_capi.hip)
+enum class AlignMode { Global, Fit, Local };
 
 // The host's decisions about one batch.  bialign_batch (bialign_host.hpp) derives from it and adds what lives on the
 // device: buffers, events, run state, the engine.
@@ -72,13 +73,16 @@ struct BatchPlan {
   bool level_trace = false;
   int wide_seg = 0;
   int resw_k = 1;           // strips re-swept and walked per round (more when the batch has few pairs)
-  // Fit alignments (BIALIGN_BATCH_FIT): free end gaps in B.  Tiled bands, full storage or SCORE_ONLY; the generic
-  // tracebacks only (host: trace_fast_lds); never the storage ladder's LEAN_TRACE rung (plan_storage: BIALIGN_E_NOMEM).
-  bool fit = false;
-  // Local alignments (BIALIGN_BATCH_LOCAL): free ends in both molecules.  Tiled bands, beta <= 0 in the affine recurrence,
-  // full storage or SCORE_ONLY; sweeps of their own (launch_fill_*_local) that never pack, never take the slim kernel or a
-  // cross-CU team (decide_pack, slim_available, team_shape); the generic tracebacks only; no LEAN_TRACE rung either.
-  bool local = false;
+  // The alignment mode, one per batch (check_inputs).  Fit (BIALIGN_BATCH_FIT): free end gaps in B.  Local (BIALIGN_BATCH_LOCAL):
+  // free ends in both molecules.  What the host does differently for a mode it reads from the two properties below.
+  AlignMode mode = AlignMode::Global;
+  const char* mode_name() const { return mode == AlignMode::Fit ? "FIT" : "LOCAL"; }  // (for messages about a non-global mode)
+  // free ends: tiled bands, full storage or SCORE_ONLY; spans beside the scores; the generic tracebacks only (host:
+  // trace_fast_lds); never the storage ladder's LEAN_TRACE rung (plan_storage: BIALIGN_E_NOMEM)
+  bool free_ends() const { return mode != AlignMode::Global; }
+  // sweeps of its own (launch_fill_*_local, best-end keys behind them): no packed records, slim kernel or cross-CU team
+  // (decide_pack, slim_available, team_shape); beta <= 0 in the affine recurrence
+  bool own_sweeps() const { return mode == AlignMode::Local; }
 };
 
 // What the host needs of the kernels' compile-time geometry, for a run-time (max_shift, recurrence): read from the types
@@ -133,7 +137,7 @@ struct TeamShape {
 inline bool slim_available(const BatchPlan& b) {
   const char* sw = getenv("BIALIGN_SLIM");  // "0": tests / A-B, the two-wave kernels only
   const bool off = sw && atoi(sw) == 0;
-  return !off && !b.local && b.affine && b.S == 1 && !b.dense && !b.dense1 && !b.wide && b.prm.gap_opening_cost <= 0 && (b.lean || b.pack_now());
+  return !off && !b.own_sweeps() && b.affine && b.S == 1 && !b.dense && !b.dense1 && !b.wide && b.prm.gap_opening_cost <= 0 && (b.lean || b.pack_now());
 }
 inline bool diet8_available(const BatchPlan& b) {  // the eight-wave s=2 affine kernel and its LDS layout
   return b.affine && b.S == 2 && !b.dense && !b.dense1 && b.lds_diet8 <= 160 * 1024;
@@ -154,7 +158,7 @@ inline bool diet8_available(const BatchPlan& b) {  // the eight-wave s=2 affine 
 // xcu8_resident: likewise its eight-wave workgroups (s=2 affine sweep only, else 0); num_cu: the device's compute units
 inline TeamShape team_shape(const BatchPlan& b, int first, int count, int num_cu, int xcu_resident, int xcu8_resident = 0) {
   TeamShape ts;
-  if (b.local) xcu_resident = xcu8_resident = 0;  // local alignments: in-workgroup teams only
+  if (b.own_sweeps()) xcu_resident = xcu8_resident = 0;  // (local alignments) in-workgroup teams only
   const SweepInfo& geo = sweep_info(b);
   const int lag = 2 * (geo.R - 1) + 2 * geo.blk + 16;
   int fit_exact = PROG_WORDS;  // largest team the pairs of this launch allow: T*lag + 64 <= P (P >= 256), two strips per wave
@@ -475,18 +479,16 @@ inline int check_inputs(const bialign_params* prm, const bialign_scoring* sc, co
   constexpr uint32_t KNOWN_FLAGS =
       BIALIGN_BATCH_SCORE_ONLY | BIALIGN_BATCH_LEAN_TRACE | BIALIGN_BATCH_LEVEL_TRACE | BIALIGN_BATCH_FIT | BIALIGN_BATCH_LOCAL;
   if (prm->flags & ~KNOWN_FLAGS) return fail(BIALIGN_E_INVALID, "unknown bits 0x%x in bialign_params.flags", prm->flags & ~KNOWN_FLAGS);
-  b.fit = (prm->flags & BIALIGN_BATCH_FIT) != 0;
-  if (b.fit && (prm->flags & (BIALIGN_BATCH_LEAN_TRACE | BIALIGN_BATCH_LEVEL_TRACE)))
-    return fail(BIALIGN_E_UNSUPPORTED, "FIT exists in full storage and in SCORE_ONLY: not with LEAN_TRACE or LEVEL_TRACE");
-  if (b.fit && b.wide)
-    return fail(BIALIGN_E_UNSUPPORTED, "FIT exists for max_shift <= %d only (the tiled sweeps)", BIALIGN_MAX_SHIFT_TILED);
-  b.local = (prm->flags & BIALIGN_BATCH_LOCAL) != 0;
-  if (b.local && b.fit) return fail(BIALIGN_E_INVALID, "LOCAL and FIT exclude each other");
-  if (b.local && (prm->flags & (BIALIGN_BATCH_LEAN_TRACE | BIALIGN_BATCH_LEVEL_TRACE)))
-    return fail(BIALIGN_E_UNSUPPORTED, "LOCAL exists in full storage and in SCORE_ONLY: not with LEAN_TRACE or LEVEL_TRACE");
-  if (b.local && b.wide)
-    return fail(BIALIGN_E_UNSUPPORTED, "LOCAL exists for max_shift <= %d only (the tiled sweeps)", BIALIGN_MAX_SHIFT_TILED);
-  if (b.local && b.affine && prm->gap_opening_cost > 0)
+  // the mode, decoded once.  Both bits are refused behind the free-ends refusals, which then name FIT: the order in which
+  // callers meet the refusals is part of the interface (tests/mode_expected.txt)
+  const bool fit = (prm->flags & BIALIGN_BATCH_FIT) != 0, local = (prm->flags & BIALIGN_BATCH_LOCAL) != 0;
+  b.mode = fit ? AlignMode::Fit : local ? AlignMode::Local : AlignMode::Global;
+  if (b.free_ends() && (prm->flags & (BIALIGN_BATCH_LEAN_TRACE | BIALIGN_BATCH_LEVEL_TRACE)))
+    return fail(BIALIGN_E_UNSUPPORTED, "%s exists in full storage and in SCORE_ONLY: not with LEAN_TRACE or LEVEL_TRACE", b.mode_name());
+  if (b.free_ends() && b.wide)
+    return fail(BIALIGN_E_UNSUPPORTED, "%s exists for max_shift <= %d only (the tiled sweeps)", b.mode_name(), BIALIGN_MAX_SHIFT_TILED);
+  if (fit && local) return fail(BIALIGN_E_INVALID, "LOCAL and FIT exclude each other");
+  if (b.mode == AlignMode::Local && b.affine && prm->gap_opening_cost > 0)
     return fail(BIALIGN_E_UNSUPPORTED, "LOCAL exists for gap_opening_cost <= 0 only in the affine recurrence (no general-beta sweep)");
   if (prm->flags & BIALIGN_BATCH_LEVEL_TRACE) {
     if (b.lean) return fail(BIALIGN_E_INVALID, "LEVEL_TRACE excludes SCORE_ONLY and LEAN_TRACE");
@@ -590,7 +592,7 @@ inline int plan_pairs(const bialign_pairs* pr, const NullPlan* nul, int64_t colm
     if ((2 * ((int64_t)n + m) + 8) * colmax >= (1 << 28))
       return fail(BIALIGN_E_RANGE, "pair %d: scores may leave the int32 safety window (n+m=%d, column bound %lld)", shown(p),
                   n + m, (long long)colmax);
-    if (b.local && n + m >= LOCAL_MAX_NM)  // the end's position in the pair's key is 32 bits (bialign_local.hpp)
+    if (b.mode == AlignMode::Local && n + m >= LOCAL_MAX_NM)  // the end's position in the pair's key is 32 bits (bialign_local.hpp)
       return fail(BIALIGN_E_UNSUPPORTED, "pair %d: LOCAL takes n + m < %d (n+m=%d)", shown(p), LOCAL_MAX_NM, n + m);
     if (nul) {  // the reduction's int64 sum of squares: replicas * bound^2 with the window's bound on |score| (< 2^28)
       const int64_t bound = (2 * ((int64_t)n + m) + 8) * colmax;
@@ -640,7 +642,7 @@ inline void decide_pack(BatchPlan& b, int64_t colmax) {
   const SweepInfo& pki = sweep_info(b);
   const char* e = getenv("BIALIGN_PACK");  // "0" never, "1" wherever the layout allows (tests), unset: when it pays
   const bool force = e && e[0] == '1';
-  bool ok = b.affine && S >= 1 && S <= BIALIGN_MAX_SHIFT_PACKED && !b.lean && !b.dense1 && !b.local && b.prm.gap_opening_cost <= 0 &&
+  bool ok = b.affine && S >= 1 && S <= BIALIGN_MAX_SHIFT_PACKED && !b.lean && !b.dense1 && !b.own_sweeps() && b.prm.gap_opening_cost <= 0 &&
             !(e && e[0] == '0') &&
             (force || colmax < 8192) &&  // offsets span a few column scores (measured: up to 2.5): beyond this they will not fit
             // s=3 runs one wave per SIMD and is bound by issue: packing pays where the device is full (512 pairs x len 512
@@ -739,9 +741,9 @@ inline int plan_storage(BatchPlan& b, int64_t budget_dw) {
     }
   }
   if (!b.lean && !b.wide && max_need() > budget_dw) {
-    if (b.fit || b.local)  // no silent change of mode: the memory-lean traceback has no FIT or LOCAL form
+    if (b.free_ends())  // no silent change of mode: the memory-lean traceback has no FIT or LOCAL form
       return fail(BIALIGN_E_NOMEM, "a pair needs %lld bytes of layers, budget is %lld: a %s batch does not fall back to LEAN_TRACE",
-                  (long long)max_need() * 4, (long long)budget_dw * 4, b.fit ? "FIT" : "LOCAL");
+                  (long long)max_need() * 4, (long long)budget_dw * 4, b.mode_name());
     b.lean = b.lean_trace = true;
     b.pack = false;
     pick_resw_k();

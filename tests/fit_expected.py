@@ -14,28 +14,14 @@ import random
 import numpy as np
 
 from bialign_amd import synth
+from free_ends_expected import NONE, NONE32, _mutate, cell_seconds, compare_layers, plain_pair, pool_map, run_mask, tables_of  # noqa: F401
 from oracle import oracle
-
-NEG_INF = -(1 << 30)   # BIALIGN_NEG_INF
-LOW = NEG_INF // 2     # layers are compared where the expectation is above this
-NONE = -(1 << 40)      # "no such substring" / "no run covers this cell"
-NONE32 = -(1 << 31)    # ... in the int32 layers a pool worker hands back
 
 
 def cut_tables(mu1, mu2, j0):
     """The (n+1) x (m-j0+1) tables of A against B[j0:] out of the pair's (n+1) x (m+1) tables (column 0 stays)."""
     cut = lambda t: np.ascontiguousarray(np.concatenate([t[:, :1], t[:, j0 + 1:]], axis=1))
     return cut(mu1), cut(mu2)
-
-
-def run_mask(n, mr, s):
-    """[i, j, a, b] -> is (i, j, i+a-s, j+b-s) a cell of the n x mr lattice (the oracle leaves the others unwritten)."""
-    w = 2 * s + 1
-    i = np.arange(n + 1)[:, None, None, None]
-    j = np.arange(mr + 1)[None, :, None, None]
-    k = i + np.arange(w)[None, None, :, None] - s
-    l = j + np.arange(w)[None, None, None, :] - s
-    return (k >= 0) & (k <= n) & (l >= 0) & (l <= mr)
 
 
 def fit_partial(job):
@@ -63,9 +49,8 @@ def fit_partial(job):
 
 def split_jobs(key, n, m, params, mu1, mu2, want_layers=True, seconds=3.0):
     """The jobs of one pair for ``fit_partial``: the starts 0..m-1 cut into ranges of about ``seconds`` of oracle time
-    each (a run of start j0 costs about n (m - j0) band cells; measured: 0.6 M affine band cells per second)."""
-    s = params["max_shift"]
-    per_col = n * (2 * s + 1) ** 2 * (1.0 if params["gap_opening_cost"] != 0 else 1 / 15) / 0.6e6
+    each (a run of start j0 costs about n (m - j0) lattice points)."""
+    per_col = n * cell_seconds(params)
     jobs, lo, acc = [], 0, 0.0
     for j0 in range(m):
         acc += per_col * (m - j0)
@@ -102,33 +87,10 @@ def fit_expected(n, m, params, mu1, mu2, want_layers=True):
 def expected_many(cases, procs=None):
     """``cases``: {key: (n, m, params, mu1, mu2, want_layers)} -> {key: fit_combine's dict}; the oracle runs of all
     cases share one spawn pool."""
-    import multiprocessing as mp
-    import os
     jobs = [j for key, c in cases.items() for j in split_jobs(key, *c)]
     jobs.sort(key=lambda j: -(j[7] - j[6]) * j[1] * (j[2] - j[6]))  # (roughly) the long ones first
-    procs = procs or max(1, min(16, len(os.sched_getaffinity(0)), len(jobs)))
-    with mp.get_context("spawn").Pool(procs) as pool:
-        done = pool.map(fit_partial, jobs, chunksize=1)
+    done = pool_map(fit_partial, jobs, procs)
     return {key: fit_combine(c[0], c[1], c[2]["max_shift"], [d for d in done if d[0] == key]) for key, c in cases.items()}
-
-
-def compare_layers(got, want, n, m, s):
-    """The engine's dump against ``fit_expected``'s layers, over the in-band cells: equal where the expectation is
-    above LOW, below LOW too elsewhere."""
-    ok = run_mask(n, m, s)[None]
-    want = np.where(ok, want, NONE)
-    hi = ok & (want > LOW)
-    np.testing.assert_array_equal(got[hi], want[hi])
-    assert (got[ok & ~hi] <= LOW).all()
-
-
-def tables_of(pair, params):
-    sa, sb, ta, tb = pair
-    return oracle.mu_tables(sa, sb, ta, tb, params)
-
-
-def _mutate(rng, text, alphabet, rate=0.15):
-    return "".join(rng.choice(alphabet) if rng.random() < rate else ch for ch in text)
 
 
 def planted_pair(kind, seed, n, m):
@@ -157,6 +119,4 @@ def planted_pair(kind, seed, n, m):
 
 
 def make_pair(kind, seed, n, m, planted):
-    if planted:
-        return planted_pair(kind, seed, n, m)
-    return synth.rna_pair(seed, n, m) if kind == "rna" else synth.protein_pair(seed, n, m)
+    return planted_pair(kind, seed, n, m) if planted else plain_pair(kind, seed, n, m)

@@ -1,5 +1,5 @@
-"""What a local alignment (BIALIGN_BATCH_LOCAL, include/bialign.h) must give, from the CPU oracle alone.  It generalises
-tests/fit_expected.py from free starts in B to free starts in both molecules.
+"""What a local alignment (BIALIGN_BATCH_LOCAL, include/bialign.h) must give, from the CPU oracle alone: free starts in
+both molecules, where tests/fit_expected.py has them in B (tests/free_ends_expected.py holds what the two share).
 
 A DP value depends only on prefixes: one oracle fill of (A[i0:], B[j0:]) holds, at its diagonal points
 (i1 - i0, j1 - j0, i1 - i0, j1 - j0), the global score of A[i0:i1] against B[j0:j1] for every (i1, j1) at once.  So
@@ -21,7 +21,7 @@ import random
 import numpy as np
 
 from bialign_amd import synth
-from fit_expected import LOW, NONE, NONE32, compare_layers, run_mask, tables_of  # noqa: F401 (shared with the tests)
+from free_ends_expected import NONE, NONE32, _mutate, cell_seconds, compare_layers, plain_pair, pool_map, run_mask, tables_of  # noqa: F401
 from oracle import oracle
 
 
@@ -84,9 +84,8 @@ def local_partial(job):
 
 def split_jobs(key, n, m, params, mu1, mu2, want_layers=True, want_windows=False, seconds=3.0):
     """The jobs of one pair for ``local_partial``: the starts i0 = 0..n-1 cut into ranges of about ``seconds`` of oracle
-    time each (the runs of one i0 cost about (n - i0) m^2 / 2 band cells)."""
-    s = params["max_shift"]
-    per_row = m * m / 2 * (2 * s + 1) ** 2 * (1.0 if params["gap_opening_cost"] != 0 else 1 / 15) / 0.6e6
+    time each (the runs of one i0 cost about (n - i0) m^2 / 2 lattice points)."""
+    per_row = m * m / 2 * cell_seconds(params)
     jobs, lo, acc = [], 0, 0.0
     for i0 in range(n):
         acc += per_row * (n - i0)
@@ -130,15 +129,10 @@ def local_expected(n, m, params, mu1, mu2, want_layers=True, want_windows=True):
 def expected_many(cases, procs=None):
     """``cases``: {key: (n, m, params, mu1, mu2, want_layers)} -> {key: local_combine's dict}; the oracle runs of all
     cases share one spawn pool."""
-    import multiprocessing as mp
-    import os
     jobs = [j for key, c in cases.items() for j in split_jobs(key, *c)]
     jobs.sort(key=lambda j: -sum(j[1] - i0 for i0 in range(j[6], j[7])) * j[2] * j[2] * (2 * j[3]["max_shift"] + 1) ** 2 *
               (15 if j[3]["gap_opening_cost"] != 0 else 1))  # (roughly) the long ones first
-    procs = procs or max(1, min(16, len(os.sched_getaffinity(0)), len(jobs)))
-    oracle.lib()  # (built on first use: here, not by sixteen workers at once)
-    with mp.get_context("spawn").Pool(procs) as pool:
-        done = pool.map(local_partial, jobs, chunksize=1)
+    done = pool_map(local_partial, jobs, procs)
     return {key: local_combine(c[0], c[1], [d for d in done if d[0] == key]) for key, c in cases.items()}
 
 
@@ -153,10 +147,6 @@ def span_score(want, params, mu1, mu2, span):
         return 0
     assert i0 < i1 and j0 < j1, "a window that is empty in one molecule only: keep the windows to score it"
     return window_global(params, mu1, mu2, i0, i1, j0, j1)
-
-
-def _mutate(rng, text, alphabet, rate=0.15):
-    return "".join(rng.choice(alphabet) if rng.random() < rate else ch for ch in text)
 
 
 def planted_pair(seed, n, m):
@@ -178,6 +168,4 @@ def planted_pair(seed, n, m):
 
 
 def make_pair(kind, seed, n, m, planted):
-    if planted:
-        return planted_pair(seed, n, m)
-    return synth.rna_pair(seed, n, m) if kind == "rna" else synth.protein_pair(seed, n, m)
+    return planted_pair(seed, n, m) if planted else plain_pair(kind, seed, n, m)

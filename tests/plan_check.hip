@@ -13,7 +13,8 @@
 //   batch: rec flags, form=lookup|mu1|mu2|mu12|feature, amax bmax (one entry of otherwise zero S1 / S2 tables), mu1 mu2 (the
 //          constant of the dense tables), fa=up,down,unp fb=up,down,unp (one feature value per plane and side), sw,
 //          replicas seed (null batch)
-// Answer of a batch: `rc=<code> msg=<message>`, and on success the plan as print_plan() writes it.
+// Answer of a batch: `rc=<code> msg=<message>`, `mode=<0 global|1 fit|2 local> flags=<the flags the planner saw>`, and on
+// success the plan as print_plan() writes it.
 #include "bialign_plan.hpp"
 
 #include <cstdarg>
@@ -218,7 +219,7 @@ static void run_batch(const Request& r) {
     decide_pack(b, colmax);
     rc = plan_storage(b, budget_dwords(r.num("budget"), (size_t)r.num("free", 1ll << 40)));
   }
-  std::printf("rc=%d msg=%s\n", rc, g_msg);
+  std::printf("rc=%d msg=%s\nmode=%d flags=%u\n", rc, g_msg, (int)b.mode, (unsigned)b.prm.flags);
   if (rc != BIALIGN_OK) return;
   std::printf("colmax=%lld npairs=%d tot_a=%lld tot_b=%lld tot_tab=%lld\n", (long long)colmax, b.npairs, (long long)b.tot_a,
               (long long)b.tot_b, (long long)b.tot_tab);

@@ -1,5 +1,6 @@
 """The batch planner on the CPU: build tests/plan_check.hip (host code only), feed it requests, read its plans.
-Shared by test_plan_host.py (no GPU) and test_gpu_plan_agrees.py (the library reports the same plans)."""
+Shared by test_plan_host.py, test_fit_host.py, test_local_host.py (no GPU) and test_gpu_plan_agrees.py (the library reports
+the same plans); ``build`` also compiles the other stand-alone host checks around the kernels' headers."""
 import os
 import re
 import shutil
@@ -8,15 +9,18 @@ import subprocess
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(REPO, "tests", "plan_check.hip")
 EXPECTED = os.path.join(REPO, "tests", "plan_expected.txt")
+MODE_EXPECTED = os.path.join(REPO, "tests", "mode_expected.txt")
+SCORE_ONLY, LEAN_TRACE, LEVEL_TRACE, FIT, LOCAL = 1, 2, 4, 8, 64   # bialign_params.flags
 E_INVALID, E_UNSUPPORTED, E_NOMEM, E_RANGE = -1, -2, -4, -5   # include/bialign.h
 
 
-def build(tmp, name="plan_check", extra=()):
+def build(tmp, src=SRC, extra=(), name=None):
+    """Compile a stand-alone host program around the headers of bialign_amd/csrc -> the path of the executable."""
     hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     assert os.path.exists(hipcc), "hipcc is needed to compile the host check"
-    exe = os.path.join(str(tmp), name)
+    exe = os.path.join(str(tmp), name or os.path.splitext(os.path.basename(src))[0])
     subprocess.run([hipcc, "-x", "hip", "--cuda-host-only", "-O1", "-std=c++17", *extra,
-                    "-I" + os.path.join(REPO, "bialign_amd", "csrc"), "-o", exe, SRC], check=True)
+                    "-I" + os.path.join(REPO, "bialign_amd", "csrc"), "-o", exe, src], check=True)
     return exe
 
 
@@ -145,3 +149,54 @@ def moved_requests():
         out += [f"env BIALIGN_TEAM={team}"] + forced
     out += ["env BIALIGN_TEAM=", "env BIALIGN_SLIM=0"] + headline + ["env BIALIGN_SLIM="]
     return out
+
+
+# ---- one alignment mode per batch: two pairs of 300 x 400 (full layers at max_shift 1: ~42 MB a pair, LEAN: ~2 MB), on a
+# ---- device that would hold cross-CU teams
+
+SMALL = dict(amax=1100, bmax=800, gamma=-50, delta=-150, num_cu=256, resid=4096, resid8=512, quiet=1)
+ROOMY, TIGHT = 1 << 36, 16 << 20
+
+
+def case(flags, s=1, beta=-150, budget=ROOMY, **kw):
+    """dense=1: mu1 and mu2 as tables; null=1: a null batch; team, pack: the BIALIGN_TEAM / BIALIGN_PACK a test would force"""
+    return dict(flags=flags, s=s, beta=beta, budget=budget, **kw)
+
+
+def mode_answers(exe, cases):
+    """cases: name -> case(...).  -> name -> dict(rc, mode, storage, flags, pack, tw, gw, slim, msg), the team shape being
+    the first chunk's."""
+    lines = []
+    for c in cases.values():
+        words = dict(SMALL, flags=c["flags"], s=c["s"], beta=c["beta"], budget=c["budget"])
+        if c.get("dense"):
+            words.update(form="mu12", mu1=100, mu2=100)
+        if c.get("null"):
+            words.update(replicas=4, seed=7)
+        lines += [f"env BIALIGN_TEAM={c.get('team', '')}", f"env BIALIGN_PACK={c.get('pack', '')}", request(pairs=[(300, 400, 2)], **words)]
+    got = {}
+    for name, p in zip(cases, plans(exe, lines)):
+        team = p.teams[0] if p.teams else dict(tw=1, gw=1, slim=0)
+        got[name] = dict(rc=p.rc, mode=p.mode, storage=p.fields.get("storage", 0), flags=p.flags, pack=p.fields.get("pack", 0),
+                         tw=team["tw"], gw=team["gw"], slim=team["slim"], msg=p.msg)
+    return got
+
+
+# ---- the requests behind tests/mode_expected.txt: every mode against every storage flag, band, gap opening cost and
+# ---- budget, and a few null batches and unknown bits -- the file holds the answers of the planner that kept FIT and LOCAL
+# ---- as two booleans (its `batch` answers had no `mode=` line: drop_mode_lines)
+
+def mode_requests():
+    modes = (0, FIT, LOCAL, FIT | LOCAL)
+    out = [request(pairs=[(300, 400, 2)], flags=mode | storage, s=s, beta=beta, budget=budget, **SMALL)
+           for mode in modes for storage in (0, SCORE_ONLY, LEAN_TRACE, LEVEL_TRACE) for s in (1, 6) for beta in (-150, 0, 100)
+           for budget in (ROOMY, TIGHT)]
+    out += [request(pairs=[(300, 400, 2)], flags=mode, s=1, beta=beta, budget=ROOMY, replicas=4, seed=7, **SMALL)
+            for mode in modes for beta in (-150, 100)]
+    out += [request(pairs=[(300, 400, 2)], flags=mode | bit, s=1, beta=-150, budget=ROOMY, **SMALL) for mode in modes for bit in (16, 0x100)]
+    out.append(request(pairs=[(300, 400, 2)], flags=LOCAL | 32, s=1, beta=-150, budget=ROOMY, replicas=4, seed=7, **SMALL))
+    return out
+
+
+def drop_mode_lines(text):
+    return re.sub(r"^mode=\d flags=\d+\n", "", text, flags=re.M)

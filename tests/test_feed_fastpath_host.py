@@ -7,10 +7,10 @@ with the factored general source dword for all 64 lanes of every DMA round where
 unpack's per-entry test agrees that the whole block is packed.  It prints the steady share per case; the shares are
 asserted here.  The same program is built once more with AddressSanitizer and UBSan and must print the same."""
 import os
-import shutil
-import subprocess
 
 import pytest
+
+import plan_host as ph
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(REPO, "tests", "feed_fastpath_check.hip")
@@ -18,19 +18,8 @@ SRC = os.path.join(REPO, "tests", "feed_fastpath_check.hip")
 GPU_SHAPES = {(61, 256): 2, (110, 280): 3, (221, 500): 6}
 
 
-def _hipcc():
-    exe = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    assert os.path.exists(exe), "hipcc is needed to compile the host check"
-    return exe
-
-
 def _build_and_run(tmp, name, extra):
-    exe = str(tmp / name)
-    subprocess.run([_hipcc(), "-x", "hip", "--cuda-host-only", "-O1", "-std=c++17", *extra,
-                    "-I" + os.path.join(REPO, "bialign_amd", "csrc"), "-o", exe, SRC], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-4000:]
-    return r.stdout
+    return ph.run(ph.build(tmp, SRC, extra, name), "")
 
 
 @pytest.fixture(scope="module")

@@ -3,14 +3,12 @@
   * the expectation the GPU tests rely on (tests/fit_expected.py: one oracle fill per start of the substring) against
     plain ``oracle.solve`` on explicitly cut substrings;
   * the planner's decisions about the flag -- where it is accepted, its refusals, no silent fallback to LEAN_TRACE,
-    null batches pass it through, unknown flag bits are refused -- through tests/fit_plan_check.hip, a stand-alone host
-    program around bialign_plan.hpp;
+    null batches pass it through, unknown flag bits are refused -- as ``batch`` requests to tests/plan_check.hip, the
+    stand-alone host program around bialign_plan.hpp;
   * ``batch_cli --fit``: argument handling and the span line, with the engine stubbed;
   * the binding declares the new entry point."""
 import os
 import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -18,11 +16,12 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import fit_expected as fe
+import plan_host as ph
 from bialign_amd import _lib, synth
 from oracle import oracle
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SCORE_ONLY, LEAN_TRACE, FIT = 1, 2, 8
+SCORE_ONLY, LEAN_TRACE, LEVEL_TRACE, FIT = 1, 2, 4, 8
 E_INVALID, E_UNSUPPORTED, E_NOMEM = -1, -2, -4
 
 
@@ -53,21 +52,34 @@ def test_expectation_equals_global_scores_of_cut_substrings(seed, n, m, beta, s)
 
 # ---- the planner ---------------------------------------------------------------------------------------------------
 
+CASES = {   # two pairs of 300 x 400: full layers at max_shift 1 ~42 MB a pair (packed: about half), the LEAN form ~2 MB
+    "plain-full": ph.case(0),
+    "fit-full-affine": ph.case(FIT),
+    "fit-full-linear": ph.case(FIT, s=2, beta=0),
+    "fit-full-s5": ph.case(FIT, s=5),
+    "fit-full-dense": ph.case(FIT, dense=1),
+    "fit-score-only": ph.case(FIT | SCORE_ONLY),
+    "fit-lean-trace": ph.case(FIT | LEAN_TRACE),
+    "fit-level-trace": ph.case(FIT | LEVEL_TRACE),
+    "fit-level-trace-wide": ph.case(FIT | LEVEL_TRACE, s=7),
+    "fit-wide": ph.case(FIT, s=6),
+    "fit-wide-score-only": ph.case(FIT | SCORE_ONLY, s=6),
+    "plain-tight": ph.case(0, budget=ph.TIGHT),
+    "fit-tight": ph.case(FIT, budget=ph.TIGHT),
+    "fit-tight-score-only": ph.case(FIT | SCORE_ONLY, budget=ph.TIGHT),
+    "null-plain": ph.case(0, null=1),
+    "null-fit": ph.case(FIT, null=1),
+    "null-fit-dense": ph.case(FIT, null=1, dense=1),
+    "unknown-bit": ph.case(16),
+    "unknown-bit-fit": ph.case(FIT | 0x100),
+    "null-unknown-bit": ph.case(32, null=1),
+}
+
+
 @pytest.fixture(scope="module")
 def plan_lines(tmp_path_factory):
-    hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    assert os.path.exists(hipcc), "hipcc is needed to compile the host check"
-    exe = os.path.join(str(tmp_path_factory.mktemp("fitplan")), "fit_plan_check")
-    subprocess.run([hipcc, "-x", "hip", "--cuda-host-only", "-O1", "-std=c++17", "-I" + os.path.join(REPO, "bialign_amd", "csrc"),
-                    "-o", exe, os.path.join(REPO, "tests", "fit_plan_check.hip")], check=True)
-    clean = {k: v for k, v in os.environ.items() if not k.startswith("BIALIGN_")}
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=clean, check=True).stdout
-    got = {}
-    for ln in out.splitlines():
-        mt = re.match(r"(\S+) rc=(-?\d+) fit=(\d) storage=(\d+) flags=(\d+) msg=(.*)", ln)
-        got[mt.group(1)] = dict(rc=int(mt.group(2)), fit=int(mt.group(3)), storage=int(mt.group(4)), flags=int(mt.group(5)),
-                                msg=mt.group(6))
-    return got
+    got = ph.mode_answers(ph.build(tmp_path_factory.mktemp("fitplan")), CASES)
+    return {name: dict(rc=g["rc"], fit=int(g["mode"] == 1), storage=g["storage"], flags=g["flags"], msg=g["msg"]) for name, g in got.items()}
 
 
 def test_planner_accepts_fit_in_full_storage_and_score_only(plan_lines):

@@ -2,7 +2,6 @@
 substring gives every substring's global score, hence the fit score, the smallest best end, and the FIT layers.
 
 The oracle runs of every case of this module are made once, in one spawn pool (``ref``), and shared."""
-import math
 import os
 import sys
 
@@ -11,23 +10,20 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import fit_expected as fe
+import free_ends_gpu as fg
 from bialign_amd import significance as sg
 from bialign_amd import synth
+from free_ends_gpu import feature_mu2, pad, params_of, seq_mu1, stats_of
 
 pytestmark = pytest.mark.gpu
 
 SHIFTS, NS, MS = (0, 1, 2, 3, 5), (1, 22, 50), (50, 97)
 SHAPES = [(n, m) for n in NS for m in MS]
-COSTS = {"affine": {}, "one-layer": dict(gap_opening_cost=0), "beta>0": dict(gap_opening_cost=100)}
-BASE = {"protein": synth.PROTEIN_PARAMS, "rna": synth.RNA_PARAMS}
 # max_shift 1: n = 50 spans three strips of 21 rows, m = 97 a dozen 8-column ghost blocks and six range-check intervals.
 # A team of three waves needs six strips and a column period of 280: the smallest such shape, for the forced team shapes.
 TEAM_SHAPE = (101, 278)
 NULL_R, NULL_SEED = 8, 5
-
-
-def params_of(kind, cost, s):
-    return dict(BASE[kind], max_shift=s, **COSTS[cost])
+pair_of = fg.pair_of(fe.make_pair, 7000)
 
 
 def case_pairs(cost, s):
@@ -43,60 +39,15 @@ def case_pairs(cost, s):
     return out
 
 
-def pair_of(kind, n, m, planted):
-    return fe.make_pair(kind, 7000 + 31 * n + m + (500 if planted else 0), n, m, planted)
-
-
 def main_cases():
     return [(cost, s) for cost in ("affine", "one-layer") for s in SHIFTS] + [("beta>0", 1)]
-
-
-def feature_molecules():
-    """Two RNA molecules with real-valued features (A, then the longer B): three non-negative numbers per residue that
-    sum to 1."""
-    rng = np.random.default_rng(77)
-    mols = []
-    for length in (20, 47):
-        seq = "".join(rng.choice(list(synth.RNA_ALPHABET), size=length))
-        f = rng.random((3, length))
-        f /= f.sum(axis=0)
-        mols.append((seq, tuple(np.ascontiguousarray(x) for x in f)))
-    return mols
-
-
-def feature_mu2(fa, fb, sw):
-    """(n+1) x (m+1) table of the reference's expression (pyx:416-423), row and column 0 zero."""
-    n, m = len(fa[0]), len(fb[0])
-    tab = np.zeros((n + 1, m + 1), dtype=np.int32)
-    for k in range(n):
-        for l in range(m):
-            tab[k + 1, l + 1] = int(sw * (math.sqrt(fa[0][k] * fb[0][l]) + math.sqrt(fa[1][k] * fb[1][l]) + math.sqrt(fa[2][k] * fb[2][l])))
-    return tab
-
-
-def seq_mu1(seq_a, seq_b, params):
-    return fe.tables_of((seq_a, seq_b, "." * len(seq_a), "." * len(seq_b)), dict(params, type="RNA"))[0]
-
-
-def pad(tab):
-    """An (n, m) dense table as the oracle's (n+1) x (m+1) table."""
-    out = np.zeros((tab.shape[0] + 1, tab.shape[1] + 1), dtype=np.int32)
-    out[1:, 1:] = tab
-    return out
 
 
 FORM_PARAMS = dict(synth.PROTEIN_PARAMS)
 FORM_PAIR = fe.make_pair("protein", 4242, 22, 50, True)
 NULL_PAIRS = [fe.make_pair("protein", 4300, 22, 50, True), fe.make_pair("protein", 4301, 15, 41, False)]
-
-
-def form_tables():
-    """The dense tables of the forms' cases: mu1 and mu2 of FORM_PAIR with position-specific changes."""
-    rng = np.random.default_rng(9)
-    mu1, mu2 = fe.tables_of(FORM_PAIR, FORM_PARAMS)
-    d1 = (mu1[1:, 1:] + rng.integers(-150, 150, size=(22, 50))).astype(np.int32)
-    d2 = (mu2[1:, 1:] + rng.integers(-200, 200, size=(22, 50))).astype(np.int32)
-    return mu1, mu2, d1, d2
+feature_molecules = lambda: fg.feature_molecules(77, (20, 47))
+form_tables = lambda: fg.form_tables(FORM_PAIR, FORM_PARAMS)
 
 
 @pytest.fixture(scope="module")
@@ -308,12 +259,6 @@ def test_feature_form(ref):
 
 
 # ---- null batches ---------------------------------------------------------------------------------------------------
-
-def stats_of(replica_scores, observed):
-    arr = np.asarray(replica_scores, dtype=np.int64)
-    return dict(sum=arr.sum(axis=1), sumsq=(arr * arr).sum(axis=1), min=arr.min(axis=1), max=arr.max(axis=1),
-                n_ge=(arr >= np.asarray(observed)[:, None]).sum(axis=1), replicas=np.full(len(arr), arr.shape[1]))
-
 
 def test_null_batch_scores_the_shuffles_in_fit_mode(ref):
     want = [[ref[("null", p, r)]["score"] for r in range(NULL_R)] for p in range(len(NULL_PAIRS))]

@@ -11,7 +11,6 @@ about 0.6 M cells per second and core in the affine recurrence, a fifteenth of t
 large shape, five bands: 10 affine expectations of 8..12 s, 10 one-layer ones of under 1 s, the small shapes, forms and
 null replicas another 20 s: about 150 core-seconds, 10 to 20 s of wall time in a pool of 16.
 """
-import math
 import os
 import sys
 
@@ -20,14 +19,14 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import local_expected as le
+import free_ends_gpu as fg
 from bialign_amd import significance as sg
 from bialign_amd import synth
+from free_ends_gpu import feature_mu2, pad, params_of, seq_mu1, stats_of
 
 pytestmark = pytest.mark.gpu
 
 SHIFTS, M_LONG, M_SHORT = (0, 1, 2, 3, 5), 41, 7
-COSTS = {"affine": {}, "one-layer": dict(gap_opening_cost=0)}
-BASE = {"protein": synth.PROTEIN_PARAMS, "rna": synth.RNA_PARAMS}
 # max_shift 2: a team of four waves needs eight strips and a column period of 280 -- the smallest such shape
 TEAM_SHAPE, TEAM_SHIFT, TEAM_SIZES = (101, 278), 2, (1, 4)
 NULL_R, NULL_SEED = 3, 5
@@ -42,8 +41,7 @@ def shapes_of(s):
     return [(rows_of(s), M_LONG), (1, M_LONG), (rows_of(s), M_SHORT)]
 
 
-def params_of(kind, cost, s):
-    return dict(BASE[kind], max_shift=s, **COSTS[cost])
+pair_of = fg.pair_of(le.make_pair, 9000)
 
 
 def case_pairs(s):
@@ -52,60 +50,16 @@ def case_pairs(s):
     return [c for n, m in shapes_of(s) for c in (("protein", n, m, True), ("rna", n, m, False))]
 
 
-def pair_of(kind, n, m, planted):
-    return le.make_pair(kind, 9000 + 31 * n + m + (500 if planted else 0), n, m, planted)
-
-
 def main_cases():
     return [(cost, s) for cost in ("affine", "one-layer") for s in SHIFTS]
-
-
-def feature_molecules():
-    """Two RNA molecules with real-valued features: three non-negative numbers per residue that sum to 1."""
-    rng = np.random.default_rng(78)
-    mols = []
-    for length in (16, 30):
-        seq = "".join(rng.choice(list(synth.RNA_ALPHABET), size=length))
-        f = rng.random((3, length))
-        f /= f.sum(axis=0)
-        mols.append((seq, tuple(np.ascontiguousarray(x) for x in f)))
-    return mols
-
-
-def feature_mu2(fa, fb, sw):
-    """(n+1) x (m+1) table of the reference's expression (pyx:416-423), row and column 0 zero."""
-    n, m = len(fa[0]), len(fb[0])
-    tab = np.zeros((n + 1, m + 1), dtype=np.int32)
-    for k in range(n):
-        for l in range(m):
-            tab[k + 1, l + 1] = int(sw * (math.sqrt(fa[0][k] * fb[0][l]) + math.sqrt(fa[1][k] * fb[1][l]) + math.sqrt(fa[2][k] * fb[2][l])))
-    return tab
-
-
-def seq_mu1(seq_a, seq_b, params):
-    return le.tables_of((seq_a, seq_b, "." * len(seq_a), "." * len(seq_b)), dict(params, type="RNA"))[0]
-
-
-def pad(tab):
-    """An (n, m) dense table as the oracle's (n+1) x (m+1) table."""
-    out = np.zeros((tab.shape[0] + 1, tab.shape[1] + 1), dtype=np.int32)
-    out[1:, 1:] = tab
-    return out
 
 
 FORM_PARAMS = dict(synth.PROTEIN_PARAMS)
 FORM_SHAPE = (22, 30)
 FORM_PAIR = le.make_pair("protein", 4242, *FORM_SHAPE, True)
 NULL_PAIRS = [le.make_pair("protein", 4300, 14, 24, True), le.make_pair("protein", 4301, 11, 19, False)]
-
-
-def form_tables():
-    """The dense tables of the forms' cases: mu1 and mu2 of FORM_PAIR with position-specific changes."""
-    rng = np.random.default_rng(9)
-    mu1, mu2 = le.tables_of(FORM_PAIR, FORM_PARAMS)
-    d1 = (mu1[1:, 1:] + rng.integers(-150, 150, size=FORM_SHAPE)).astype(np.int32)
-    d2 = (mu2[1:, 1:] + rng.integers(-200, 200, size=FORM_SHAPE)).astype(np.int32)
-    return mu1, mu2, d1, d2
+feature_molecules = lambda: fg.feature_molecules(78, (16, 30))
+form_tables = lambda: fg.form_tables(FORM_PAIR, FORM_PARAMS)
 
 
 @pytest.fixture(scope="module")
@@ -302,12 +256,6 @@ def test_feature_form(ref):
 
 
 # ---- null batches ---------------------------------------------------------------------------------------------------
-
-def stats_of(replica_scores, observed):
-    arr = np.asarray(replica_scores, dtype=np.int64)
-    return dict(sum=arr.sum(axis=1), sumsq=(arr * arr).sum(axis=1), min=arr.min(axis=1), max=arr.max(axis=1),
-                n_ge=(arr >= np.asarray(observed)[:, None]).sum(axis=1), replicas=np.full(len(arr), arr.shape[1]))
-
 
 def test_null_batch_scores_the_shuffles_in_local_mode(ref):
     want = [[ref[("null", p, r)]["score"] for r in range(NULL_R)] for p in range(len(NULL_PAIRS))]

@@ -3,14 +3,12 @@
   * the expectation the GPU tests rely on (tests/local_expected.py: one oracle fill per start (i0, j0)) against plain
     ``oracle.solve`` on explicitly cut windows;
   * the planner's decisions about the flag -- where it is accepted, every refusal, no silent fallback to LEAN_TRACE, null
-    batches pass it through, bits 16 and 32 stay unknown, no pack, no slim sweep and no cross-CU team -- through
-    tests/local_plan_check.hip, a stand-alone host program around bialign_plan.hpp;
+    batches pass it through, bits 16 and 32 stay unknown, no pack, no slim sweep and no cross-CU team -- as ``batch``
+    requests to tests/plan_check.hip, the stand-alone host program around bialign_plan.hpp;
   * ``batch_cli --local``: argument handling, the span lines and the windows, with the engine stubbed;
   * the binding declares the new entry point."""
 import os
 import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -18,11 +16,12 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import local_expected as le
+import plan_host as ph
 from bialign_amd import _lib, synth
 from oracle import oracle
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SCORE_ONLY, LEAN_TRACE, FIT, LOCAL = 1, 2, 8, 64
+SCORE_ONLY, LEAN_TRACE, LEVEL_TRACE, FIT, LOCAL = 1, 2, 4, 8, 64
 E_INVALID, E_UNSUPPORTED, E_NOMEM = -1, -2, -4
 
 
@@ -76,21 +75,45 @@ def test_planted_pair_has_an_inner_window():
 
 # ---- the planner ---------------------------------------------------------------------------------------------------
 
+CASES = {   # two pairs of 300 x 400: full layers at max_shift 1 ~42 MB a pair, the LEAN form ~2 MB
+    "plain-full": ph.case(0),
+    "local-full-affine": ph.case(LOCAL),
+    "local-full-linear": ph.case(LOCAL, s=2, beta=0),
+    "local-full-s0": ph.case(LOCAL, s=0),
+    "local-full-s5": ph.case(LOCAL, s=5),
+    "local-full-dense": ph.case(LOCAL, dense=1),
+    "local-score-only": ph.case(LOCAL | SCORE_ONLY),
+    "local-fit": ph.case(LOCAL | FIT),
+    "local-lean-trace": ph.case(LOCAL | LEAN_TRACE),
+    "local-level-trace": ph.case(LOCAL | LEVEL_TRACE),
+    "local-level-trace-wide": ph.case(LOCAL | LEVEL_TRACE, s=7),
+    "local-wide": ph.case(LOCAL, s=6),
+    "local-wide-score-only": ph.case(LOCAL | SCORE_ONLY, s=6),
+    "local-beta-positive": ph.case(LOCAL, beta=100),
+    "plain-tight": ph.case(0, budget=ph.TIGHT),
+    "local-tight": ph.case(LOCAL, budget=ph.TIGHT),
+    "local-tight-score-only": ph.case(LOCAL | SCORE_ONLY, budget=ph.TIGHT),
+    "null-plain": ph.case(0, null=1),
+    "null-local": ph.case(LOCAL, null=1),
+    "null-local-dense": ph.case(LOCAL, null=1, dense=1),
+    "unknown-bit-16": ph.case(16),
+    "unknown-bit-32": ph.case(32),
+    "unknown-bit-local": ph.case(LOCAL | 0x100),
+    "null-unknown-bit": ph.case(32, null=1),
+    # what a test can force: without the flag it takes, with the flag it does not
+    "plain-forced-pack-x4": ph.case(0, team="x4", pack="1"),
+    "local-forced-pack-x4": ph.case(LOCAL, team="x4", pack="1"),
+    "plain-forced-3": ph.case(0, team="3", pack="1"),
+    "local-forced-3": ph.case(LOCAL, team="3", pack="1"),
+    "local-forced-h2": ph.case(LOCAL, s=2, team="h2", pack="1"),
+    "local-score-only-forced-3": ph.case(LOCAL | SCORE_ONLY, team="3"),
+}
+
+
 @pytest.fixture(scope="module")
 def plan_lines(tmp_path_factory):
-    hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    assert os.path.exists(hipcc), "hipcc is needed to compile the host check"
-    exe = os.path.join(str(tmp_path_factory.mktemp("localplan")), "local_plan_check")
-    subprocess.run([hipcc, "-x", "hip", "--cuda-host-only", "-O1", "-std=c++17", "-I" + os.path.join(REPO, "bialign_amd", "csrc"),
-                    "-o", exe, os.path.join(REPO, "tests", "local_plan_check.hip")], check=True)
-    clean = {k: v for k, v in os.environ.items() if not k.startswith("BIALIGN_")}
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=clean, check=True).stdout
-    got = {}
-    for ln in out.splitlines():
-        mt = re.match(r"(\S+) rc=(-?\d+) local=(\d) storage=(\d+) flags=(\d+) pack=(\d) tw=(\d+) gw=(\d+) slim=(\d) msg=(.*)", ln)
-        got[mt.group(1)] = dict(zip(("rc", "local", "storage", "flags", "pack", "tw", "gw", "slim"), (int(x) for x in mt.groups()[1:9])),
-                                msg=mt.group(10))
-    return got
+    got = ph.mode_answers(ph.build(tmp_path_factory.mktemp("localplan")), CASES)
+    return {name: dict(g, local=int(g["mode"] == 2)) for name, g in got.items()}
 
 
 def accepted(got, storage, flags):

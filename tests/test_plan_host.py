@@ -6,6 +6,8 @@ uploads; tests/plan_check.hip is a stand-alone host program around the same func
   * the storage ladder takes the steps the GPU fallback tests expect, from their inputs;
   * nothing moved: team_shape, plan_chunks, sweep_geometry, lds_need* and cells_of answer tests/plan_expected.txt, the
     table the code gave before it moved into the header;
+  * one mode, the rules as before: every combination of FIT / LOCAL with the storage flags, bands, gap opening costs and
+    budgets answers tests/mode_expected.txt, the table the planner gave while it kept the two flags as two booleans;
   * the same program under AddressSanitizer and UBSan prints the same; the header calls nothing of HIP."""
 import os
 import re
@@ -218,8 +220,19 @@ def test_moved_functions_answer_as_before_the_split(moved):
     assert len(teams) >= 15 and any("slim=1" in t for t in teams) and any("tw=8 gw=" in t and "gw=1 " not in t for t in teams)
 
 
+def test_modes_answer_as_the_two_booleans_did(exe):
+    got = ph.drop_mode_lines(ph.run(exe, "\n".join(ph.mode_requests()) + "\n")).splitlines()
+    with open(ph.MODE_EXPECTED) as f:
+        want = [ln for ln in f.read().splitlines() if not ln.startswith("#")]
+    for at, (g, w) in enumerate(zip(got, want), 1):
+        assert g == w, f"line {at}"
+    assert len(got) == len(want)
+    refusals = {ln.split(" msg=")[1] for ln in want if ln.startswith("rc=-")}
+    assert len(refusals) >= 12 and sum(ln == "rc=0 msg=" for ln in want) >= 40
+
+
 def test_same_under_address_and_ub_sanitizers(moved, tmp_path):
-    san = ph.build(tmp_path, "plan_check_san", ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])
+    san = ph.build(tmp_path, name="plan_check_san", extra=["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])
     assert ph.run(san, "\n".join(ph.moved_requests()) + "\n") == moved
     reqs = [window_request([p], p.k + d) for p in we.BOTH_SIDES for d in (0, 1)] + \
            [ph.request(pairs=c["pairs"], replan=1, **{k: v for k, v in c.items() if k != "pairs"}) for c in CHUNKED.values()]

@@ -9,10 +9,10 @@ scalar base + lane offset + immediate with the per-lane store address, the one-i
 and, at every step, the mirrors with lane 0.  It prints the step counts per case; they are asserted here.  The same program
 is built once more with AddressSanitizer and UBSan and must print the same."""
 import os
-import shutil
-import subprocess
 
 import pytest
+
+import plan_host as ph
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(REPO, "tests", "step_addr_check.hip")
@@ -21,19 +21,8 @@ LAG, RR = 72, 20               # max_shift 1: 2 (R - 1) + 2 BLK + 16; lattice ro
 LO, Q0 = 44, 1                 # Pack<1>: first interior phase, first strip with interior steps
 
 
-def _hipcc():
-    exe = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    assert os.path.exists(exe), "hipcc is needed to compile the host check"
-    return exe
-
-
 def _build_and_run(tmp, name, extra):
-    exe = str(tmp / name)
-    subprocess.run([_hipcc(), "-x", "hip", "--cuda-host-only", "-O1", "-std=c++17", *extra,
-                    "-I" + os.path.join(REPO, "bialign_amd", "csrc"), "-o", exe, SRC], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-4000:]
-    return r.stdout
+    return ph.run(ph.build(tmp, SRC, extra, name), "")
 
 
 @pytest.fixture(scope="module")

@@ -9,29 +9,18 @@ packed_load(packed_addr()) with packed_cell on every in-band cell.  It prints, p
 how many took the fast path; the coverage is asserted here.  The same program is built once more with AddressSanitizer
 and UBSan and must print the same."""
 import os
-import shutil
-import subprocess
 
 import pytest
+
+import plan_host as ph
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(REPO, "tests", "trace_fast_check.hip")
 RR = {1: 20, 2: 11, 3: 8}
 
 
-def _hipcc():
-    exe = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    assert os.path.exists(exe), "hipcc is needed to compile the host check"
-    return exe
-
-
 def _build_and_run(tmp, name, extra):
-    exe = str(tmp / name)
-    subprocess.run([_hipcc(), "-x", "hip", "--cuda-host-only", "-O1", "-std=c++17", *extra,
-                    "-I" + os.path.join(REPO, "bialign_amd", "csrc"), "-o", exe, SRC], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-4000:]
-    return r.stdout
+    return ph.run(ph.build(tmp, SRC, extra, name), "")
 
 
 @pytest.fixture(scope="module")
