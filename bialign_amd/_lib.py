@@ -37,6 +37,7 @@ BATCH_LEAN_TRACE = 2  # BIALIGN_BATCH_LEAN_TRACE
 BATCH_LEVEL_TRACE = 4  # BIALIGN_BATCH_LEVEL_TRACE
 BATCH_FIT = 8  # BIALIGN_BATCH_FIT: fit alignments, free end gaps in B
 BATCH_LOCAL = 64  # BIALIGN_BATCH_LOCAL: local alignments, free ends in both molecules
+BATCH_OVERLAP = 128  # BIALIGN_BATCH_OVERLAP: overlap alignments, the global alignment with free end gaps in both molecules
 
 
 class Scoring(ctypes.Structure):
@@ -122,6 +123,7 @@ SYMBOLS = [
     ("bialign_batch_get_traces", ctypes.c_int, [ctypes.c_void_p, c_u8p, c_i64p, c_i32p, c_i32p]),
     ("bialign_batch_get_fit_spans", ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p]),
     ("bialign_batch_get_local_spans", ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p, c_i32p]),
+    ("bialign_batch_get_overlap_spans", ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p, c_i32p]),
     ("bialign_batch_dump_layers", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_i32p]),
     ("bialign_batch_create_null", ctypes.c_int,
      [ctypes.c_void_p, ctypes.POINTER(Params), ctypes.POINTER(Scoring), ctypes.POINTER(Pairs),

@@ -76,9 +76,10 @@ def encode_pairs(pairs, params):
 
 def make_batch(pairs, params, engine=None, hbm_budget_bytes=0, recurrence=0, mu2_dense=None,
                score_only=False, lean_trace=False, mu1_dense=None, level_trace=False, null_dense=None, fit=False,
-               local=False):
+               local=False, overlap=False):
     """``fit``: fit alignments, A inside a longer B with B's end gaps free (engine.Batch).
     ``local``: local alignments, the best-scoring parts of A and B with the ends of both free (engine.Batch).
+    ``overlap``: overlap alignments, the global alignment with the end gaps of both molecules free (engine.Batch).
     ``mu1_dense`` / ``mu2_dense``: optional lists of one (len A, len B) int table per pair (engine.Batch).
     ``level_trace``: full results from checkpointed levels, for bands beyond the tiled kernels (engine.Batch).
     ``null_dense``: ``(replicas, seed)``, a null batch of these pairs with their dense tables
@@ -96,7 +97,7 @@ def make_batch(pairs, params, engine=None, hbm_budget_bytes=0, recurrence=0, mu2
                  params["gap_opening_cost"], params["gap_cost"], params["shift_cost"],
                  params["max_shift"], hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence,
                  mu2_dense=mu2_dense, score_only=score_only, lean_trace=lean_trace, mu1_dense=mu1_dense,
-                 level_trace=level_trace, fit=fit, local=local, **({} if null_dense is None else dict(null_dense=null_dense)))
+                 level_trace=level_trace, fit=fit, local=local, overlap=overlap, **({} if null_dense is None else dict(null_dense=null_dense)))
 
 
 def _check_storage(score_only, lean_trace, level_trace):
@@ -107,7 +108,7 @@ def _check_storage(score_only, lean_trace, level_trace):
 
 def make_feature_batch(molecules, pair_index, params, engine=None, hbm_budget_bytes=0, recurrence=0,
                        score_only=False, lean_trace=False, mu1_dense=None, level_trace=False, null=None, fit=False,
-                       local=False):
+                       local=False, overlap=False):
     """Batch with mu2 in FEATURE form (include/bialign.h, bialign_features): RNA molecules with real-valued
     structure features, e.g. from predicted base-pair probabilities.  ``molecules``: a list of
     ``(seq, (up, down, unp))``, three numbers per residue as ``scoring.rna_features`` makes them; ``pair_index``: a
@@ -120,7 +121,8 @@ def make_feature_batch(molecules, pair_index, params, engine=None, hbm_budget_by
     ``replicas`` shuffles of its B molecule, a residue's three numbers moving with its letter; score-only, mu1 in
     LOOKUP form.
     ``fit``: fit alignments, A inside a longer B with B's end gaps free (engine.Batch).
-    ``local``: local alignments, the best-scoring parts of A and B with the ends of both free (engine.Batch)."""
+    ``local``: local alignments, the best-scoring parts of A and B with the ends of both free (engine.Batch).
+    ``overlap``: overlap alignments, the global alignment with the end gaps of both molecules free (engine.Batch)."""
     from .scoring import check_features
     _check_storage(score_only, lean_trace, level_trace)
     if null is not None:
@@ -153,7 +155,7 @@ def make_feature_batch(molecules, pair_index, params, engine=None, hbm_budget_by
                  params["gap_opening_cost"], params["gap_cost"], params["shift_cost"],
                  params["max_shift"], hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence,
                  score_only=score_only, lean_trace=lean_trace, mu1_dense=mu1_dense, level_trace=level_trace,
-                 mu2_features=(int(params["structure_weight"]), flat, flat), null=null, fit=fit, local=local)
+                 mu2_features=(int(params["structure_weight"]), flat, flat), null=null, fit=fit, local=local, overlap=overlap)
 
 
 def shard(npairs, rank, world_size, costs=None):

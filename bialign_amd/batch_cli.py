@@ -24,6 +24,11 @@ alignments, the ends of both molecules free: include/bialign.h, BIALIGN_BATCH_LO
 lines ``A span\t <start_a+1>..<end_a>`` and ``B span\t <start_b+1>..<end_b>`` (1-based, inclusive) follow ``SCORE:``,
 the alignment is decoded on the two windows, ``--score_only`` lines gain the 1-based ends of A and B as a fourth and
 fifth column, and ``--zscore`` scores the shuffles in the same mode.
+
+``--overlap`` aligns every pair end to end on the stretch its molecules share, with the end gaps of both molecules free
+(overlap alignments: include/bialign.h, BIALIGN_BATCH_OVERLAP; not with ``--fit`` or ``--local``).  The output has the
+form of ``--local``: the ``A span`` and ``B span`` lines, the alignment decoded on the two windows, the 1-based ends as
+fourth and fifth column under ``--score_only``, ``--zscore`` in the same mode.
 """
 import argparse
 import sys
@@ -69,6 +74,10 @@ def build_parser():
                    help="Local alignments: the best-scoring part of molecule A against the best-scoring part of molecule "
                         "B (the ends of both are free); prints the parts as 'A span' and 'B span' lines behind 'SCORE:'. "
                         "Not with --fit.")
+    p.add_argument("--overlap", action="store_true",
+                   help="Overlap alignments: the global alignment whose end gaps are free in both molecules (dovetails, "
+                        "containment in either direction); prints the aligned stretch as 'A span' and 'B span' lines "
+                        "behind 'SCORE:'. Not with --fit or --local.")
     p.add_argument("--zscore_seed", type=int, default=0, metavar="N",
                    help="Seed of the shuffles (default 0); shuffle r of a pair is a function of the seed, r and the "
                         "pair's position among the pairs its process aligns.")
@@ -88,7 +97,7 @@ def span_line(start_b, end_b):
 
 
 def local_span_lines(start_a, end_a, start_b, end_b):
-    """The lines behind ``SCORE:`` of a ``--local`` pair: the aligned parts of A and B, 1-based and inclusive (an empty
+    """The lines behind ``SCORE:`` of a ``--local`` or ``--overlap`` pair: the aligned parts of A and B, 1-based and inclusive (an empty
     part reads start+1..start)."""
     return [f"A span\t {int(start_a) + 1}..{int(end_a)}", span_line(start_b, end_b)]
 
@@ -115,7 +124,7 @@ def fit_window(seq_b, str_b, start_b, end_b, rna):
 def pair_block(idx, rec, params, score, trace, complete, verbose, span=None, local_span=None):
     """Output lines of one pair, framed like the reference CLI (bialign.py:109-124).  ``span``: ``(start_b, end_b)`` of
     a ``--fit`` pair, whose alignment is decoded on that part of B.  ``local_span``: ``(start_a, end_a, start_b, end_b)``
-    of a ``--local`` pair, whose alignment is decoded on those parts of A and B."""
+    of a ``--local`` or ``--overlap`` pair, whose alignment is decoded on those parts of A and B."""
     name_a, seq_a, str_a, name_b, seq_b, str_b = rec
     yield f">pair {idx}\t{name_a}\t{name_b}"
     yield "Input:"
@@ -157,8 +166,10 @@ def _main(argv=None):
     args = parser.parse_args(argv)
     if args.fit and args.local:
         parser.error("--fit and --local exclude each other")
+    if args.overlap and (args.fit or args.local):
+        parser.error("--overlap excludes --fit and --local")
     params = {k: v for k, v in vars(args).items()
-              if k not in ("pairs", "verbose", "score_only", "zscore", "zscore_seed", "fit", "local")}
+              if k not in ("pairs", "verbose", "score_only", "zscore", "zscore_seed", "fit", "local", "overlap")}
     if args.zscore:
         from .significance import check_null
         check_null((args.zscore, args.zscore_seed))
@@ -173,20 +184,21 @@ def _main(argv=None):
     if len(mine):
         batch = make_batch([(r[1], r[4], r[2], r[5]) for r in (records[p] for p in mine)], params,
                            engine=default_engine(local_rank), score_only=args.score_only, fit=args.fit,
-                           local=args.local)
+                           local=args.local, overlap=args.overlap)
         batch.run()
         scores = batch.scores()
         start_b, end_b = batch.fit_spans() if args.fit else (None, None)
-        lspans = batch.local_spans() if args.local else None
+        lspans = batch.local_spans() if args.local else batch.overlap_spans() if args.overlap else None
         z = None
         if args.zscore:
             from .significance import zscores
             z = zscores([(r[1], r[4], r[2], r[5]) for r in (records[p] for p in mine)], params, replicas=args.zscore,
-                        seed=args.zscore_seed, observed=scores, engine=default_engine(local_rank), fit=args.fit, local=args.local)
+                        seed=args.zscore_seed, observed=scores, engine=default_engine(local_rank), fit=args.fit, local=args.local,
+                        overlap=args.overlap)
         if args.score_only:
             for t, p in enumerate(mine):
                 print(f"pair {p}\t{records[p][0]}\t{records[p][3]}\t{int(scores[t])}" + (f"\t{int(end_b[t])}" if args.fit else "") +
-                      (f"\t{int(lspans[1][t])}\t{int(lspans[3][t])}" if args.local else ""))
+                      (f"\t{int(lspans[1][t])}\t{int(lspans[3][t])}" if lspans else ""))
                 if z:
                     print(zscore_line(z, t))
         else:
@@ -194,7 +206,7 @@ def _main(argv=None):
             for t, p in enumerate(mine):
                 trace = trace_codes_to_columns(traces[t], as_tuples=not batch.affine)
                 span = (int(start_b[t]), int(end_b[t])) if args.fit and complete[t] else None
-                lspan = tuple(int(x[t]) for x in lspans) if args.local and complete[t] else None
+                lspan = tuple(int(x[t]) for x in lspans) if lspans and complete[t] else None
                 for line in pair_block(p, records[p], params, int(scores[t]), trace, bool(complete[t]), args.verbose, span, lspan):
                     print(line)
                 if z:

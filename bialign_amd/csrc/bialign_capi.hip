@@ -331,7 +331,7 @@ int upload_inputs(bialign_batch* b, const bialign_scoring* sc, const bialign_pai
   }
   HIP_TRY(b->d_scores.alloc(pr->npairs));
   if (b->free_ends()) HIP_TRY(b->d_span.alloc(4 * (size_t)pr->npairs));
-  if (b->own_sweeps()) HIP_TRY(b->d_local_key.alloc((size_t)pr->npairs));
+  if (b->end_key()) HIP_TRY(b->d_local_key.alloc((size_t)pr->npairs));
   if (b->lean_trace || b->level_trace) HIP_TRY(b->d_tstate.alloc(pr->npairs));
   HIP_TRY(b->d_tlen.alloc(pr->npairs));
   HIP_TRY(b->d_complete.alloc(pr->npairs));
@@ -601,7 +601,7 @@ static int enqueue_run(bialign_batch* b, uint32_t flags) {
   HIP_TRY(hipStreamWaitEvent(st, b->uploaded, 0));
   HIP_TRY(hipMemsetAsync(b->d_err.p, 0, sizeof(int32_t), st));  // the flag is per run
   if (b->free_ends()) HIP_TRY(hipMemsetAsync(b->d_span.p, 0xff, sizeof(int32_t) * b->d_span.n, st));  // spans: -1 until a kernel writes them
-  if (b->own_sweeps())  // keys: zero, below every key a sweep folds in
+  if (b->end_key())  // keys: zero, below every key a sweep folds in
     HIP_TRY(hipMemsetAsync(b->d_local_key.p, 0, sizeof(unsigned long long) * b->npairs, st));
   if (b->null_R) {  // null batch: the replicas' B codes, all of them ahead of the first sweep (timed on its own, outside fill_ms)
     HIP_TRY(hipEventRecord(b->null_evs[0], st));
@@ -622,7 +622,7 @@ static int enqueue_run(bialign_batch* b, uint32_t flags) {
     }
     HIP_TRY(hipEventRecord(b->evs[3 * c], st));
     int rc = launch_fill(b, v, first, count);
-    if (rc == BIALIGN_OK && b->own_sweeps()) rc = launch_local_finish(b, v, first, count);  // in every storage mode: scores and ends
+    if (rc == BIALIGN_OK && b->end_key()) rc = launch_local_finish(b, v, first, count);  // scores and ends (local: in every storage mode)
     if (rc) return rc;
     HIP_TRY(hipEventRecord(b->evs[3 * c + 1], st));
     if (!b->lean) {  // (with LEAN records the sweep itself wrote the scores)
@@ -749,6 +749,11 @@ int bialign_batch_get_fit_spans(const bialign_batch* b, int32_t* start_b, int32_
 int bialign_batch_get_local_spans(const bialign_batch* b, int32_t* start_a, int32_t* end_a, int32_t* start_b, int32_t* end_b) {
   int32_t* const out[] = {start_a, end_a, start_b, end_b};
   return read_spans(b, bialign::AlignMode::Local, "batch was created without BIALIGN_BATCH_LOCAL: it has no local spans", 4, out);
+}
+
+int bialign_batch_get_overlap_spans(const bialign_batch* b, int32_t* start_a, int32_t* end_a, int32_t* start_b, int32_t* end_b) {
+  int32_t* const out[] = {start_a, end_a, start_b, end_b};
+  return read_spans(b, bialign::AlignMode::Overlap, "batch was created without BIALIGN_BATCH_OVERLAP: it has no overlap spans", 4, out);
 }
 
 int bialign_batch_get_traces(const bialign_batch* b, uint8_t* trace, int64_t* trace_off, int32_t* trace_len,

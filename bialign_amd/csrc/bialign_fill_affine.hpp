@@ -122,7 +122,7 @@ __global__ void __launch_bounds__(64 * TW) fill_affine_kernel(const DeviceBatch 
   uint8_t* cb = sb + (DENSE1 ? 0 : mpad);                   // cls B,       [l-1+PADB]
 
   for (int t = threadIdx.x; t < TW * PERW; t += 64 * TW) smem[t] = SENT;
-  if (threadIdx.x < LDS_PROG_WORDS) prog_lds[threadIdx.x] = (threadIdx.x == FIT_FLOOR_WORD && !A.fit) ? SENT : 0;
+  if (threadIdx.x < LDS_PROG_WORDS) prog_lds[threadIdx.x] = prog_word_init(threadIdx.x, A.fit);
   for (int t = threadIdx.x; t < k1 * k1; t += 64 * TW) s1[t] = A.s1[t];
   for (int t = threadIdx.x; t < k2 * k2; t += 64 * TW) s2[t] = A.s2[t];
   if (!DIET)
@@ -462,6 +462,9 @@ __global__ void __launch_bounds__(64 * TW) fill_affine_kernel(const DeviceBatch 
     const bool tile_act = INTERIOR ? true : (act_row && jj >= 0 && jj <= m);
     const bool is_origin = INTERIOR ? false : (tile_act && i == 0 && jj == 0 && aa == S);
     const bool row0_diag = INTERIOR ? false : (tile_act && i == 0 && aa == S);  // lattice points (0, j, 0, j): a fit batch's paths may start there
+    // lattice points (i, 0, i, 0): an overlap batch's paths may start there too (a ghost lane replays a value that is floored
+    // already).  Never in an interior step: its phase >= Pack<S>::LO puts every lane's column at S + 1 or beyond
+    const bool col0_diag = INTERIOR ? false : (tile_act && jj == 0 && aa == S);
     const int c3M = mu1 + dd, c_Mg = mu1 + gD;
 
     // Layer stores (pyx:504: M[state][idx] = ...).  Every real lane owns a 16-byte slot in
@@ -536,6 +539,7 @@ __global__ void __launch_bounds__(64 * TW) fill_affine_kernel(const DeviceBatch 
         }
         if (bb == S) M[8] = is_origin ? 0 : M[8];  // pyx:483-485
         if (bb == S && row0_diag) M[8] = imax(M[8], prog_lds[FIT_FLOOR_WORD]);
+        if (bb == S && col0_diag) M[8] = imax(M[8], prog_lds[COL0_FLOOR_WORD]);
         if constexpr (LOCAL) {  // a path may start at any (i, j, i, j); ghost lanes replay values that are floored already
           if (bb == S) M[8] = (aa == S && act) ? imax(M[8], 0) : M[8];
         }
@@ -560,10 +564,21 @@ __global__ void __launch_bounds__(64 * TW) fill_affine_kernel(const DeviceBatch 
 #pragma unroll
           for (int q = 1; q < 9; ++q) best = imax(best, M[q]);
           if (best > fit_best) fit_best = best, fit_j = jj;
-          if (jj == m) {
-            A.scores[pid] = fit_best;
-            A.fit_span[2 * pid + 1] = fit_j;
+          if (!INTERIOR && jj == m) {  // (a boundary step: an interior step's owner lanes stay left of column m - S)
+            if (A.fit & FREE_A_ENDS) {  // overlap: row n's best goes into the pair's key, beside the other rows' end cells
+              atomicMax(A.local_key + pid, local_key_of(fit_best, n, fit_j, m));
+            } else {
+              A.scores[pid] = fit_best;
+              A.fit_span[2 * pid + 1] = fit_j;
+            }
           }
+        } else if (!INTERIOR && (A.fit & FREE_A_ENDS) && live && !ghost && aa == S && act_row && jj == m) {
+          // overlap: (i, m, i, m), i < n, is an end cell too; its row's owner folds it into the pair's key, which
+          // local_finish_kernel decodes.  (A boundary step: an interior step's owner lanes stay left of column m - S.)
+          int best = M[0];
+#pragma unroll
+          for (int q = 1; q < 9; ++q) best = imax(best, M[q]);
+          atomicMax(A.local_key + pid, local_key_of(best, i, m, m));
         }
       }
       if (PACK && INTERIOR) {

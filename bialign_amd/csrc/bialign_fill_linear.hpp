@@ -70,7 +70,7 @@ __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch 
   uint8_t* cb = sb + (DENSE1 ? 0 : mpad);
 
   for (int t = threadIdx.x; t < TW * PERW; t += 64 * TW) smem[t] = SENT;
-  if (threadIdx.x < LDS_PROG_WORDS) prog[threadIdx.x] = (threadIdx.x == FIT_FLOOR_WORD && !A.fit) ? SENT : 0;
+  if (threadIdx.x < LDS_PROG_WORDS) prog[threadIdx.x] = prog_word_init(threadIdx.x, A.fit);
   for (int t = threadIdx.x; t < k1 * k1; t += 64 * TW) s1[t] = A.s1[t];
   for (int t = threadIdx.x; t < k2 * k2; t += 64 * TW) s2[t] = A.s2[t];
   for (int t = threadIdx.x; t < n; t += 64 * TW) {
@@ -214,6 +214,8 @@ __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch 
     const bool tile_act = act_row && jj >= 0 && jj <= m;
     const bool is_origin = tile_act && i == 0 && jj == 0 && aa == S;
     const bool row0_diag = tile_act && i == 0 && aa == S;  // lattice points (0, j, 0, j): a fit batch's paths may start there
+    // lattice points (i, 0, i, 0): an overlap batch's paths may start there too (a ghost lane replays a value that is floored already)
+    const bool col0_diag = tile_act && jj == 0 && aa == S;
     const int c4 = mu1 + delta, c12 = mu1 + gD;
 
     int outv[ND];
@@ -244,6 +246,7 @@ __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch 
       int M = bad ? (act ? NEG : SENT) : tv;             // pyx:299-303
       if (bb == S) M = is_origin ? 0 : M;                // np.zeros origin (pyx:27, 464-465)
       if (bb == S && row0_diag) M = imax(M, prog[FIT_FLOOR_WORD]);
+      if (bb == S && col0_diag) M = imax(M, prog[COL0_FLOOR_WORD]);
       if constexpr (LOCAL) {  // a path may start at any (i, j, i, j); ghost lanes replay values that are floored already
         if (bb == S) M = (aa == S && act) ? imax(M, 0) : M;
       }
@@ -267,11 +270,15 @@ __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch 
       // fit: row n has one owner, the lane of (n, j, n, j), which passes over the columns in order: the best end cell
       // and the smallest column that attains it stay in its registers
       if (outv[S] > fit_best) fit_best = outv[S], fit_j = jj;
-      if (jj == m) {
+      if (jj == m && !(A.fit & FREE_A_ENDS)) {
         A.scores[pid] = fit_best;
         A.fit_span[2 * pid + 1] = fit_j;
       }
     }
+    if (LEAN && !LOCAL && (A.fit & FREE_A_ENDS) && live && !ghost && aa == S && act_row && jj == m)
+      // overlap: the end cells are (i, m), i < n, and row n.  Every row's owner folds its own at column m -- row n's its
+      // best -- into the pair's key, which local_finish_kernel decodes
+      atomicMax(A.local_key + pid, i == n ? local_key_of(fit_best, n, fit_j, m) : local_key_of(outv[S], i, m, m));
     const int pad_idx = L < W ? L : (L >= R * W ? W + (L - R * W) : 64);
     const bool pad_lane = !LEAN && pad_idx < R_::SLP - R_::SL;  // spare lanes owning a pad slot (Rec::SLP)
     const bool do_store = __builtin_amdgcn_ballot_w64(tile_act && !ghost) != 0 &&

@@ -79,6 +79,7 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
   int32_t* sentblk = smem + NW * PERW;
   volatile int32_t* prog_lds = smem + NW * PERW + SENTBLK + pw * TW;  // [16]: this team's words
   const volatile int32_t* const fit_floor = smem + NW * PERW + SENTBLK + FIT_FLOOR_WORD;  // (a constant LDS address)
+  const volatile int32_t* const col0_floor = smem + NW * PERW + SENTBLK + COL0_FLOOR_WORD;  // (likewise)
   // the ghost feed's lane offsets of a steady block (GhostFeed::issue_steady), [round][lane]; one table per workgroup
   // (packed records only: the LEAN form leaves it unused)
   int32_t* offtab = smem + NW * PERW + SENTBLK + LDS_PROG_WORDS;
@@ -92,7 +93,7 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
   uint8_t* cb = sb + mpad;                                  // cls B,       [l-1+PADB]
 
   for (int t = threadIdx.x; t < NW * PERW + SENTBLK; t += 64 * NW) smem[t] = SENT;
-  if (threadIdx.x < LDS_PROG_WORDS) smem[NW * PERW + SENTBLK + threadIdx.x] = (threadIdx.x == FIT_FLOOR_WORD && !A.fit) ? SENT : 0;
+  if (threadIdx.x < LDS_PROG_WORDS) smem[NW * PERW + SENTBLK + threadIdx.x] = prog_word_init(threadIdx.x, A.fit);
   if (!LEAN)
     for (int t = threadIdx.x; t < GF::OFFTAB_DW; t += 64 * NW) offtab[t] = (int32_t)GF::lane_offset(t >> 6, t & 63);
   for (int t = threadIdx.x; t < k1 * k1; t += 64 * NW) s1[t] = A.s1[t];
@@ -341,6 +342,9 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
     const bool tile_act = INTERIOR ? true : (act_row && jj >= 0 && jj <= m);
     const bool is_origin = INTERIOR ? false : (tile_act && i == 0 && jj == 0 && aa == S);
     const bool row0_diag = INTERIOR ? false : (tile_act && i == 0 && aa == S);  // lattice points (0, j, 0, j): a fit batch's paths may start there
+    // lattice points (i, 0, i, 0): an overlap batch's paths may start there too (a ghost lane replays a value that is floored
+    // already).  Never in an interior step: its phase >= Pack<S>::LO puts every lane's column at S + 1 or beyond
+    const bool col0_diag = INTERIOR ? false : (tile_act && jj == 0 && aa == S);
     const int c3M = mu1 + dd, c_Mg = mu1 + gD;
 
     // ---- layer stores (as fill_affine_kernel: every real lane stores every active step, spare lanes fill the pad slots)
@@ -418,6 +422,7 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
         }
         if (bb == S) M[8] = is_origin ? 0 : M[8];  // pyx:483-485
         if (bb == S && row0_diag) M[8] = imax(M[8], fit_floor[0]);
+        if (bb == S && col0_diag) M[8] = imax(M[8], col0_floor[0]);
       }
       if (!PACKED) {
 #pragma unroll
@@ -441,9 +446,20 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
             for (int q = 1; q < 9; ++q) best = imax(best, M[q]);
             if (best > fit_best) fit_best = best, fit_j = col;
             if (!INTERIOR && col == m) {
-              A.scores[pid] = fit_best;
-              A.fit_span[2 * pid + 1] = fit_j;
+              if (A.fit & FREE_A_ENDS) {  // overlap: row n's best goes into the pair's key, beside the other rows' end cells
+                atomicMax(A.local_key + pid, local_key_of(fit_best, n, fit_j, m));
+              } else {
+                A.scores[pid] = fit_best;
+                A.fit_span[2 * pid + 1] = fit_j;
+              }
             }
+          } else if (!INTERIOR && (A.fit & FREE_A_ENDS) && live && !ghost && aa == S && act_row && col == m) {
+            // overlap: (i, m, i, m), i < n, is an end cell too; its row's owner folds it into the pair's key, which
+            // local_finish_kernel decodes.  (A boundary step: an interior step's owner lanes stay left of column m - S.)
+            int best = M[0];
+#pragma unroll
+            for (int q = 1; q < 9; ++q) best = imax(best, M[q]);
+            atomicMax(A.local_key + pid, local_key_of(best, i, m, m));
           }
         }
       }

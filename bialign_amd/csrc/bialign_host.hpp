@@ -87,9 +87,9 @@ struct bialign_batch : bialign::BatchPlan {  // the plan (bialign_plan.hpp), and
   DevBuf<PairDesc> d_pairs;
   DevBuf<int32_t> d_order, d_s1, d_s2, d_layers, d_scores, d_tlen, d_complete, d_err, d_prog;
   // free ends (BatchPlan::free_ends): [npairs][4] spans, -1 ahead of every run.  Fit: the first 2 * npairs words as
-  // [npairs][2] = (start_b, end_b); local: (start_a, end_a, start_b, end_b)
+  // [npairs][2] = (start_b, end_b); local and overlap: (start_a, end_a, start_b, end_b)
   DevBuf<int32_t> d_span;
-  DevBuf<unsigned long long> d_local_key;  // local alignments: [npairs] best-end keys, zeroed ahead of every run
+  DevBuf<unsigned long long> d_local_key;  // BatchPlan::end_key: [npairs] best-end keys, zeroed ahead of every run
   int last_team = 1;  // waves per pair of the last fill launch (negative: cross-CU team)
   // Cross-CU teams need every workgroup of the launch resident at once.  The grid is sized from the
   // occupancy the runtime reports for the actual kernel (xcu_resident, cached per LEAN flavour) and
@@ -174,7 +174,10 @@ struct bialign_batch : bialign::BatchPlan {  // the plan (bialign_plan.hpp), and
     v.wide_s = S;
     v.prio_mode = getenv("BIALIGN_PRIO") ? atoi(getenv("BIALIGN_PRIO")) : 1;
     v.spin_limit = 1 << 20;  // waves of one workgroup are co-resident by construction: a timeout there is a bug
-    v.fit = mode == bialign::AlignMode::Fit;
+    // whose end gaps are free in the sweeps of the global recurrence: B's (fit), both molecules' (overlap)
+    v.fit = mode == bialign::AlignMode::Fit       ? bialign::FREE_B_ENDS
+            : mode == bialign::AlignMode::Overlap ? bialign::FREE_B_ENDS | bialign::FREE_A_ENDS
+                                                  : 0;
     v.local = mode == bialign::AlignMode::Local;
     v.fit_span = v.local_span = d_span.p;
     v.local_key = d_local_key.p;
@@ -506,7 +509,7 @@ template <int S>
 size_t trace_fast_lds(const bialign_batch* b, int first, int count, int* tbuf) {
   const char* sw = getenv("BIALIGN_TRACE_FAST");  // "0": tests / A-B, the generic kernel only
   if ((sw && atoi(sw) == 0) || b->dense || b->dense1 || b->wide || b->lean) return 0;
-  if (b->free_ends()) return 0;  // fit and local alignments take the generic walk: the short-chain kernel has neither the end rules nor the stop rules
+  if (b->free_ends()) return 0;  // fit, local and overlap alignments take the generic walk: the short-chain kernel has neither the end rules nor the stop rules
   int cap = 0;
   for (int t = first; t < first + count; ++t) {
     const PairDesc& d = b->pairs[b->order[t]];

@@ -21,7 +21,7 @@
 namespace bialign {
 
 int fail(int code, const char* fmt, ...);  // records the message bialign_last_error() returns (bialign_capi.hip)
-enum class AlignMode { Global, Fit, Local };
+enum class AlignMode { Global, Fit, Local, Overlap };
 
 // The host's decisions about one batch.  bialign_batch (bialign_host.hpp) derives from it and adds what lives on the
 // device: buffers, events, run state, the engine.
@@ -74,15 +74,22 @@ struct BatchPlan {
   int wide_seg = 0;
   int resw_k = 1;           // strips re-swept and walked per round (more when the batch has few pairs)
   // The alignment mode, one per batch (check_inputs).  Fit (BIALIGN_BATCH_FIT): free end gaps in B.  Local (BIALIGN_BATCH_LOCAL):
-  // free ends in both molecules.  What the host does differently for a mode it reads from the two properties below.
+  // free ends in both molecules.  Overlap (BIALIGN_BATCH_OVERLAP): the global alignment whose end gaps are free in both
+  // molecules.  What the host does differently for a mode it reads from the three properties below.
   AlignMode mode = AlignMode::Global;
-  const char* mode_name() const { return mode == AlignMode::Fit ? "FIT" : "LOCAL"; }  // (for messages about a non-global mode)
+  const char* mode_name() const {  // (for messages about a non-global mode)
+    return mode == AlignMode::Fit ? "FIT" : mode == AlignMode::Local ? "LOCAL" : "OVERLAP";
+  }
   // free ends: tiled bands, full storage or SCORE_ONLY; spans beside the scores; the generic tracebacks only (host:
   // trace_fast_lds); never the storage ladder's LEAN_TRACE rung (plan_storage: BIALIGN_E_NOMEM)
   bool free_ends() const { return mode != AlignMode::Global; }
   // sweeps of its own (launch_fill_*_local, best-end keys behind them): no packed records, slim kernel or cross-CU team
   // (decide_pack, slim_available, team_shape); beta <= 0 in the affine recurrence
   bool own_sweeps() const { return mode == AlignMode::Local; }
+  // its sweeps raise the pair's best-end key (bialign_local.hpp), which local_finish_kernel decodes behind them: local
+  // alignments always, overlap alignments where no traceback prologue scans the end cells (SCORE_ONLY).  It sizes and
+  // zeroes the key buffer, launches the finish kernel and bounds n + m (the key's position is 32 bits wide)
+  bool end_key() const { return mode == AlignMode::Local || (mode == AlignMode::Overlap && lean); }
 };
 
 // What the host needs of the kernels' compile-time geometry, for a run-time (max_shift, recurrence): read from the types
@@ -477,17 +484,21 @@ inline int check_inputs(const bialign_params* prm, const bialign_scoring* sc, co
   b.lean = b.lean_trace || (prm->flags & BIALIGN_BATCH_SCORE_ONLY) != 0;
   b.wide = prm->max_shift > BIALIGN_MAX_SHIFT_TILED;  // bialign_wide.hpp: anti-diagonal path, all layers in HBM
   constexpr uint32_t KNOWN_FLAGS =
-      BIALIGN_BATCH_SCORE_ONLY | BIALIGN_BATCH_LEAN_TRACE | BIALIGN_BATCH_LEVEL_TRACE | BIALIGN_BATCH_FIT | BIALIGN_BATCH_LOCAL;
+      BIALIGN_BATCH_SCORE_ONLY | BIALIGN_BATCH_LEAN_TRACE | BIALIGN_BATCH_LEVEL_TRACE | BIALIGN_BATCH_FIT | BIALIGN_BATCH_LOCAL |
+      BIALIGN_BATCH_OVERLAP;
   if (prm->flags & ~KNOWN_FLAGS) return fail(BIALIGN_E_INVALID, "unknown bits 0x%x in bialign_params.flags", prm->flags & ~KNOWN_FLAGS);
-  // the mode, decoded once.  Both bits are refused behind the free-ends refusals, which then name FIT: the order in which
-  // callers meet the refusals is part of the interface (tests/mode_expected.txt)
+  // the mode, decoded once.  Two bits at once are refused behind the free-ends refusals, which then name the first of FIT,
+  // LOCAL, OVERLAP that is set: the order in which callers meet the refusals is part of the interface
+  // (tests/mode_expected.txt)
   const bool fit = (prm->flags & BIALIGN_BATCH_FIT) != 0, local = (prm->flags & BIALIGN_BATCH_LOCAL) != 0;
-  b.mode = fit ? AlignMode::Fit : local ? AlignMode::Local : AlignMode::Global;
+  const bool overlap = (prm->flags & BIALIGN_BATCH_OVERLAP) != 0;
+  b.mode = fit ? AlignMode::Fit : local ? AlignMode::Local : overlap ? AlignMode::Overlap : AlignMode::Global;
   if (b.free_ends() && (prm->flags & (BIALIGN_BATCH_LEAN_TRACE | BIALIGN_BATCH_LEVEL_TRACE)))
     return fail(BIALIGN_E_UNSUPPORTED, "%s exists in full storage and in SCORE_ONLY: not with LEAN_TRACE or LEVEL_TRACE", b.mode_name());
   if (b.free_ends() && b.wide)
     return fail(BIALIGN_E_UNSUPPORTED, "%s exists for max_shift <= %d only (the tiled sweeps)", b.mode_name(), BIALIGN_MAX_SHIFT_TILED);
   if (fit && local) return fail(BIALIGN_E_INVALID, "LOCAL and FIT exclude each other");
+  if (overlap && (fit || local)) return fail(BIALIGN_E_INVALID, "OVERLAP and %s exclude each other", b.mode_name());
   if (b.mode == AlignMode::Local && b.affine && prm->gap_opening_cost > 0)
     return fail(BIALIGN_E_UNSUPPORTED, "LOCAL exists for gap_opening_cost <= 0 only in the affine recurrence (no general-beta sweep)");
   if (prm->flags & BIALIGN_BATCH_LEVEL_TRACE) {
@@ -592,8 +603,10 @@ inline int plan_pairs(const bialign_pairs* pr, const NullPlan* nul, int64_t colm
     if ((2 * ((int64_t)n + m) + 8) * colmax >= (1 << 28))
       return fail(BIALIGN_E_RANGE, "pair %d: scores may leave the int32 safety window (n+m=%d, column bound %lld)", shown(p),
                   n + m, (long long)colmax);
-    if (b.mode == AlignMode::Local && n + m >= LOCAL_MAX_NM)  // the end's position in the pair's key is 32 bits (bialign_local.hpp)
-      return fail(BIALIGN_E_UNSUPPORTED, "pair %d: LOCAL takes n + m < %d (n+m=%d)", shown(p), LOCAL_MAX_NM, n + m);
+    // the end's position in the pair's key is 32 bits (bialign_local.hpp); an overlap batch is held to the bound in full
+    // storage too, so that what the mode accepts does not depend on the storage
+    if ((b.end_key() || b.mode == AlignMode::Overlap) && n + m >= LOCAL_MAX_NM)
+      return fail(BIALIGN_E_UNSUPPORTED, "pair %d: %s takes n + m < %d (n+m=%d)", shown(p), b.mode_name(), LOCAL_MAX_NM, n + m);
     if (nul) {  // the reduction's int64 sum of squares: replicas * bound^2 with the window's bound on |score| (< 2^28)
       const int64_t bound = (2 * ((int64_t)n + m) + 8) * colmax;
       if (bound > 0 && bound * bound > INT64_MAX / nul->replicas)
@@ -809,7 +822,7 @@ inline int expand_null_pairs(const bialign_params* prm, const bialign_pairs* pr,
   if (!mu1_off.empty()) vp.mu1_off = mu1_off.data();
   if (!mu2_off.empty()) vp.mu2_off = mu2_off.data();
   plan.vprm = *prm;
-  // SCORE_ONLY is forced (the caller refused LEAN_TRACE / LEVEL_TRACE); FIT and LOCAL pass through -- the replicas are
+  // SCORE_ONLY is forced (the caller refused LEAN_TRACE / LEVEL_TRACE); FIT, LOCAL and OVERLAP pass through -- the replicas are
   // scored in the observed batch's mode -- and so do unknown bits, for check_inputs to refuse
   plan.vprm.flags = BIALIGN_BATCH_SCORE_ONLY | (prm->flags & ~(uint32_t)(BIALIGN_BATCH_LEAN_TRACE | BIALIGN_BATCH_LEVEL_TRACE));
   return BIALIGN_OK;

@@ -61,19 +61,30 @@ __device__ __forceinline__ int wave_min64(int v) {  // min over the wave's 64 la
   return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
              min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
 }
-// Fit alignments (DeviceBatch::fit), end rule of the full-storage tracebacks: the wave's lanes stride over the end cells
-// (n, j, n, j), j = 0..m, whose value end_cell(j) reads through the kernel's own cell addressing, and reduce to the best
-// one and the smallest column that attains it.
+// Fit and overlap alignments (DeviceBatch::fit), end rule of the full-storage tracebacks.  The end cells in position
+// order: x < n -> (x, m), else (n, x - n), for x = 0 .. n + m; that is the order by (i, j), and the order of local_key_of.
+// An overlap batch takes all of them, a fit batch those of row n (x >= n).  The wave's lanes stride over the positions,
+// read each cell's value through the kernel's own cell addressing (end_cell(i, j)), and reduce to the best one and the
+// smallest position that attains it.  Column m and row n are scanned by a loop each, so that a fit batch runs the loop
+// over row n it always ran (its row is loop-invariant); a lane meets its positions in rising order in both.
 template <typename EndCell>
-__device__ __forceinline__ void fit_end_scan(int m, int lane, EndCell&& end_cell, int* best, int* end_b) {
+__device__ __forceinline__ void free_end_scan(int n, int m, bool a_ends, int lane, EndCell&& end_cell, int* end_a, int* end_b) {
   constexpr int BIG = 0x7fffffff;
-  int bv = -BIG, bj = 0;
-  for (int x = lane; x <= m; x += 64) {
-    const int e = end_cell(x);
-    if (e > bv) bv = e, bj = x;
+  int bv = -BIG, bx = 0;
+  if (a_ends) {
+    for (int x = lane; x < n; x += 64) {
+      const int e = end_cell(x, m);
+      if (e > bv) bv = e, bx = x;
+    }
   }
-  *best = -wave_min64(-bv);
-  *end_b = wave_min64(bv == *best ? bj : BIG);
+  for (int j = lane; j <= m; j += 64) {
+    const int e = end_cell(n, j);
+    if (e > bv) bv = e, bx = n + j;
+  }
+  const int best = -wave_min64(-bv);
+  const int x = wave_min64(bv == best ? bx : BIG);
+  *end_a = x < n ? x : n;
+  *end_b = x < n ? m : x - n;
 }
 
 //   STRIP (lean traceback): the walk continues from the pair's
@@ -135,23 +146,29 @@ __global__ void __launch_bounds__(64) traceback_affine_kernel(const DeviceBatch 
   int st = 0, cur = 0;
   constexpr bool FIT_FORM = !STRIP && !WIDE && !LEVEL;  // fit alignments: the tiled full-storage forms
   const bool fit = FIT_FORM && A.fit;
+  const bool ovl = fit && (A.fit & FREE_A_ENDS);  // overlap alignments: A's end gaps are free as well
   const bool local = FIT_FORM && A.local;  // local alignments: the same forms
   if (!(STRIP || LEVEL) || !ts.started) {
     if (local) {  // the walk starts at the end local_finish_kernel decoded: (end_a, end_b, end_a, end_b)
       i = k = A.local_span[4 * (int64_t)pid + 1];
       j = l = A.local_span[4 * (int64_t)pid + 3];
     }
-    if (fit) {  // the walk starts at the best end cell (n, end_b, n, end_b)
-      int fbest, fend;
-      fit_end_scan(m, c, [&](int x) {
-        int e = cell(n, x, SR, SR, 0);
-        for (int q = 1; q < 9; ++q) e = max(e, cell(n, x, SR, SR, q));
+    if (fit) {  // the walk starts at the best end cell: (n, end_b, n, end_b), or (overlap) also (end_a, m, end_a, m)
+      int ea, eb;
+      free_end_scan(n, m, ovl, c, [&](int pi, int pj) {
+        int e = cell(pi, pj, SR, SR, 0);
+        for (int q = 1; q < 9; ++q) e = max(e, cell(pi, pj, SR, SR, q));
         return e;
-      }, &fbest, &fend);
-      j = l = fend;
-      if (c == 0) {
+      }, &ea, &eb);
+      i = k = ea;
+      j = l = eb;
+      if (c == 0 && !ovl) {
         A.fit_span[2 * pid] = -1;
-        A.fit_span[2 * pid + 1] = fend;
+        A.fit_span[2 * pid + 1] = eb;
+      }
+      if (c == 0 && ovl) {  // (start_a, end_a, start_b, end_b), as local_finish_kernel leaves them
+        int32_t* span = A.local_span + 4 * (int64_t)pid;
+        span[0] = -1, span[1] = ea, span[2] = -1, span[3] = eb;
       }
     }
     // pyx:573-582: best end layer, first one with the least shift
@@ -177,6 +194,7 @@ __global__ void __launch_bounds__(64) traceback_affine_kernel(const DeviceBatch 
   while (true) {
     if (i == 0 && j == 0 && k == 0 && l == 0 && st == 8) { complete = 1; break; }
     if (fit && i == 0 && k == 0 && j == l && st == 8 && cur == 0) { complete = 1; break; }  // fit: a free start, start_b = j
+    if (ovl && j == 0 && l == 0 && i == k && st == 8 && cur == 0) { complete = 1; break; }  // overlap: and on column 0, start_a = i
     if (local && i == k && j == l && st == 8 && cur == 0) { complete = 1; break; }  // local: a free start, (start_a, start_b) = (i, j)
     if (STRIP && i < Qlo * RR) { finished = false; break; }  // above the re-swept strips: next round
     if (LEVEL && seg > 0 && i + j + k + l < seg_base + WIDE_SEG_OVERLAP) { finished = false; break; }  // a candidate may lie below the scratch
@@ -242,7 +260,8 @@ __global__ void __launch_bounds__(64) traceback_affine_kernel(const DeviceBatch 
   if (c == 0) {
     A.trace_len[pid] = len;
     A.complete[pid] = complete;
-    if (fit && complete) A.fit_span[2 * pid] = j;
+    if (fit && !ovl && complete) A.fit_span[2 * pid] = j;
+    if (ovl && complete) A.local_span[4 * (int64_t)pid] = i, A.local_span[4 * (int64_t)pid + 2] = j;
     if (local && complete) A.local_span[4 * (int64_t)pid] = i, A.local_span[4 * (int64_t)pid + 2] = j;
     if (STRIP || LEVEL) {
       ts.done = 1;
@@ -293,18 +312,22 @@ __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch 
   };
   constexpr bool FIT_FORM = !STRIP && !WIDE && !LEVEL;  // fit alignments: the tiled full-storage forms
   const bool fit = FIT_FORM && A.fit;
+  const bool ovl = fit && (A.fit & FREE_A_ENDS);  // overlap alignments: A's end gaps are free as well
   const bool local = FIT_FORM && A.local;  // local alignments: the same forms
   int iend = n, jend = m;
   if (local) {  // the walk starts at the end local_finish_kernel decoded: (end_a, end_b, end_a, end_b)
     iend = A.local_span[4 * (int64_t)pid + 1];
     jend = A.local_span[4 * (int64_t)pid + 3];
   }
-  if (fit) {  // the walk starts at the best end cell (n, end_b, n, end_b)
-    int fbest;
-    fit_end_scan(m, c, [&](int x) { return cell(n, x, SR, SR); }, &fbest, &jend);
-    if (c == 0) {
+  if (fit) {  // the walk starts at the best end cell: (n, end_b, n, end_b), or (overlap) also (end_a, m, end_a, m)
+    free_end_scan(n, m, ovl, c, [&](int pi, int pj) { return cell(pi, pj, SR, SR); }, &iend, &jend);
+    if (c == 0 && !ovl) {
       A.fit_span[2 * pid] = -1;
       A.fit_span[2 * pid + 1] = jend;
+    }
+    if (c == 0 && ovl) {  // (start_a, end_a, start_b, end_b), as local_finish_kernel leaves them
+      int32_t* span = A.local_span + 4 * (int64_t)pid;
+      span[0] = -1, span[1] = iend, span[2] = -1, span[3] = jend;
     }
   }
   int cur = (CONT && ts.started) ? ts.cur : cell(iend, jend, SR, SR);
@@ -332,6 +355,7 @@ __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch 
   bool finished = true;
   while (true) {
     if (fit && i == 0 && k == 0 && j == l && cur == 0) break;  // fit: a free start, start_b = j
+    if (ovl && j == 0 && l == 0 && i == k && cur == 0) break;  // overlap: and on column 0, start_a = i
     if (local && i == k && j == l && cur == 0) break;          // local: a free start, (start_a, start_b) = (i, j)
     if (STRIP && i < Qlo * RR) { finished = false; break; }
     if (LEVEL && seg > 0 && i + j + k + l < seg_base + WIDE_SEG_OVERLAP) { finished = false; break; }
@@ -376,7 +400,8 @@ __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch 
   if (c == 0) {
     A.trace_len[pid] = len;
     A.complete[pid] = 1;
-    if (fit) A.fit_span[2 * pid] = j;
+    if (fit && !ovl) A.fit_span[2 * pid] = j;
+    if (ovl) A.local_span[4 * (int64_t)pid] = i, A.local_span[4 * (int64_t)pid + 2] = j;
     if (local) A.local_span[4 * (int64_t)pid] = i, A.local_span[4 * (int64_t)pid + 2] = j;
     if (CONT) {
       ts.done = 1;

@@ -14,6 +14,17 @@ constexpr int LDS_PROG_WORDS = 16;                  // in-workgroup teams: progr
 // lies.  The sweeps' prologue writes it; boundary steps read it back where row 0 is computed, so the mode costs the
 // interior loops neither a register nor an instruction.
 constexpr int FIT_FLOOR_WORD = LDS_PROG_WORDS - 1;
+// The one before it holds the same floor for the lattice points (i, 0, i, 0): 0 in an overlap batch (DeviceBatch::fit bit
+// FREE_A_ENDS), where FIT_FLOOR_WORD is 0 as well, else the sentinel.
+constexpr int COL0_FLOOR_WORD = LDS_PROG_WORDS - 2;
+// DeviceBatch::fit: whose end gaps are free in the sweeps that serve the global recurrence.  FIT sets FREE_B_ENDS, OVERLAP both.
+constexpr int32_t FREE_B_ENDS = 1, FREE_A_ENDS = 2;
+// the prologue's value of progress word t (threads 0 .. LDS_PROG_WORDS-1): the two floor words, zero for the teams' words
+__device__ __forceinline__ int32_t prog_word_init(int t, int32_t fit) {
+  if (t == FIT_FLOOR_WORD) return (fit & FREE_B_ENDS) ? 0 : SENT;
+  if (t == COL0_FLOOR_WORD) return (fit & FREE_A_ENDS) ? 0 : SENT;
+  return 0;
+}
 constexpr int XCH_ROWS = 12;                        // affine sweeps: exchange rows per lattice point that go through LDS
 // Bytes one array of a molecule's codes takes in LDS: whole dwords, `guard` bytes around (B's codes in the sweeps: Geo<S>::PADB)
 __host__ __device__ constexpr int code_pad(int len, int guard = 0) { return (len + 2 * guard + 3) & ~3; }
@@ -77,6 +88,9 @@ struct DeviceBatch {
   // in their prologue (FIT_FLOOR_WORD, applied in boundary steps where is_origin is tested) and, LEAN forms, where the
   // end cell's score is written; the generic tracebacks in their prologue and stop test.
   // fit_span: [npairs][2] = (start_b, end_b), -1 until written.
+  // Overlap alignments (BIALIGN_BATCH_OVERLAP) set FREE_A_ENDS beside FREE_B_ENDS: the same sweeps floor
+  // the points (i, 0, i, 0) too (COL0_FLOOR_WORD), their LEAN forms fold every row's end cell on column m, and row n's best,
+  // into local_key; the generic tracebacks scan both end lines.  Spans: local_span's layout.
   int32_t fit;
   // Local alignments (BIALIGN_BATCH_LOCAL, DESIGN.md "Local alignments"): free ends in both molecules.  Wave-uniform; the
   // sweeps built for it (template parameter LOCAL) do not read it, the generic tracebacks do, beside `fit`.  (It fills

@@ -72,10 +72,12 @@ def gather_scores(local_scores, npairs_total, costs=None):
     return assemble_scores([p.cpu().numpy() for p in parts], npairs_total, costs)
 
 
-def align_sharded(pairs, params, device=None, hbm_budget_bytes=0, balance=True):
+def align_sharded(pairs, params, device=None, hbm_budget_bytes=0, balance=True, overlap=False):
     """Align this rank's shard of ``pairs`` on its GPU; every rank returns the scores of ALL
     pairs (gathered) and the traces of its own shard.  ``balance``: cut the shards by lattice
-    cells ("cost-balance by n*m when lengths vary") instead of pair count."""
+    cells ("cost-balance by n*m when lengths vary") instead of pair count.
+    ``overlap``: overlap alignments (engine.Batch); a pair's entry is then ``(trace, complete, span)`` with
+    ``span = (start_a, end_a, start_b, end_b)``."""
     import torch.distributed as dist
     from .batch import make_batch, pair_cost
     from .engine import default_engine
@@ -89,10 +91,13 @@ def align_sharded(pairs, params, device=None, hbm_budget_bytes=0, balance=True):
     local_scores, local = np.zeros(0, dtype=np.int32), {}
     if len(mine):  # a rank may own nothing (fewer pairs than ranks, one giant pair)
         batch = make_batch([pairs[p] for p in mine], params, engine=default_engine(device),
-                           hbm_budget_bytes=hbm_budget_bytes)
+                           hbm_budget_bytes=hbm_budget_bytes, overlap=overlap)
         batch.run()
         traces, complete = batch.traces()
         local_scores = batch.scores()
         local = {p: (traces[t], bool(complete[t])) for t, p in enumerate(mine)}
+        if overlap:
+            spans = batch.overlap_spans()
+            local = {p: local[p] + (tuple(int(x[t]) for x in spans),) for t, p in enumerate(mine)}
         batch.close()
     return gather_scores(local_scores, len(pairs), costs), local

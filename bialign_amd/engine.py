@@ -110,12 +110,17 @@ class Batch:
     alignment, ``local_spans()`` the two substrings.  Bands up to ``_lib.MAX_SHIFT_TILED``, ``gap_opening_cost <= 0``
     in the affine recurrence, full storage or ``score_only`` (and so null batches); not with ``fit``, ``lean_trace``
     or ``level_trace``.
+    ``overlap``: overlap alignments (BIALIGN_BATCH_OVERLAP): the global alignment whose end gaps cost nothing in either
+    molecule.  ``scores()`` is the best global score of A[i0:i1] against B[j0:j1] over the windows that start at the
+    beginning of A or of B and end at the end of A or of B (>= 0), ``traces()`` that alignment, ``overlap_spans()`` the
+    window.  Bands up to ``_lib.MAX_SHIFT_TILED``, full storage or ``score_only`` (and so null batches); not with
+    ``fit``, ``local``, ``lean_trace`` or ``level_trace``.
     """
 
     def __init__(self, engine, mols_a, mols_b, s1, s2, gap_opening_cost, gap_cost, shift_cost,
                  max_shift, hbm_budget_bytes=0, recurrence=0, mu2_dense=None, score_only=False,
                  lean_trace=False, mu1_dense=None, mu2_features=None, level_trace=False, null=None, null_dense=None,
-                 fit=False, local=False):
+                 fit=False, local=False, overlap=False):
         null_kind = "dense" if null_dense is not None else ("lookup" if null is not None else None)
         if null_dense is not None:
             if mu1_dense is None and mu2_dense is None:
@@ -183,7 +188,7 @@ class Batch:
                           int(recurrence), (_lib.BATCH_SCORE_ONLY if score_only else 0) |
                           (_lib.BATCH_LEAN_TRACE if lean_trace else 0) |
                           (_lib.BATCH_LEVEL_TRACE if level_trace else 0) | (_lib.BATCH_FIT if fit else 0) |
-                          (_lib.BATCH_LOCAL if local else 0))
+                          (_lib.BATCH_LOCAL if local else 0) | (_lib.BATCH_OVERLAP if overlap else 0))
         sc = _lib.Scoring(s1.shape[0], _ptr(s1, ctypes.c_int32), s2.shape[0], _ptr(s2, ctypes.c_int32))
         pr = _lib.Pairs(self.npairs, _ptr(self.len_a, ctypes.c_int32), _ptr(self.len_b, ctypes.c_int32),
                         _ptr(off_a, ctypes.c_int64), _ptr(off_b, ctypes.c_int64),
@@ -194,6 +199,7 @@ class Batch:
         self.replicas = None
         self.fit = bool(fit)
         self.local = bool(local)
+        self.overlap = bool(overlap)
         self._null_forms = (mu1_flat is not None, mu2_flat is not None) if null_dense is not None else None
         args = [engine._h, ctypes.byref(prm), ctypes.byref(sc), ctypes.byref(pr)]
         if feat is not None:
@@ -394,6 +400,14 @@ class Batch:
         are -1."""
         out = [np.empty(self.npairs, dtype=np.int32) for _ in range(4)]
         check(lib.bialign_batch_get_local_spans(self._h, *[_ptr(x, ctypes.c_int32) for x in out]))
+        return tuple(out)
+
+    def overlap_spans(self):
+        """Overlap batch: ``(start_a, end_a, start_b, end_b)`` as int32 arrays -- pair p's alignment is that of
+        ``A[start_a[p]:end_a[p]]`` with ``B[start_b[p]:end_b[p]]``.  After a score-only or fill-only run the starts
+        are -1."""
+        out = [np.empty(self.npairs, dtype=np.int32) for _ in range(4)]
+        check(lib.bialign_batch_get_overlap_spans(self._h, *[_ptr(x, ctypes.c_int32) for x in out]))
         return tuple(out)
 
     def dump_layers(self, pair):

@@ -139,10 +139,12 @@ def check_null(null):
     return int(replicas), int(seed)
 
 
-def _check_mode(fit, local):
-    """``fit`` and ``local`` name two alignment modes: one batch has one of them."""
+def _check_mode(fit, local, overlap=False):
+    """``fit``, ``local`` and ``overlap`` name three alignment modes: one batch has one of them."""
     if fit and local:
         raise ValueError("fit= and local= exclude each other")
+    if overlap and (fit or local):
+        raise ValueError("overlap= excludes fit= and local=")
 
 
 def _check_pairs(pairs, replicas, seed):
@@ -155,19 +157,20 @@ def _check_pairs(pairs, replicas, seed):
     return pairs, replicas, seed
 
 
-def null_batch(pairs, params, replicas, seed=0, engine=None, hbm_budget_bytes=0, recurrence=0, fit=False, local=False):
+def null_batch(pairs, params, replicas, seed=0, engine=None, hbm_budget_bytes=0, recurrence=0, fit=False, local=False, overlap=False):
     """A null batch of ``pairs`` (``(seqA, seqB, strA, strB)`` each, as ``batch.make_batch`` takes them): every pair
     against ``replicas`` shuffles of its B.  -> ``engine.Batch``; ``run()`` it, then ``null_scores()`` /
     ``null_stats()``.  ``fit``: the replicas are scored as fit alignments (engine.Batch) -- the mode the observed
-    scores they are compared with must have been scored in.  ``local``: likewise, as local alignments; excludes ``fit``."""
-    _check_mode(fit, local)
+    scores they are compared with must have been scored in.  ``local``: likewise, as local alignments; excludes ``fit``.
+    ``overlap``: likewise, as overlap alignments; excludes both."""
+    _check_mode(fit, local, overlap)
     pairs, replicas, seed = _check_pairs(pairs, replicas, seed)
     from .batch import encode_flat
     from .engine import Batch, default_engine  # loads the HIP library (no CPU fallback)
     model, fb = encode_flat(pairs, params)
     return Batch(engine or default_engine(), fb, None, model.s1, model.s2,
                  params["gap_opening_cost"], params["gap_cost"], params["shift_cost"], params["max_shift"],
-                 hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence, null=(replicas, seed), fit=fit, local=local)
+                 hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence, null=(replicas, seed), fit=fit, local=local, overlap=overlap)
 
 
 def zscores_from_stats(score, stats):
@@ -211,14 +214,14 @@ def _zscores(npairs, observed, score_batch, null_batch):
     return zscores_from_stats(observed, _run_and_close(null_batch(), lambda nb: nb.null_stats(observed)))
 
 
-def zscores(pairs, params, replicas=100, seed=0, observed=None, engine=None, hbm_budget_bytes=0, recurrence=0, fit=False, local=False):
+def zscores(pairs, params, replicas=100, seed=0, observed=None, engine=None, hbm_budget_bytes=0, recurrence=0, fit=False, local=False, overlap=False):
     """z-scores of the pairs' optimal scores against ``replicas`` shuffles of each pair's B (``zscores_from_stats``).
     ``observed``: the pairs' real scores if the caller has them; else a score-only batch computes them first.
     ``fit``: fit alignments (engine.Batch) -- observed scores and replicas alike (``observed``, if given, must be fit
-    scores then).  ``local``: likewise, local alignments; excludes ``fit``."""
-    _check_mode(fit, local)
+    scores then).  ``local``: likewise, local alignments; excludes ``fit``.  ``overlap``: likewise, overlap alignments; excludes both."""
+    _check_mode(fit, local, overlap)
     pairs, replicas, seed = _check_pairs(pairs, replicas, seed)
-    common = dict(engine=engine, hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence, fit=fit, local=local)
+    common = dict(engine=engine, hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence, fit=fit, local=local, overlap=overlap)
 
     def score_batch():
         from .batch import make_batch
@@ -246,26 +249,26 @@ def _check_feature_args(molecules, pair_index, replicas, seed):
 
 
 def null_feature_batch(molecules, pair_index, params, replicas, seed=0, engine=None, hbm_budget_bytes=0, recurrence=0,
-                       fit=False, local=False):
+                       fit=False, local=False, overlap=False):
     """A FEATURE-form null batch: ``molecules`` (``(seq, (up, down, unp))`` each) and ``pair_index`` as
     ``batch.make_feature_batch`` takes them, every pair against ``replicas`` shuffles of its B -- letters and
     features, made on the GPU from the one uploaded copy of every molecule.  -> ``engine.Batch``; ``run()`` it, then
-    ``null_scores()`` / ``null_stats()``.  ``fit``, ``local``: as for ``null_batch``."""
-    _check_mode(fit, local)
+    ``null_scores()`` / ``null_stats()``.  ``fit``, ``local``, ``overlap``: as for ``null_batch``."""
+    _check_mode(fit, local, overlap)
     molecules, pair_index, replicas, seed = _check_feature_args(molecules, pair_index, replicas, seed)
     from .batch import make_feature_batch
     return make_feature_batch(molecules, pair_index, params, engine=engine, hbm_budget_bytes=hbm_budget_bytes,
-                              recurrence=recurrence, score_only=True, null=(replicas, seed), fit=fit, local=local)
+                              recurrence=recurrence, score_only=True, null=(replicas, seed), fit=fit, local=local, overlap=overlap)
 
 
 def zscores_features(molecules, pair_index, params, replicas=100, seed=0, observed=None, engine=None, hbm_budget_bytes=0,
-                     recurrence=0, fit=False, local=False):
+                     recurrence=0, fit=False, local=False, overlap=False):
     """``zscores`` for RNA molecules with real-valued structure features: z-scores of the pairs' optimal scores
     against ``replicas`` shuffles of each pair's B (``zscores_from_stats``).  ``observed``: the pairs' real scores if
-    the caller has them; else ``make_feature_batch(score_only=True)`` computes them first.  ``fit``, ``local``: as for ``zscores``."""
-    _check_mode(fit, local)
+    the caller has them; else ``make_feature_batch(score_only=True)`` computes them first.  ``fit``, ``local``, ``overlap``: as for ``zscores``."""
+    _check_mode(fit, local, overlap)
     molecules, pair_index, replicas, seed = _check_feature_args(molecules, pair_index, replicas, seed)
-    common = dict(engine=engine, hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence, fit=fit, local=local)
+    common = dict(engine=engine, hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence, fit=fit, local=local, overlap=overlap)
 
     def score_batch():
         from .batch import make_feature_batch
@@ -275,28 +278,28 @@ def zscores_features(molecules, pair_index, params, replicas=100, seed=0, observ
 
 
 def null_dense_batch(pairs, params, replicas, seed=0, mu1_dense=None, mu2_dense=None, engine=None, hbm_budget_bytes=0,
-                     recurrence=0, fit=False, local=False):
+                     recurrence=0, fit=False, local=False, overlap=False):
     """A DENSE-form null batch: ``pairs`` and their tables as ``batch.make_batch`` takes them (one integer table of shape
     (len A, len B) per pair in ``mu1_dense`` and / or ``mu2_dense``), every pair against ``replicas`` shuffles of its B --
     the tables' columns, and the codes of a form left in LOOKUP form, permuted on the GPU from the one uploaded copy.
-    -> ``engine.Batch``; ``run()`` it, then ``null_scores()`` / ``null_stats()``.  ``fit``, ``local``: as for ``null_batch``."""
-    _check_mode(fit, local)
+    -> ``engine.Batch``; ``run()`` it, then ``null_scores()`` / ``null_stats()``.  ``fit``, ``local``, ``overlap``: as for ``null_batch``."""
+    _check_mode(fit, local, overlap)
     pairs, replicas, seed = check_dense_args(pairs, (replicas, seed), mu1_dense, mu2_dense)
     from .batch import make_batch
     return make_batch(pairs, params, engine=engine, hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence,
-                      score_only=True, mu1_dense=mu1_dense, mu2_dense=mu2_dense, null_dense=(replicas, seed), fit=fit, local=local)
+                      score_only=True, mu1_dense=mu1_dense, mu2_dense=mu2_dense, null_dense=(replicas, seed), fit=fit, local=local, overlap=overlap)
 
 
 def zscores_dense(pairs, params, replicas=100, seed=0, mu1_dense=None, mu2_dense=None, observed=None, engine=None,
-                  hbm_budget_bytes=0, recurrence=0, fit=False, local=False):
+                  hbm_budget_bytes=0, recurrence=0, fit=False, local=False, overlap=False):
     """``zscores`` for pairs scored through dense tables (a PSSM as ``mu1_dense``, structure scores as ``mu2_dense``):
     z-scores of the pairs' optimal scores against ``replicas`` shuffles of each pair's B (``zscores_from_stats``).
     ``observed``: the pairs' real scores if the caller has them; else ``make_batch(score_only=True)`` with the same
-    tables computes them first.  ``fit``, ``local``: as for ``zscores``."""
-    _check_mode(fit, local)
+    tables computes them first.  ``fit``, ``local``, ``overlap``: as for ``zscores``."""
+    _check_mode(fit, local, overlap)
     pairs, replicas, seed = check_dense_args(pairs, (replicas, seed), mu1_dense, mu2_dense)
     common = dict(mu1_dense=mu1_dense, mu2_dense=mu2_dense, engine=engine, hbm_budget_bytes=hbm_budget_bytes,
-                  recurrence=recurrence, fit=fit, local=local)
+                  recurrence=recurrence, fit=fit, local=local, overlap=overlap)
 
     def score_batch():
         from .batch import make_batch

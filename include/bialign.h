@@ -147,6 +147,35 @@ extern "C" {
  * bialign_batch_get_local_spans the spans.  Scores and ends are there after every run, SCORE_ONLY and
  * BIALIGN_RUN_FILL_ONLY included; only the one best local hit of a pair is reported. */
 #define BIALIGN_BATCH_LOCAL 64u
+/* OVERLAP (new in ABI 10 as added symbols: no existing struct or function changes): overlap alignments -- the global
+ * alignment whose end gaps cost nothing in either molecule ("ends-free", "semi-global": two fragments whose ends overhang
+ * each other, a domain against a protein when it is not known which contains the other).  The recurrence, the guards,
+ * the band and the tie-breaks are unchanged.  The mode makes the following changes.
+ *   Start.  At every lattice point (0, j, 0, j) with j >= 1, and at every (i, 0, i, 0) with i >= 1, the value that the
+ *     origin's 0 occupies today becomes max(recurrence value, 0).  In the affine recurrence that value is state 8.  In
+ *     the one-layer recurrence it is the cell's one value.  The origin stays 0.  Every other state and cell is computed
+ *     as before.
+ *   End.  score = max E over the end cells (i, m, i, m), 0 <= i <= n, and (n, j, n, j), 0 <= j <= m.  E is defined as for
+ *     FIT and LOCAL.  (end_a, end_b) is the end cell that attains the maximum with the smallest i, then the smallest j.
+ *     This is LOCAL's order, and the order of LOCAL's key.  score >= 0 always: (0, m, 0, m) and (n, 0, n, 0) are floored
+ *     starts and ends at once.
+ *   Walk.  The walk starts at (end_a, end_b, end_a, end_b).  In the affine recurrence it starts in the best state there,
+ *     with ties broken as today at (n, m, n, m).  It applies the existing tie-breaks.  It stops, complete, the first
+ *     time it stands on a point (0, j, 0, j) or (i, 0, i, 0) whose stored value is exactly 0.  In the affine recurrence
+ *     it must also be in state 8.  It is checked once on arrival, before it picks a predecessor.  That point is
+ *     (start_a, start_b).  The trace is the global alignment of A[start_a:end_a] with B[start_b:end_b], in the existing
+ *     byte code.
+ *   Equivalence.  For costs inside the int32 safety window, score = the maximum of global(A[i0:i1], B[j0:j1]) over the
+ *     windows with (i0 = 0 or j0 = 0) and (i1 = n or j1 = m).  The per-column bound is unchanged.
+ * Accepted for max_shift <= BIALIGN_MAX_SHIFT_TILED, both recurrences, any sign of gap_opening_cost (as FIT), every form
+ * of mu1 and mu2, in full storage and with SCORE_ONLY (so in all three bialign_batch_create_null* entry points, which pass
+ * it through), for pairs with n + m < 60000 (the key's position is 32 bits wide).  With FIT or LOCAL: BIALIGN_E_INVALID.
+ * With LEAN_TRACE or LEVEL_TRACE, or beyond the tiled band: BIALIGN_E_UNSUPPORTED.  There is no silent fallback to
+ * LEAN_TRACE: it is BIALIGN_E_NOMEM instead.  bialign_batch_get_scores returns the overlap score,
+ * bialign_batch_get_traces the walk above (complete keeps its meaning), bialign_batch_dump_layers the OVERLAP layers,
+ * bialign_batch_get_overlap_spans the spans.  Scores and ends are there after every run, SCORE_ONLY and
+ * BIALIGN_RUN_FILL_ONLY included. */
+#define BIALIGN_BATCH_OVERLAP 128u
 /* Bits of bialign_params.flags beyond the ones above: BIALIGN_E_INVALID. */
 
 typedef struct bialign_engine bialign_engine; /* one per (process, device) */
@@ -399,6 +428,13 @@ int bialign_batch_get_fit_spans(const bialign_batch* b, int32_t* start_b, int32_
  * SCORE_ONLY or BIALIGN_RUN_FILL_ONLY run the ends are valid and start_a[p] = start_b[p] = -1 (so they are for a pair
  * whose traceback is incomplete). */
 int bialign_batch_get_local_spans(const bialign_batch* b, int32_t* start_a, int32_t* end_a, int32_t* start_b, int32_t* end_b);
+
+/* Overlap alignments (BIALIGN_BATCH_OVERLAP, new in ABI 10 as an added symbol): the contract of
+ * bialign_batch_get_local_spans.  Pair p's alignment is that of A[start_a[p]:end_a[p]] with B[start_b[p]:end_b[p]]
+ * (0-based, half open).  The ends are valid after every run; the starts are -1 after a SCORE_ONLY or
+ * BIALIGN_RUN_FILL_ONLY run, or for a pair whose traceback is incomplete.  A batch created without OVERLAP, or a null
+ * batch: BIALIGN_E_INVALID. */
+int bialign_batch_get_overlap_spans(const bialign_batch* b, int32_t* start_a, int32_t* end_a, int32_t* start_b, int32_t* end_b);
 
 /* Test / introspection hooks.
  * dump_layers re-runs the fill of one pair and writes its layers in the
