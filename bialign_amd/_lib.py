@@ -81,6 +81,21 @@ class NullInfo(ctypes.Structure):
                 ("replica_bytes", ctypes.c_int64)]
 
 
+class HitSpec(ctypes.Structure):
+    """bialign_hit_spec: the hit search of a FIT batch."""
+    _fields_ = [("max_hits", ctypes.c_int32), ("max_walks", ctypes.c_int32), ("min_score", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+class HitInfo(ctypes.Structure):
+    _fields_ = [("spec", HitSpec), ("buffer_bytes", ctypes.c_int64), ("search_ms", ctypes.c_double)]
+
+
+HITS_NOT_SEARCHED, HITS_EXHAUSTED, HITS_MAX_HITS, HITS_MAX_WALKS = 0, 1, 2, 3  # BIALIGN_HITS_*
+HIT_STATUS = ("not_searched", "exhausted", "max_hits", "max_walks")
+MAX_HITS = 256
+
+
 class BatchInfo(ctypes.Structure):
     _fields_ = [("npairs", ctypes.c_int32), ("nchunks", ctypes.c_int32),
                 ("affine", ctypes.c_int32), ("max_shift", ctypes.c_int32),
@@ -124,6 +139,11 @@ SYMBOLS = [
     ("bialign_batch_get_fit_spans", ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p]),
     ("bialign_batch_get_local_spans", ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p, c_i32p]),
     ("bialign_batch_get_overlap_spans", ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p, c_i32p]),
+    ("bialign_batch_set_hits", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HitSpec)]),
+    ("bialign_batch_get_hit_profile", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_i32p]),
+    ("bialign_batch_get_hits", ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_u8p, c_i64p]),
+    ("bialign_batch_get_hit_walks", ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p]),
+    ("bialign_batch_get_hit_info", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HitInfo)]),
     ("bialign_batch_dump_layers", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_i32p]),
     ("bialign_batch_create_null", ctypes.c_int,
      [ctypes.c_void_p, ctypes.POINTER(Params), ctypes.POINTER(Scoring), ctypes.POINTER(Pairs),

@@ -76,8 +76,10 @@ def encode_pairs(pairs, params):
 
 def make_batch(pairs, params, engine=None, hbm_budget_bytes=0, recurrence=0, mu2_dense=None,
                score_only=False, lean_trace=False, mu1_dense=None, level_trace=False, null_dense=None, fit=False,
-               local=False, overlap=False):
+               local=False, overlap=False, hits=None):
     """``fit``: fit alignments, A inside a longer B with B's end gaps free (engine.Batch).
+    ``hits``: ``(max_hits, min_score)`` or ``(max_hits, min_score, max_walks)``, a shorthand for ``Batch.set_hits`` on a
+    ``fit`` batch in full storage: every run also searches each pair for its disjoint placements of A in B.
     ``local``: local alignments, the best-scoring parts of A and B with the ends of both free (engine.Batch).
     ``overlap``: overlap alignments, the global alignment with the end gaps of both molecules free (engine.Batch).
     ``mu1_dense`` / ``mu2_dense``: optional lists of one (len A, len B) int table per pair (engine.Batch).
@@ -85,6 +87,8 @@ def make_batch(pairs, params, engine=None, hbm_budget_bytes=0, recurrence=0, mu2
     ``null_dense``: ``(replicas, seed)``, a null batch of these pairs with their dense tables
     (``significance.null_dense_batch``): score-only, no ``lean_trace`` / ``level_trace``."""
     _check_storage(score_only, lean_trace, level_trace)
+    if hits is not None:
+        hits = check_hits_arg(hits, fit, score_only, null_dense)
     if null_dense is not None:
         from .significance import check_dense_args
         if lean_trace or level_trace:
@@ -93,11 +97,44 @@ def make_batch(pairs, params, engine=None, hbm_budget_bytes=0, recurrence=0, mu2
         null_dense = (replicas, seed)
     from .engine import Batch, default_engine  # loads the HIP library (no CPU fallback)
     model, fb = encode_flat(pairs, params)
-    return Batch(engine or default_engine(), fb, None, model.s1, model.s2,
-                 params["gap_opening_cost"], params["gap_cost"], params["shift_cost"],
-                 params["max_shift"], hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence,
-                 mu2_dense=mu2_dense, score_only=score_only, lean_trace=lean_trace, mu1_dense=mu1_dense,
-                 level_trace=level_trace, fit=fit, local=local, overlap=overlap, **({} if null_dense is None else dict(null_dense=null_dense)))
+    b = Batch(engine or default_engine(), fb, None, model.s1, model.s2,
+              params["gap_opening_cost"], params["gap_cost"], params["shift_cost"],
+              params["max_shift"], hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence,
+              mu2_dense=mu2_dense, score_only=score_only, lean_trace=lean_trace, mu1_dense=mu1_dense,
+              level_trace=level_trace, fit=fit, local=local, overlap=overlap, **({} if null_dense is None else dict(null_dense=null_dense)))
+    if hits is not None:
+        b.set_hits(*hits)
+    return b
+
+
+def check_hit_spec(max_hits, min_score, max_walks=0):
+    """The hit search's parameters as include/bialign.h states them -> ints; ValueError before the library is called."""
+    try:
+        max_hits, min_score, max_walks = int(max_hits), int(min_score), int(max_walks)
+    except (TypeError, ValueError):
+        raise ValueError("max_hits, min_score and max_walks must be integers") from None
+    if not 1 <= max_hits <= 256:
+        raise ValueError(f"max_hits must be 1..256, got {max_hits}")
+    if min_score < 1:
+        raise ValueError(f"min_score must be >= 1, got {min_score}")
+    if max_walks != 0 and max_walks < max_hits:
+        raise ValueError(f"max_walks must be 0 (4 * max_hits) or >= max_hits, got {max_walks}")
+    return max_hits, min_score, max_walks
+
+
+def check_hits_arg(hits, fit, score_only, null=None):
+    """``hits=`` of ``make_batch`` -> ``(max_hits, min_score, max_walks)``: the search needs a fit batch in full storage."""
+    if not fit:
+        raise ValueError("hits= needs fit=True: the hit search walks the placements of A in B of a fit batch")
+    if score_only or null is not None:
+        raise ValueError("hits= excludes score_only and null batches: the hit search walks through the full layers")
+    try:
+        hits = tuple(hits)
+    except TypeError:
+        raise ValueError("hits must be (max_hits, min_score) or (max_hits, min_score, max_walks)") from None
+    if len(hits) not in (2, 3):
+        raise ValueError("hits must be (max_hits, min_score) or (max_hits, min_score, max_walks)")
+    return check_hit_spec(*hits)
 
 
 def _check_storage(score_only, lean_trace, level_trace):

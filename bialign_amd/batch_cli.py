@@ -29,6 +29,11 @@ fifth column, and ``--zscore`` scores the shuffles in the same mode.
 (overlap alignments: include/bialign.h, BIALIGN_BATCH_OVERLAP; not with ``--fit`` or ``--local``).  The output has the
 form of ``--local``: the ``A span`` and ``B span`` lines, the alignment decoded on the two windows, the 1-based ends as
 fourth and fifth column under ``--score_only``, ``--zscore`` in the same mode.
+
+``--fit --hits K --hit_min_score X`` also searches every pair for up to K disjoint placements of A in B that score at
+least X (include/bialign.h, "Hit search").  Behind each pair's block follow ``HITS: <n> (<status>)`` and one line per hit
+in the form of ``--fit``'s span line behind a hit index, ``hit <h>\tB span\t <start_b+1>..<end_b>\t<score>``; hit 0 is the
+pair's own alignment.  Not without ``--fit``, not with ``--score_only`` or ``--zscore``.
 """
 import argparse
 import sys
@@ -78,6 +83,11 @@ def build_parser():
                    help="Overlap alignments: the global alignment whose end gaps are free in both molecules (dovetails, "
                         "containment in either direction); prints the aligned stretch as 'A span' and 'B span' lines "
                         "behind 'SCORE:'. Not with --fit or --local.")
+    p.add_argument("--hits", type=int, default=0, metavar="K",
+                   help="With --fit: also search every pair for up to K (1..256) disjoint placements of molecule A in "
+                        "molecule B and print one 'hit' line each behind the pair's block. Not with --score_only or --zscore.")
+    p.add_argument("--hit_min_score", type=int, default=None, metavar="X",
+                   help="The least score (>= 1) of a placement that --hits reports; required with --hits.")
     p.add_argument("--zscore_seed", type=int, default=0, metavar="N",
                    help="Seed of the shuffles (default 0); shuffle r of a pair is a function of the seed, r and the "
                         "pair's position among the pairs its process aligns.")
@@ -94,6 +104,28 @@ def span_line(start_b, end_b):
     """The line behind ``SCORE:`` of a ``--fit`` pair: the aligned part of B, 1-based and inclusive (an empty part, where
     all of A is gapped, reads start_b+1..start_b)."""
     return f"B span\t {int(start_b) + 1}..{int(end_b)}"
+
+
+def hit_line(h, start_b, end_b, score):
+    """The line of hit ``h`` of a ``--hits`` pair: ``--fit``'s span line behind the hit index, then the hit's score."""
+    return f"hit {h}\t{span_line(start_b, end_b)}\t{int(score)}"
+
+
+def check_hit_options(parser, args):
+    """``--hits`` / ``--hit_min_score`` -> ``hits=`` of ``make_batch`` or None; a parser error where they do not apply."""
+    if not args.hits and args.hit_min_score is None:
+        return None
+    if not args.hits or args.hit_min_score is None:
+        parser.error("--hits and --hit_min_score go together")
+    if not args.fit:
+        parser.error("--hits needs --fit")
+    if args.score_only or args.zscore:
+        parser.error("--hits excludes --score_only and --zscore")
+    from .batch import check_hit_spec
+    try:
+        return check_hit_spec(args.hits, args.hit_min_score)
+    except ValueError as e:
+        parser.error(str(e))
 
 
 def local_span_lines(start_a, end_a, start_b, end_b):
@@ -168,8 +200,9 @@ def _main(argv=None):
         parser.error("--fit and --local exclude each other")
     if args.overlap and (args.fit or args.local):
         parser.error("--overlap excludes --fit and --local")
+    hits = check_hit_options(parser, args)
     params = {k: v for k, v in vars(args).items()
-              if k not in ("pairs", "verbose", "score_only", "zscore", "zscore_seed", "fit", "local", "overlap")}
+              if k not in ("pairs", "verbose", "score_only", "zscore", "zscore_seed", "fit", "local", "overlap", "hits", "hit_min_score")}
     if args.zscore:
         from .significance import check_null
         check_null((args.zscore, args.zscore_seed))
@@ -184,7 +217,7 @@ def _main(argv=None):
     if len(mine):
         batch = make_batch([(r[1], r[4], r[2], r[5]) for r in (records[p] for p in mine)], params,
                            engine=default_engine(local_rank), score_only=args.score_only, fit=args.fit,
-                           local=args.local, overlap=args.overlap)
+                           local=args.local, overlap=args.overlap, hits=hits)
         batch.run()
         scores = batch.scores()
         start_b, end_b = batch.fit_spans() if args.fit else (None, None)
@@ -203,12 +236,17 @@ def _main(argv=None):
                     print(zscore_line(z, t))
         else:
             traces, complete = batch.traces()
+            found, status = batch.fit_hits() if hits else (None, None)
             for t, p in enumerate(mine):
                 trace = trace_codes_to_columns(traces[t], as_tuples=not batch.affine)
                 span = (int(start_b[t]), int(end_b[t])) if args.fit and complete[t] else None
                 lspan = tuple(int(x[t]) for x in lspans) if lspans and complete[t] else None
                 for line in pair_block(p, records[p], params, int(scores[t]), trace, bool(complete[t]), args.verbose, span, lspan):
                     print(line)
+                if hits:
+                    print(f"HITS: {len(found[t])} ({status[t]})")
+                    for h, (hs, he, hscore, _) in enumerate(found[t]):
+                        print(hit_line(h, hs, he, hscore))
                 if z:
                     print(zscore_line(z, t))
         batch.close()

@@ -3,7 +3,7 @@
 The kernels are templates on max_shift; each (max_shift, kind) slice is its own translation unit
 (csrc/bialign_inst.hip with -DBIALIGN_TU_S / -DBIALIGN_TU_KIND), compiled in parallel, then linked
 with the wide-band unit, the mu2 table builder (csrc/bialign_mu2_build.hip), the shuffled-null kernels
-(csrc/bialign_null.hip) and the C-ABI unit
+(csrc/bialign_null.hip), the hit search of FIT batches (csrc/bialign_hits.hip) and the C-ABI unit
 (csrc/bialign_capi.hip) into one shared library.
 """
 import concurrent.futures
@@ -42,6 +42,7 @@ def units():
     # the FEATURE form's table builder reproduces the reference's doubles operation by operation: nothing contracted
     out.append(("mu2_build.o", "bialign_mu2_build.hip", ["-ffp-contract=off"]))
     out.append(("null.o", "bialign_null.hip", []))
+    out.append(("hits.o", "bialign_hits.hip", []))  # the hit search of FIT batches: a unit of its own
     out.append(("capi.o", "bialign_capi.hip", []))
     return out
 

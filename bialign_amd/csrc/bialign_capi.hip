@@ -4,7 +4,7 @@
 // HBM-budgeted chunks, team shapes) decided, launch fill + traceback per chunk on the engine's
 // stream, time the kernels with HIP events, hand results back.  No CPU compute
 // path exists here: if the device or a kernel is unavailable the call fails.
-#include "bialign_host.hpp"
+#include "bialign_hits.hpp"
 
 using namespace bialign;
 
@@ -347,6 +347,41 @@ int upload_inputs(bialign_batch* b, const bialign_scoring* sc, const bialign_pai
   return BIALIGN_OK;
 }
 
+// ---- hit search (bialign_hits.hpp): what a launch is given, and the state its results have ahead of a run
+HitArgs hit_args(const bialign_batch* b, bool search) {
+  HitArgs h{};
+  h.max_hits = b->hit_spec.max_hits, h.max_walks = b->hit_spec.max_walks, h.min_score = b->hit_spec.min_score;
+  h.search = search ? 1 : 0;
+  h.lds_inputs = (int32_t)((b->lds_trace + 15) & ~size_t(15));
+  h.mask_words = b->hit_mask_words;
+  h.prof_off = b->d_hit_prof_off.p;
+  h.profile = b->d_hit_profile.p;
+  h.head = b->d_hit_head.p;
+  h.hits = b->d_hit_rec.p;
+  h.walks = b->d_hit_walks.p;
+  h.trace = b->d_hit_trace.p;
+  return h;
+}
+
+// profile: -infinity; status NOT_SEARCHED, no hits, no walks; records -1
+int reset_hits(bialign_batch* b, hipStream_t st) {
+  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)b->d_hit_profile.p, BIALIGN_NEG_INF, b->d_hit_profile.n, st));
+  HIP_TRY(hipMemsetAsync(b->d_hit_head.p, 0, sizeof(int32_t) * b->d_hit_head.n, st));
+  HIP_TRY(hipMemsetAsync(b->d_hit_rec.p, 0xff, sizeof(int32_t) * b->d_hit_rec.n, st));
+  HIP_TRY(hipMemsetAsync(b->d_hit_walks.p, 0xff, sizeof(int32_t) * b->d_hit_walks.n, st));
+  return BIALIGN_OK;
+}
+
+// the hit getters' common refusals, and the end of a pending run
+int hits_ready(const bialign_batch* b) {
+  if (!b) return fail(BIALIGN_E_INVALID, "NULL batch");
+  if (int rc = bialign_batch_wait(const_cast<bialign_batch*>(b))) return rc;
+  if (!b->hits_on) return fail(BIALIGN_E_INVALID, "no hit search is set on this batch (bialign_batch_set_hits)");
+  if (!b->ran || !b->hits_ran) return fail(BIALIGN_E_INVALID, "bialign_batch_run has not been called since bialign_batch_set_hits");
+  HIP_TRY(hipSetDevice(b->eng->device));
+  return BIALIGN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -603,6 +638,15 @@ static int enqueue_run(bialign_batch* b, uint32_t flags) {
   if (b->free_ends()) HIP_TRY(hipMemsetAsync(b->d_span.p, 0xff, sizeof(int32_t) * b->d_span.n, st));  // spans: -1 until a kernel writes them
   if (b->end_key())  // keys: zero, below every key a sweep folds in
     HIP_TRY(hipMemsetAsync(b->d_local_key.p, 0, sizeof(unsigned long long) * b->npairs, st));
+  b->hits_pending = false;
+  if (b->hits_on) {  // hit search: its results are per run, like the spans
+    while ((int)b->hit_evs.size() < 2 * nchunks) {
+      hipEvent_t e = nullptr;
+      HIP_TRY(hipEventCreate(&e));
+      b->hit_evs.push_back(e);
+    }
+    if (int rc = reset_hits(b, st)) return rc;
+  }
   if (b->null_R) {  // null batch: the replicas' B codes, all of them ahead of the first sweep (timed on its own, outside fill_ms)
     HIP_TRY(hipEventRecord(b->null_evs[0], st));
     if (int rc = launch_shuffle_null(b, 0, b->npairs)) return rc;
@@ -636,6 +680,12 @@ static int enqueue_run(bialign_batch* b, uint32_t flags) {
       if (rc) return rc;
     }
     HIP_TRY(hipEventRecord(b->evs[3 * c + 2], st));
+    if (b->hits_on) {  // behind the chunk's traceback, ahead of the next chunk's sweep: the layers are still the chunk's
+      HIP_TRY(hipEventRecord(b->hit_evs[2 * c], st));
+      if (int rc2 = launch_fit_hits(b, v, hit_args(b, do_trace), first, count)) return rc2;
+      HIP_TRY(hipEventRecord(b->hit_evs[2 * c + 1], st));
+      b->hits_pending = true;
+    }
     b->timing.fill_launches += 1;
     b->timing.traceback_launches += 1;
     b->timing.waves_per_pair = std::abs(b->last_team);
@@ -671,6 +721,15 @@ int bialign_batch_wait(bialign_batch* b) {
       HIP_TRY(hipEventElapsedTime(&f, b->null_evs[0], b->null_evs[1]));
       b->shuffle_ms = f;
     }
+    if (b->hits_pending) {  // the last chunk's search lies behind the event waited for above
+      HIP_TRY(hipEventSynchronize(b->hit_evs[2 * nchunks - 1]));
+      b->search_ms = 0;
+      for (int c = 0; c < nchunks; ++c) {
+        float f = 0;
+        HIP_TRY(hipEventElapsedTime(&f, b->hit_evs[2 * c], b->hit_evs[2 * c + 1]));
+        b->search_ms += f;
+      }
+    }
     int32_t err = 0;
     HIP_TRY(hipMemcpy(&err, b->d_err.p, sizeof err, hipMemcpyDeviceToHost));
     if (!err) break;
@@ -698,6 +757,7 @@ int bialign_batch_wait(bialign_batch* b) {
   b->timing.packed_records = b->used_pack ? 1 : 0;
   b->ran = true;
   b->ran_trace = b->pending_trace;
+  b->hits_ran = b->hits_pending;
   return BIALIGN_OK;
 }
 
@@ -768,6 +828,112 @@ int bialign_batch_get_traces(const bialign_batch* b, uint8_t* trace, int64_t* tr
   HIP_TRY(hipMemcpy(trace_len, b->d_tlen.p, sizeof(int32_t) * b->npairs, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(complete, b->d_complete.p, sizeof(int32_t) * b->npairs, hipMemcpyDeviceToHost));
   for (int p = 0; p < b->npairs; ++p) trace_off[p] = b->pairs[p].trace_off;
+  return BIALIGN_OK;
+}
+
+int bialign_batch_set_hits(bialign_batch* b, const bialign_hit_spec* spec) {
+  if (!b) return fail(BIALIGN_E_INVALID, "NULL batch");
+  if (int rc = bialign_batch_wait(b)) return rc;  // a pending run still writes the buffers released below
+  HIP_TRY(hipSetDevice(b->eng->device));
+  b->release_hits();
+  if (!spec) return BIALIGN_OK;
+  if (b->mode != bialign::AlignMode::Fit || b->lean || b->null_R)
+    return fail(BIALIGN_E_UNSUPPORTED, "the hit search needs a FIT batch in full storage (not %s)",
+                b->null_R ? "a null batch" : (b->mode != bialign::AlignMode::Fit ? "a batch without BIALIGN_BATCH_FIT" : "SCORE_ONLY"));
+  if (spec->max_hits < 1 || spec->max_hits > 256) return fail(BIALIGN_E_INVALID, "max_hits must be 1..256, got %d", spec->max_hits);
+  if (spec->min_score < 1) return fail(BIALIGN_E_INVALID, "min_score must be >= 1, got %d", spec->min_score);
+  if (spec->max_walks != 0 && spec->max_walks < spec->max_hits)
+    return fail(BIALIGN_E_INVALID, "max_walks must be 0 (4 * max_hits) or >= max_hits = %d, got %d", spec->max_hits, spec->max_walks);
+  if (spec->reserved != 0) return fail(BIALIGN_E_INVALID, "bialign_hit_spec.reserved must be 0");
+  bialign_hit_spec sp = *spec;
+  if (sp.max_walks == 0) sp.max_walks = 4 * sp.max_hits;
+  int max_m = 0;
+  b->hit_prof_off.assign((size_t)b->npairs + 1, 0);
+  for (int p = 0; p < b->npairs; ++p) {
+    max_m = std::max(max_m, b->pairs[p].m);
+    b->hit_prof_off[p + 1] = b->hit_prof_off[p] + b->pairs[p].m + 1;
+  }
+  b->hit_spec = sp;
+  b->hit_mask_words = (max_m + 32) >> 5;
+  const size_t lds = fit_hits_lds(hit_args(b, true));
+  if (lds > 160 * 1024)
+    return fail(BIALIGN_E_UNSUPPORTED, "the hit search's mask, spans and staged inputs need %zu bytes of LDS (160 KiB at most)", lds);
+  const size_t prof = (size_t)b->hit_prof_off.back(), recs = (size_t)b->npairs * sp.max_hits * 4,
+               walks = (size_t)b->npairs * sp.max_walks * 4, trace = (size_t)sp.max_hits * (size_t)b->trace_bytes;
+  hipStream_t st = b->eng->stream;
+  hipError_t err = b->d_hit_profile.alloc(prof);
+  if (err == hipSuccess) err = b->d_hit_head.alloc(4 * (size_t)b->npairs);
+  if (err == hipSuccess) err = b->d_hit_rec.alloc(recs);
+  if (err == hipSuccess) err = b->d_hit_walks.alloc(walks);
+  if (err == hipSuccess) err = b->d_hit_trace.alloc(trace);
+  if (err == hipSuccess) err = b->d_hit_prof_off.upload(b->hit_prof_off.data(), (size_t)b->npairs, st);
+  if (err == hipSuccess) err = hipStreamSynchronize(st);
+  if (err == hipSuccess && getenv("BIALIGN_TEST_FAIL_HITS_ALLOC")) err = hipErrorOutOfMemory;  // tests: pretend an allocation failed
+  if (err != hipSuccess) {
+    (void)hipGetLastError();
+    b->release_hits();
+    return fail(BIALIGN_E_NOMEM, "hit search: allocating %zu bytes of result buffers failed: %s",
+                (prof + 4 * (size_t)b->npairs + recs + walks) * 4 + trace, hipGetErrorString(err));
+  }
+  b->hit_bytes = (int64_t)((prof + 4 * (size_t)b->npairs + recs + walks) * 4 + trace + (size_t)b->npairs * 8);
+  b->hits_on = true;
+  b->search_ms = 0;
+  return BIALIGN_OK;
+}
+
+int bialign_batch_get_hit_profile(const bialign_batch* b, int32_t pair, int32_t* out) {
+  if (!out) return fail(BIALIGN_E_INVALID, "NULL argument");
+  if (int rc = hits_ready(b)) return rc;
+  if (pair < 0 || pair >= b->npairs) return fail(BIALIGN_E_INVALID, "pair %d out of range", pair);
+  HIP_TRY(hipMemcpy(out, b->d_hit_profile.p + b->hit_prof_off[pair], sizeof(int32_t) * (b->pairs[pair].m + 1), hipMemcpyDeviceToHost));
+  return BIALIGN_OK;
+}
+
+int bialign_batch_get_hits(const bialign_batch* b, int32_t* nhits, int32_t* status, int32_t* start_b, int32_t* end_b,
+                           int32_t* score, int32_t* trace_len, uint8_t* trace, int64_t* trace_off) {
+  if (!nhits || !status || !start_b || !end_b || !score || !trace_len || !trace != !trace_off) return fail(BIALIGN_E_INVALID, "NULL argument");
+  if (int rc = hits_ready(b)) return rc;
+  const int K = b->hit_spec.max_hits;
+  std::vector<int32_t> head(4 * (size_t)b->npairs), rec((size_t)b->npairs * K * 4);
+  HIP_TRY(hipMemcpy(head.data(), b->d_hit_head.p, sizeof(int32_t) * head.size(), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(rec.data(), b->d_hit_rec.p, sizeof(int32_t) * rec.size(), hipMemcpyDeviceToHost));
+  if (trace) HIP_TRY(hipMemcpy(trace, b->d_hit_trace.p, (size_t)K * b->trace_bytes, hipMemcpyDeviceToHost));
+  for (int p = 0; p < b->npairs; ++p) {
+    nhits[p] = head[4 * (size_t)p], status[p] = head[4 * (size_t)p + 2];
+    for (int h = 0; h < K; ++h) {
+      const size_t t = (size_t)p * K + h;
+      start_b[t] = rec[4 * t], end_b[t] = rec[4 * t + 1], score[t] = rec[4 * t + 2], trace_len[t] = rec[4 * t + 3];
+      if (trace_off) trace_off[t] = (int64_t)K * b->pairs[p].trace_off + (int64_t)h * b->pairs[p].trace_cap;
+    }
+  }
+  return BIALIGN_OK;
+}
+
+int bialign_batch_get_hit_walks(const bialign_batch* b, int32_t* nwalks, int32_t* end_b, int32_t* start_b, int32_t* score,
+                                int32_t* accepted) {
+  if (!nwalks || !end_b || !start_b || !score || !accepted) return fail(BIALIGN_E_INVALID, "NULL argument");
+  if (int rc = hits_ready(b)) return rc;
+  const int K = b->hit_spec.max_walks;
+  std::vector<int32_t> head(4 * (size_t)b->npairs), rec((size_t)b->npairs * K * 4);
+  HIP_TRY(hipMemcpy(head.data(), b->d_hit_head.p, sizeof(int32_t) * head.size(), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(rec.data(), b->d_hit_walks.p, sizeof(int32_t) * rec.size(), hipMemcpyDeviceToHost));
+  for (int p = 0; p < b->npairs; ++p) {
+    nwalks[p] = head[4 * (size_t)p + 1];
+    for (int h = 0; h < K; ++h) {
+      const size_t t = (size_t)p * K + h;
+      end_b[t] = rec[4 * t], start_b[t] = rec[4 * t + 1], score[t] = rec[4 * t + 2], accepted[t] = rec[4 * t + 3];
+    }
+  }
+  return BIALIGN_OK;
+}
+
+int bialign_batch_get_hit_info(const bialign_batch* b, bialign_hit_info* info) {
+  if (!b || !info) return fail(BIALIGN_E_INVALID, "NULL argument");
+  if (int rc = bialign_batch_wait(const_cast<bialign_batch*>(b))) return rc;
+  if (!b->hits_on) return fail(BIALIGN_E_INVALID, "no hit search is set on this batch (bialign_batch_set_hits)");
+  info->spec = b->hit_spec;
+  info->buffer_bytes = b->hit_bytes;
+  info->search_ms = b->hits_ran ? b->search_ms : 0;
   return BIALIGN_OK;
 }
 

@@ -137,6 +137,27 @@ struct bialign_batch : bialign::BatchPlan {  // the plan (bialign_plan.hpp), and
   hipEvent_t null_evs[4] = {nullptr, nullptr, nullptr, nullptr};  // around the shuffle launch of a run, around the reduction
   double shuffle_ms = 0, stats_ms = 0;      // HIP-event times (not part of fill_ms)
   DevBuf<TraceState> d_tstate;
+  // Hit search (bialign_batch_set_hits, bialign_hits.hpp): the spec (max_walks resolved) and the result buffers of the whole
+  // batch, reset ahead of every run.  hits_on false: a run touches none of this.
+  bool hits_on = false;
+  bialign_hit_spec hit_spec{};
+  DevBuf<int32_t> d_hit_profile, d_hit_head, d_hit_rec, d_hit_walks;  // HitArgs::profile, head, hits, walks
+  DevBuf<int64_t> d_hit_prof_off;
+  DevBuf<uint8_t> d_hit_trace;
+  std::vector<int64_t> hit_prof_off;  // [npairs + 1]
+  int hit_mask_words = 0;             // HitArgs::mask_words
+  int64_t hit_bytes = 0;
+  std::vector<hipEvent_t> hit_evs;    // two per chunk, around the search's launch
+  bool hits_pending = false;          // the pending run enqueued searches
+  bool hits_ran = false;              // the last completed run filled the result buffers
+  double search_ms = 0;
+  void release_hits() {
+    hits_on = hits_ran = false;
+    for (DevBuf<int32_t>* d : {&d_hit_profile, &d_hit_head, &d_hit_rec, &d_hit_walks}) d->release();
+    d_hit_prof_off.release();
+    d_hit_trace.release();
+    hit_bytes = 0;
+  }
   bialign_timing timing{};
   bool ran = false, ran_trace = false;
   bool pending = false, pending_trace = false;  // an enqueued run not yet waited for
@@ -148,6 +169,8 @@ struct bialign_batch : bialign::BatchPlan {  // the plan (bialign_plan.hpp), and
     for (hipEvent_t e : build_evs)
       if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : null_evs)
+      if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : hit_evs)
       if (e) (void)hipEventDestroy(e);
     if (uploaded) (void)hipEventDestroy(uploaded);
   }

@@ -87,6 +87,152 @@ __device__ __forceinline__ void free_end_scan(int n, int m, bool a_ends, int lan
   *end_b = x < n ? m : x - n;
 }
 
+// ---------------------------------------------------------------------------
+// The walk as device functions: start point in, (end point, len, how it ended) out.  A walk stands on lattice point
+// (i, j, k, l) in state st (affine) with layer value cur, running shifts (d0, d1), len columns emitted.  The hit search
+// (bialign_hits.hpp) walks several ends per pair through them.  The two traceback kernels below keep the text of their own
+// loops, of which these are copies line for line: when the kernels called these functions instead, hipcc's code for them
+// changed by more than labels and register numbers (a handful of instructions per kernel, the score-only forms included;
+// DESIGN.md section 7f), and their device code is held fixed.  A change to a rule of the walk is made in both places;
+// tests/test_gpu_fit_hits.py holds hit 0 of every pair to the kernels' trace byte for byte.
+// ---------------------------------------------------------------------------
+struct WalkPoint {
+  int i, j, k, l, st, cur, d0, d1, len;
+};
+enum : int { WALK_INCOMPLETE = 0, WALK_COMPLETE = 1, WALK_LEFT = 2 };  // LEFT: `leave` said so (STRIP, LEVEL: next round)
+
+// pyx:573-582: the best end layer at (i, j, i, j), and the first state with the least shift that attains it
+template <typename Cell>
+__device__ __forceinline__ void affine_end_state(Cell&& cell, int i, int j, int SR, int c, int* best_out, int* st_out) {
+  constexpr int BIG = 0x7fffffff;
+  const int endv = c < 9 ? cell(i, j, SR, SR, c) : -BIG;
+  const int best = __builtin_amdgcn_readfirstlane(-wave_min16(-endv));
+  const int skey = (c < 9 && endv == best) ? (shift_of(c / 3, c % 3) << 4 | c) : BIG;
+  *st_out = __builtin_amdgcn_readfirstlane(wave_min16(skey)) & 15;
+  *best_out = best;
+}
+
+// Affine walk (pyx:535-586) from w to its end: lane c < 15 owns candidate c, lane 0 writes the columns end -> start into
+// out[0 .. cap).  cell(pi, pj, a, b, ss) reads a layer value, leave(i, j, k, l) ends a round of the continuing forms.
+template <bool D1, typename Cell, typename Leave>
+__device__ __forceinline__ int walk_affine(const DeviceBatch& A, const PairDesc& pd, const TraceInputs& in, const int32_t* mu1tab,
+                                           int SR, int c, bool fit, bool ovl, bool local, Cell&& cell, Leave&& leave,
+                                           uint8_t* out, int cap, WalkPoint& w) {
+  constexpr int BIG = 0x7fffffff;
+  const int m = pd.m;
+  const int beta = A.beta, gamma = A.gamma, delta = A.delta;
+  const uint8_t *sa = in.sa, *ca = in.ca, *sb = in.sb, *cb = in.cb;
+  int i = w.i, j = w.j, k = w.k, l = w.l, st = w.st, cur = w.cur, d0 = w.d0, d1 = w.d1, len = w.len;
+  int how = WALK_INCOMPLETE;
+  // lane-constant part of the candidate: its group and, for groups 2/3, the free half h
+  const int grp = c < 9 ? 1 : (c < 12 ? 2 : 3);
+  const int hfree = grp == 2 ? 2 - (c - 9) : 2 - (c - 12);  // h = M, X, Y in the generator's order
+  while (true) {
+    if (i == 0 && j == 0 && k == 0 && l == 0 && st == 8) { how = WALK_COMPLETE; break; }
+    if (fit && i == 0 && k == 0 && j == l && st == 8 && cur == 0) { how = WALK_COMPLETE; break; }  // fit: a free start, start_b = j
+    if (ovl && j == 0 && l == 0 && i == k && st == 8 && cur == 0) { how = WALK_COMPLETE; break; }  // overlap: and on column 0, start_a = i
+    if (local && i == k && j == l && st == 8 && cur == 0) { how = WALK_COMPLETE; break; }  // local: a free start, (start_a, start_b) = (i, j)
+    if (leave(i, j, k, l)) { how = WALK_LEFT; break; }
+    const int hU = st / 3, hV = st - 3 * hU;
+    const int u0 = hU >= 1, u1 = hU != 1, v0 = hV >= 1, v1 = hV != 1;
+    const int mu1 = (i >= 1 && j >= 1)
+                        ? (D1 ? mu1tab[(int64_t)(i - 1) * m + (j - 1)] : in.s1[sa[i - 1] * A.k1 + sb[j - 1]])
+                        : 0;
+    const int mu2 = (k >= 1 && l >= 1)
+                        ? ((D1 ? (A.dense_forms & 1) != 0 : A.dense_tab != nullptr)
+                               ? A.dense_tab[pd.tab_off + (int64_t)(k - 1) * m + (l - 1)]
+                               : in.s2[ca[k - 1] * A.k2 + cb[l - 1]])
+                        : 0;
+    const int valU = hU == 2 ? mu1 : gamma, valV = hV == 2 ? mu2 : gamma;
+
+    // this lane's candidate: offset, source state, score (pyx:84-131)
+    const int o0 = grp == 2 ? 0 : u0, o1 = grp == 2 ? 0 : u1;
+    const int o2 = grp == 3 ? 0 : v0, o3 = grp == 3 ? 0 : v1;
+    const int ss = grp == 1 ? c : (grp == 2 ? 3 * hU + hfree : 3 * hfree + hV);
+    const int ra = ss / 3, rb = ss - 3 * ra;
+    const int openU = (hU != 2 && ra != hU) ? beta : 0, openV = (hV != 2 && rb != hV) ? beta : 0;
+    const int sc = grp == 1   ? delta * shift_of(hU, hV) + valU + valV + openU + openV
+                   : grp == 2 ? delta * (v0 + v1) + valV + openV
+                              : delta * (u0 + u1) + valU + openU;
+    const int pi = i - o0, pj = j - o1, pk = k - o2, pl = l - o3;
+    const bool ok = c < 15 && pi >= 0 && pj >= 0 && pk >= 0 && pl >= 0 && abs(pk - pi) <= SR &&
+                    abs(pl - pj) <= SR;  // pyx:133-141
+    const int ld = ok ? cell(pi, pj, pk - pi + SR, pl - pj + SR, ss) : 0;
+    // pyx:554-565: cases reproducing the cell; look-ahead adds the offset AND the source state
+    const int r0 = ra >= 1, r1 = ra != 1, r2 = rb >= 1, r3 = rb != 1;
+    const int t0 = d0 + (o0 - o2) + (r0 - r2), t1 = d1 + (o1 - o3) + (r1 - r3);
+    const int key = (ok && ld + sc == cur) ? ((abs(t0) + abs(t1)) << 16 | abs(t1) << 8 | c) : BIG;
+    const int kmin = __builtin_amdgcn_readfirstlane(wave_min16(key));
+    if (kmin == BIG) break;  // pyx:570-571 -> "incomplete traceback"
+    const int pick = kmin & 63;
+    const int code = __builtin_amdgcn_readlane(o0 * 8 + o1 * 4 + o2 * 2 + o3, pick);
+    st = __builtin_amdgcn_readlane(ss, pick);
+    cur = __builtin_amdgcn_readlane(ld, pick);
+    const int q0 = (code >> 3) & 1, q1 = (code >> 2) & 1, q2 = (code >> 1) & 1, q3 = code & 1;
+    d0 += q0 - q2;  // pyx:566: only the offset moves the running shift
+    d1 += q1 - q3;
+    if (c == 0 && len < cap) out[len] = (uint8_t)code;
+    ++len;
+    i -= q0; j -= q1; k -= q2; l -= q3;
+  }
+  w = WalkPoint{i, j, k, l, st, cur, d0, d1, len};
+  return how;
+}
+
+// Non-affine walk (pyx:513-531): lane c < 13 = case c; it ends, complete, when no case reproduces the cell (the origin)
+// or on a free start.  w.st, w.d0 and w.d1 are unused.
+template <bool D1, typename Cell, typename Leave>
+__device__ __forceinline__ int walk_linear(const DeviceBatch& A, const PairDesc& pd, const TraceInputs& in, const int32_t* mu1tab,
+                                           int SR, int c, bool fit, bool ovl, bool local, Cell&& cell, Leave&& leave,
+                                           uint8_t* out, int cap, WalkPoint& w) {
+  constexpr int BIG = 0x7fffffff;
+  const int m = pd.m;
+  const int gamma = A.gamma, delta = A.delta;
+  const uint8_t *sa = in.sa, *ca = in.ca, *sb = in.sb, *cb = in.cb;
+  // offsets of the thirteen cases as bit masks o0*8+o1*4+o2*2+o3 (pyx:233-248), per lane
+  constexpr int OFF[16] = {15, 10, 5, 12, 3, 8, 4, 2, 1, 11, 7, 14, 13, 0, 0, 0};
+  int code_c = 0;
+#pragma unroll
+  for (int t = 0; t < 13; ++t)
+    if (c == t) code_c = OFF[t];
+  const int o0 = (code_c >> 3) & 1, o1 = (code_c >> 2) & 1, o2 = (code_c >> 1) & 1, o3 = code_c & 1;
+  // score of case c as a*mu1 + b*mu2 + const (pyx:233-248)
+  const int use1 = (c == 0 || c == 3 || c == 11 || c == 12), use2 = (c == 0 || c == 4 || c == 9 || c == 10);
+  const int gD = gamma + delta;
+  const int kconst = c == 0 ? 0 : (c <= 2 ? 2 * gamma : (c <= 4 ? delta : gD));
+
+  int i = w.i, j = w.j, k = w.k, l = w.l, cur = w.cur, len = w.len;
+  int how = WALK_COMPLETE;
+  while (true) {
+    if (fit && i == 0 && k == 0 && j == l && cur == 0) break;  // fit: a free start, start_b = j
+    if (ovl && j == 0 && l == 0 && i == k && cur == 0) break;  // overlap: and on column 0, start_a = i
+    if (local && i == k && j == l && cur == 0) break;          // local: a free start, (start_a, start_b) = (i, j)
+    if (leave(i, j, k, l)) { how = WALK_LEFT; break; }
+    const int mu1 = (i >= 1 && j >= 1)
+                        ? (D1 ? mu1tab[(int64_t)(i - 1) * m + (j - 1)] : in.s1[sa[i - 1] * A.k1 + sb[j - 1]])
+                        : 0;
+    const int mu2 = (k >= 1 && l >= 1)
+                        ? ((D1 ? (A.dense_forms & 1) != 0 : A.dense_tab != nullptr)
+                               ? A.dense_tab[pd.tab_off + (int64_t)(k - 1) * m + (l - 1)]
+                               : in.s2[ca[k - 1] * A.k2 + cb[l - 1]])
+                        : 0;
+    const int sc = kconst + (use1 ? mu1 : 0) + (use2 ? mu2 : 0);
+    const int pi = i - o0, pj = j - o1, pk = k - o2, pl = l - o3;
+    const bool ok = c < 13 && pi >= 0 && pj >= 0 && pk >= 0 && pl >= 0 && abs(pk - pi) <= SR && abs(pl - pj) <= SR;
+    const int ld = ok ? cell(pi, pj, pk - pi + SR, pl - pj + SR) : 0;
+    const int key = (ok && ld + sc == cur) ? c : BIG;
+    const int pick = __builtin_amdgcn_readfirstlane(wave_min16(key));
+    if (pick == BIG) break;
+    const int code = __builtin_amdgcn_readlane(code_c, pick);
+    cur = __builtin_amdgcn_readlane(ld, pick);
+    if (c == 0 && len < cap) out[len] = (uint8_t)code;
+    ++len;
+    i -= (code >> 3) & 1; j -= (code >> 2) & 1; k -= (code >> 1) & 1; l -= code & 1;
+  }
+  w = WalkPoint{i, j, k, l, 0, cur, 0, 0, len};
+  return how;
+}
+
 //   STRIP (lean traceback): the walk continues from the pair's
 //   TraceState through ONE strip -- the one fill_affine_kernel<.., RESW> has just re-swept into
 //   the scratch records -- and stops when it steps into the strip above (whose bottom row, the

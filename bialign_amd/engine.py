@@ -10,6 +10,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import lib, check
+from .batch import check_hit_spec
 from .significance import check_dense_tables, check_null
 
 STATES = [(0, 1, 0, 1), (0, 1, 1, 0), (0, 1, 1, 1), (1, 0, 0, 1), (1, 0, 1, 0),
@@ -104,7 +105,8 @@ class Batch:
     ``fit``: fit alignments (BIALIGN_BATCH_FIT): A inside a longer B, B's end gaps free.  ``scores()`` is the best
     global score of A against any substring of B, ``traces()`` that alignment, ``fit_spans()`` the substring.  Bands
     up to ``_lib.MAX_SHIFT_TILED``, full storage or ``score_only`` (and so null batches: the replicas are scored in
-    the same mode); not with ``lean_trace`` / ``level_trace``.
+    the same mode); not with ``lean_trace`` / ``level_trace``.  In full storage ``set_hits()`` adds a search for every
+    placement of A in B: ``fit_hits()``, ``hit_profile()``, ``fit_hit_walks()``.
     ``local``: local alignments (BIALIGN_BATCH_LOCAL): the best-scoring parts of A and B, the ends of both free.
     ``scores()`` is the best global score of any substring of A against any substring of B (>= 0), ``traces()`` that
     alignment, ``local_spans()`` the two substrings.  Bands up to ``_lib.MAX_SHIFT_TILED``, ``gap_opening_cost <= 0``
@@ -200,6 +202,7 @@ class Batch:
         self.fit = bool(fit)
         self.local = bool(local)
         self.overlap = bool(overlap)
+        self.hit_spec = None   # set_hits: (max_hits, max_walks, min_score)
         self._null_forms = (mu1_flat is not None, mu2_flat is not None) if null_dense is not None else None
         args = [engine._h, ctypes.byref(prm), ctypes.byref(sc), ctypes.byref(pr)]
         if feat is not None:
@@ -393,6 +396,67 @@ class Batch:
         start, end = np.empty(self.npairs, dtype=np.int32), np.empty(self.npairs, dtype=np.int32)
         check(lib.bialign_batch_get_fit_spans(self._h, _ptr(start, ctypes.c_int32), _ptr(end, ctypes.c_int32)))
         return start, end
+
+    def set_hits(self, max_hits, min_score=None, max_walks=0):
+        """Fit batch, full storage: search every later run for up to ``max_hits`` disjoint placements of A in B that
+        score at least ``min_score`` (bialign_batch_set_hits; the model is stated in include/bialign.h).  ``max_walks``
+        bounds the walks a pair may cost, 0 means ``4 * max_hits``.  ``set_hits(None)`` removes the search again."""
+        if max_hits is None:
+            check(lib.bialign_batch_set_hits(self._h, None))
+            self.hit_spec = None
+            return
+        if min_score is None:
+            raise ValueError("set_hits needs min_score (set_hits(None) removes the search)")
+        max_hits, min_score, max_walks = check_hit_spec(max_hits, min_score, max_walks)
+        spec = _lib.HitSpec(max_hits, max_walks, min_score, 0)
+        self.hit_spec = None
+        check(lib.bialign_batch_set_hits(self._h, ctypes.byref(spec)))
+        self.hit_spec = (max_hits, max_walks or 4 * max_hits, min_score)
+
+    def _need_hits(self):
+        if self.hit_spec is None:
+            raise ValueError("no hit search is set on this batch (set_hits, or make_batch(..., fit=True, hits=(K, min_score)))")
+        return self.hit_spec
+
+    def hit_profile(self, pair):
+        """The end-score profile of one pair: int32 ``E[0..len B]``, ``E[j]`` the score of the best placement of A that
+        ends at j.  -2^30 everywhere before a run."""
+        self._need_hits()
+        out = np.empty(int(self.len_b[pair]) + 1, dtype=np.int32)
+        check(lib.bialign_batch_get_hit_profile(self._h, int(pair), _ptr(out, ctypes.c_int32)))
+        return out
+
+    def fit_hits(self):
+        """-> (hits, status): per pair a list of ``(start_b, end_b, score, trace)`` in order of acceptance -- the global
+        alignment of A with ``B[start_b:end_b]``, trace as ``traces()`` gives it -- and one of ``_lib.HIT_STATUS``."""
+        k, _, _ = self._need_hits()
+        nh, st = (np.empty(self.npairs, dtype=np.int32) for _ in range(2))
+        start, end, score, tlen = (np.empty((self.npairs, k), dtype=np.int32) for _ in range(4))
+        buf = np.empty(max(1, k * self.info["trace_bytes"]), dtype=np.uint8)
+        off = np.empty((self.npairs, k), dtype=np.int64)
+        check(lib.bialign_batch_get_hits(self._h, *(_ptr(x, ctypes.c_int32) for x in (nh, st, start, end, score, tlen)),
+                                         _ptr(buf, ctypes.c_uint8), _ptr(off, ctypes.c_int64)))
+        hits = [[(int(start[p, h]), int(end[p, h]), int(score[p, h]), buf[off[p, h]:off[p, h] + tlen[p, h]].copy())
+                 for h in range(int(nh[p]))] for p in range(self.npairs)]
+        return hits, [_lib.HIT_STATUS[int(x)] for x in st]
+
+    def fit_hit_walks(self):
+        """The search's log: per pair a list of ``(end_b, start_b, score, accepted)``, one entry per walk in the order
+        the walks were made."""
+        _, k, _ = self._need_hits()
+        nw = np.empty(self.npairs, dtype=np.int32)
+        end, start, score, acc = (np.empty((self.npairs, k), dtype=np.int32) for _ in range(4))
+        check(lib.bialign_batch_get_hit_walks(self._h, *(_ptr(x, ctypes.c_int32) for x in (nw, end, start, score, acc))))
+        return [[(int(end[p, w]), int(start[p, w]), int(score[p, w]), bool(acc[p, w])) for w in range(int(nw[p]))]
+                for p in range(self.npairs)]
+
+    def hit_info(self):
+        """bialign_batch_get_hit_info: the spec, the result buffers' bytes, the search kernels' time of the last run."""
+        self._need_hits()
+        hi = _lib.HitInfo()
+        check(lib.bialign_batch_get_hit_info(self._h, ctypes.byref(hi)))
+        return dict(max_hits=hi.spec.max_hits, max_walks=hi.spec.max_walks, min_score=hi.spec.min_score,
+                    buffer_bytes=hi.buffer_bytes, search_ms=hi.search_ms)
 
     def local_spans(self):
         """Local batch: ``(start_a, end_a, start_b, end_b)`` as int32 arrays -- pair p's alignment is that of

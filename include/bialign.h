@@ -436,6 +436,73 @@ int bialign_batch_get_local_spans(const bialign_batch* b, int32_t* start_a, int3
  * batch: BIALIGN_E_INVALID. */
 int bialign_batch_get_overlap_spans(const bialign_batch* b, int32_t* start_a, int32_t* end_a, int32_t* start_b, int32_t* end_b);
 
+/* ---- Hit search (new in ABI 10 as added symbols: no existing struct, function or flag bit changes): every placement of A
+ * in B.  A FIT batch reports the one best placement of a pair; a target often carries the query several times (repeated
+ * domains, tandem hairpins, several binding sites).  Row n of the FIT layers already holds, for every end j, the score of
+ * the best placement that ends there, and FIT's walk already stops at a free start.
+ *   The model.  A full-storage FIT batch may be given a hit search (max_hits, max_walks, min_score).  After each chunk's
+ *   traceback, while its layers are resident, the search computes per pair:
+ *   Profile.  E(j) for j = 0..m, exactly FIT's E.  In the affine recurrence it is the maximum of the nine states at
+ *     (n, j, n, j).  In the one-layer recurrence it is the cell's value.
+ *   Greedy search.  Every end starts as a candidate.  The search repeats the following.
+ *     1. Among unmasked candidates with E(j) >= min_score, take the largest E.  On a tie take the smallest j.  If there is
+ *        none, stop with status EXHAUSTED.
+ *     2. Walk from (n, j, n, j) by FIT's walk rule, with the same start state, tie-breaks and stop rule.  This gives
+ *        start, the trace and complete.  (The one-layer walk is always complete, as in bialign_batch_get_traces.)
+ *     3. The walk's span in B is [start, j).  If the walk is complete and the span intersects no accepted hit's span,
+ *        accept it.  Record (start, end = j, score = E(j), trace).  Mask every end x with start < x <= j, and j itself.
+ *        Otherwise discard it and mask j only.  (Spans [s, e) and [s', e') intersect when s < e' and s' < e.)
+ *     4. Append (end, start, score, accepted) to the pair's walk log, in every case.
+ *     5. Stop with status MAX_HITS when max_hits hits are accepted.  Stop with status MAX_WALKS when max_walks walks are
+ *        made.  (In this order: the walk that accepts hit max_hits as walk max_walks gives MAX_HITS.)
+ *   Consequences.  Hits are disjoint in B.  Their scores do not increase in order of acceptance.  Hit 0 is the batch's own
+ *     alignment, with the same span, score and trace bytes.
+ *   Parameters.  min_score >= 1.  1 <= max_hits <= 256.  max_walks >= max_hits, and 0 means 4 * max_hits. */
+typedef struct bialign_hit_spec {
+  int32_t max_hits;
+  int32_t max_walks;
+  int32_t min_score;
+  int32_t reserved; /* 0 */
+} bialign_hit_spec;
+
+/* status of a pair's search */
+#define BIALIGN_HITS_NOT_SEARCHED 0 /* no run yet, or a BIALIGN_RUN_FILL_ONLY run */
+#define BIALIGN_HITS_EXHAUSTED 1
+#define BIALIGN_HITS_MAX_HITS 2
+#define BIALIGN_HITS_MAX_WALKS 3
+
+typedef struct bialign_hit_info {
+  bialign_hit_spec spec; /* as set, max_walks resolved (0 -> 4 * max_hits) */
+  int64_t buffer_bytes;  /* HBM of the result buffers: profile, walk log, hit records, trace slots (outside hbm_budget_bytes) */
+  double search_ms;      /* HIP-event time of the search kernels of the last run, summed over its chunks (events of their
+                            own: not part of fill_ms or traceback_ms) */
+} bialign_hit_info;
+
+/* Give the batch a hit search (spec != NULL) or take it away again (spec == NULL); after create, ahead of a run.  Allocates
+ * the result buffers for the whole batch: profile (sum of m + 1 words), walk log and hit records ([npairs][max_walks] and
+ * [npairs][max_hits] records of four words), max_hits trace slots of the pair's trace capacity each; the mask of the
+ * candidates and the accepted spans live in the kernel's LDS.  A batch that is not FIT, is SCORE_ONLY, or is a null batch:
+ * BIALIGN_E_UNSUPPORTED (the search needs a FIT batch in full storage).  So it is when the mask (m + 1 bits), the spans and
+ * the tracebacks' staged inputs together pass 160 KiB of LDS.  A bad spec: BIALIGN_E_INVALID.  An allocation that fails:
+ * BIALIGN_E_NOMEM, and the batch stays usable without hits.  Without a search a run enqueues exactly what it did before:
+ * no launch, no event, no allocation.  With one, the results are reset ahead of every run, as the spans are; a
+ * BIALIGN_RUN_FILL_ONLY run leaves the profile and status NOT_SEARCHED, with no hits and no walks. */
+int bialign_batch_set_hits(bialign_batch* b, const bialign_hit_spec* spec);
+/* Pair's profile E(0..m) of the last run.  No search set or no run since: BIALIGN_E_INVALID (so for the getters below). */
+int bialign_batch_get_hit_profile(const bialign_batch* b, int32_t pair, int32_t* out /* [m+1] */);
+/* The accepted hits, in order of acceptance.  nhits and status are [npairs]; start_b, end_b, score and trace_len are
+ * [npairs][max_hits], entries at and beyond nhits[p] are -1; hit h of pair p has its columns at
+ * trace[trace_off[p * max_hits + h] .. + trace_len[p * max_hits + h]), start -> end, in the byte code of
+ * bialign_batch_get_traces: the global alignment of A with B[start_b:end_b].  trace must hold max_hits *
+ * bialign_batch_info.trace_bytes bytes; trace and trace_off may both be NULL. */
+int bialign_batch_get_hits(const bialign_batch* b, int32_t* nhits, int32_t* status, int32_t* start_b, int32_t* end_b,
+                           int32_t* score, int32_t* trace_len, uint8_t* trace, int64_t* trace_off);
+/* The walk log, in the order the walks were made.  nwalks is [npairs]; the others are [npairs][max_walks], -1 at and
+ * beyond nwalks[p].  start_b is where the walk stopped. */
+int bialign_batch_get_hit_walks(const bialign_batch* b, int32_t* nwalks, int32_t* end_b, int32_t* start_b, int32_t* score,
+                                int32_t* accepted);
+int bialign_batch_get_hit_info(const bialign_batch* b, bialign_hit_info* info);
+
 /* Test / introspection hooks.
  * dump_layers re-runs the fill of one pair and writes its layers in the
  * reference's layout [layer][i][j][k-i+s][l-j+s] (pyx:27-41, 61-71), layers in
