@@ -102,15 +102,7 @@ __global__ void __launch_bounds__(64) fit_hits_kernel(const DeviceBatch A, const
     int meets = 0;
     for (int h = c; h < nhits; h += 64) meets |= (start < spans[2 * h + 1] && spans[2 * h] < je) ? 1 : 0;
     const bool accept = how == WALK_COMPLETE && wave_min64(meets ? 0 : 1) != 0;
-    if (accept) {
-      __builtin_amdgcn_s_waitcnt(0);  // lane 0's byte stores before the wave-wide reversal
-      __syncthreads();
-      for (int x = c; x < len / 2; x += 64) {
-        const uint8_t t = out[x];
-        out[x] = out[len - 1 - x];
-        out[len - 1 - x] = t;
-      }
-    }
+    if (accept) reverse_trace(out, len, c);
     // mask start < x <= je and je itself (accepted), or je alone: a lane per mask word
     const int lo = accept ? min(start + 1, je) : je;
     for (int t = (lo >> 5) + c; t <= (je >> 5); t += 64) {

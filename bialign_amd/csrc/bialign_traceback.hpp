@@ -4,7 +4,7 @@
 namespace bialign {
 
 // |U0-V0| + |U1-V1| of a column / state given its two halves (pyx:97, 541-545)
-__device__ __forceinline__ int shift_of(int hU, int hV) {
+__host__ __device__ __forceinline__ int shift_of(int hU, int hV) {
   return hU == hV ? 0 : ((hU == 2 || hV == 2) ? 1 : 2);
 }
 
@@ -90,16 +90,106 @@ __device__ __forceinline__ void free_end_scan(int n, int m, bool a_ends, int lan
 // ---------------------------------------------------------------------------
 // The walk as device functions: start point in, (end point, len, how it ended) out.  A walk stands on lattice point
 // (i, j, k, l) in state st (affine) with layer value cur, running shifts (d0, d1), len columns emitted.  The hit search
-// (bialign_hits.hpp) walks several ends per pair through them.  The two traceback kernels below keep the text of their own
-// loops, of which these are copies line for line: when the kernels called these functions instead, hipcc's code for them
-// changed by more than labels and register numbers (a handful of instructions per kernel, the score-only forms included;
-// DESIGN.md section 7f), and their device code is held fixed.  A change to a rule of the walk is made in both places;
-// tests/test_gpu_fit_hits.py holds hit 0 of every pair to the kernels' trace byte for byte.
+// (bialign_hits.hpp) walks several ends per pair through them, and the traceback kernels below walk one.  The rules of
+// the walk -- the scores of a point, the affine candidates, tie-break and stop rules, free ends, the trace's reversal --
+// are stated here once, and the kernels keep what is theirs (the TraceState of the continuing forms, their cell
+// addressing, staging, publishing).  One copy is left: traceback_linear_kernel holds the text of walk_linear's column
+// loop itself, because it ran slower with the call (DESIGN.md section 7f has the device code and the times).
 // ---------------------------------------------------------------------------
 struct WalkPoint {
   int i, j, k, l, st, cur, d0, d1, len;
 };
 enum : int { WALK_INCOMPLETE = 0, WALK_COMPLETE = 1, WALK_LEFT = 2 };  // LEFT: `leave` said so (STRIP, LEVEL: next round)
+
+// mu1 at (i, j) and mu2 at (k, l), 0 on the lattice's edge: LOOKUP through the staged tables and codes, dense from the
+// pair's tables (D1: dense mu1, and mu2 dense if dense_forms says so; else mu2 dense if the batch has a table).
+struct PointScores {
+  int mu1, mu2;
+};
+template <bool D1>
+__device__ __forceinline__ PointScores point_scores(const DeviceBatch& A, const PairDesc& pd, const TraceInputs& in,
+                                                    const int32_t* mu1tab, int i, int j, int k, int l) {
+  const int m = pd.m;
+  const int mu1 = (i >= 1 && j >= 1)
+                      ? (D1 ? mu1tab[(int64_t)(i - 1) * m + (j - 1)] : in.s1[in.sa[i - 1] * A.k1 + in.sb[j - 1]])
+                      : 0;
+  const int mu2 = (k >= 1 && l >= 1)
+                      ? ((D1 ? (A.dense_forms & 1) != 0 : A.dense_tab != nullptr)
+                             ? A.dense_tab[pd.tab_off + (int64_t)(k - 1) * m + (l - 1)]
+                             : in.s2[in.ca[k - 1] * A.k2 + in.cb[l - 1]])
+                      : 0;
+  return PointScores{mu1, mu2};
+}
+
+// Candidate c < 15 of a point in state st (pyx:84-131, the generator's order of pyx:275-296): its offset (o0..o3), source
+// state ss, score sc given the point's mu1 / mu2, and what offset and source state add to the running shifts for the
+// look-ahead of pyx:554-565.  Host code too: tests/trace_fast_check.hip holds the short-chain kernel's table against it.
+struct AffineCandidate {
+  int o0, o1, o2, o3, ss, sc, inc0, inc1;
+};
+__host__ __device__ __forceinline__ AffineCandidate affine_candidate(int st, int c, int beta, int gamma, int delta, int mu1, int mu2) {
+  // lane-constant part of the candidate: its group (full, structure-only, sequence-only offset) and, for groups 2/3,
+  // the free half h.  The groups are predicates of c, not a number: a number stays live in the kernels' column loop.
+  const bool grp1 = c < 9, grp2 = c >= 9 && c < 12, grp3 = c >= 12;
+  const int hfree = grp2 ? 2 - (c - 9) : 2 - (c - 12);  // h = M, X, Y in the generator's order
+  const int hU = st / 3, hV = st - 3 * hU;
+  const int u0 = hU >= 1, u1 = hU != 1, v0 = hV >= 1, v1 = hV != 1;
+  const int valU = hU == 2 ? mu1 : gamma, valV = hV == 2 ? mu2 : gamma;
+  AffineCandidate g;
+  g.o0 = grp2 ? 0 : u0, g.o1 = grp2 ? 0 : u1;
+  g.o2 = grp3 ? 0 : v0, g.o3 = grp3 ? 0 : v1;
+  g.ss = grp1 ? c : (grp2 ? 3 * hU + hfree : 3 * hfree + hV);
+  const int ra = g.ss / 3, rb = g.ss - 3 * ra;
+  const int openU = (hU != 2 && ra != hU) ? beta : 0, openV = (hV != 2 && rb != hV) ? beta : 0;
+  g.sc = grp1   ? delta * shift_of(hU, hV) + valU + valV + openU + openV
+         : grp2 ? delta * (v0 + v1) + valV + openV
+                : delta * (u0 + u1) + valU + openU;
+  const int r0 = ra >= 1, r1 = ra != 1, r2 = rb >= 1, r3 = rb != 1;
+  g.inc0 = (g.o0 - g.o2) + (r0 - r2), g.inc1 = (g.o1 - g.o3) + (r1 - r3);
+  return g;
+}
+
+// Start of a walk in the free-end modes: the end local_finish_kernel decoded (LOCAL), or the best end cell by
+// free_end_scan over end_value(i, j), the kernel's best layer value at (i, j, i, j) (FIT, OVERLAP); the spans are set to
+// (start -1, the end) in the mode's layout.  A global batch leaves (*end_a, *end_b) alone.
+template <typename EndValue>
+__device__ __forceinline__ void free_end_start(const DeviceBatch& A, int pid, int n, int m, bool fit, bool ovl, bool local, int c,
+                                               EndValue&& end_value, int* end_a, int* end_b) {
+  if (local) {
+    *end_a = A.local_span[4 * (int64_t)pid + 1];
+    *end_b = A.local_span[4 * (int64_t)pid + 3];
+  }
+  if (fit) {
+    free_end_scan(n, m, ovl, c, end_value, end_a, end_b);
+    if (c == 0 && !ovl) {
+      A.fit_span[2 * pid] = -1;
+      A.fit_span[2 * pid + 1] = *end_b;
+    }
+    if (c == 0 && ovl) {  // (start_a, end_a, start_b, end_b), as local_finish_kernel leaves them
+      int32_t* span = A.local_span + 4 * (int64_t)pid;
+      span[0] = -1, span[1] = *end_a, span[2] = -1, span[3] = *end_b;
+    }
+  }
+}
+// ... and its other end: a complete walk that stopped on the free start (i, j, i, j) publishes it (one lane calls this).
+// One test per mode: `ovl || local` is a third flag that lives through the column loop, two SGPRs that take the packed
+// affine kernels from 100 to 102 and so from eight waves to seven.
+__device__ __forceinline__ void publish_free_starts(const DeviceBatch& A, int pid, bool fit, bool ovl, bool local, int i, int j) {
+  if (fit && !ovl) A.fit_span[2 * pid] = j;
+  if (ovl) A.local_span[4 * (int64_t)pid] = i, A.local_span[4 * (int64_t)pid + 2] = j;
+  if (local) A.local_span[4 * (int64_t)pid] = i, A.local_span[4 * (int64_t)pid + 2] = j;
+}
+
+// pyx:586 reversed: lane 0 stored the columns end -> start; the wave swaps them into start -> end order in place
+__device__ __forceinline__ void reverse_trace(uint8_t* out, int len, int c) {
+  __builtin_amdgcn_s_waitcnt(0);  // lane 0's byte stores before the wave-wide reversal
+  __syncthreads();
+  for (int x = c; x < len / 2; x += 64) {
+    const uint8_t t = out[x];
+    out[x] = out[len - 1 - x];
+    out[len - 1 - x] = t;
+  }
+}
 
 // pyx:573-582: the best end layer at (i, j, i, j), and the first state with the least shift that attains it
 template <typename Cell>
@@ -119,54 +209,29 @@ __device__ __forceinline__ int walk_affine(const DeviceBatch& A, const PairDesc&
                                            int SR, int c, bool fit, bool ovl, bool local, Cell&& cell, Leave&& leave,
                                            uint8_t* out, int cap, WalkPoint& w) {
   constexpr int BIG = 0x7fffffff;
-  const int m = pd.m;
   const int beta = A.beta, gamma = A.gamma, delta = A.delta;
-  const uint8_t *sa = in.sa, *ca = in.ca, *sb = in.sb, *cb = in.cb;
   int i = w.i, j = w.j, k = w.k, l = w.l, st = w.st, cur = w.cur, d0 = w.d0, d1 = w.d1, len = w.len;
   int how = WALK_INCOMPLETE;
-  // lane-constant part of the candidate: its group and, for groups 2/3, the free half h
-  const int grp = c < 9 ? 1 : (c < 12 ? 2 : 3);
-  const int hfree = grp == 2 ? 2 - (c - 9) : 2 - (c - 12);  // h = M, X, Y in the generator's order
   while (true) {
     if (i == 0 && j == 0 && k == 0 && l == 0 && st == 8) { how = WALK_COMPLETE; break; }
     if (fit && i == 0 && k == 0 && j == l && st == 8 && cur == 0) { how = WALK_COMPLETE; break; }  // fit: a free start, start_b = j
     if (ovl && j == 0 && l == 0 && i == k && st == 8 && cur == 0) { how = WALK_COMPLETE; break; }  // overlap: and on column 0, start_a = i
     if (local && i == k && j == l && st == 8 && cur == 0) { how = WALK_COMPLETE; break; }  // local: a free start, (start_a, start_b) = (i, j)
     if (leave(i, j, k, l)) { how = WALK_LEFT; break; }
-    const int hU = st / 3, hV = st - 3 * hU;
-    const int u0 = hU >= 1, u1 = hU != 1, v0 = hV >= 1, v1 = hV != 1;
-    const int mu1 = (i >= 1 && j >= 1)
-                        ? (D1 ? mu1tab[(int64_t)(i - 1) * m + (j - 1)] : in.s1[sa[i - 1] * A.k1 + sb[j - 1]])
-                        : 0;
-    const int mu2 = (k >= 1 && l >= 1)
-                        ? ((D1 ? (A.dense_forms & 1) != 0 : A.dense_tab != nullptr)
-                               ? A.dense_tab[pd.tab_off + (int64_t)(k - 1) * m + (l - 1)]
-                               : in.s2[ca[k - 1] * A.k2 + cb[l - 1]])
-                        : 0;
-    const int valU = hU == 2 ? mu1 : gamma, valV = hV == 2 ? mu2 : gamma;
-
-    // this lane's candidate: offset, source state, score (pyx:84-131)
-    const int o0 = grp == 2 ? 0 : u0, o1 = grp == 2 ? 0 : u1;
-    const int o2 = grp == 3 ? 0 : v0, o3 = grp == 3 ? 0 : v1;
-    const int ss = grp == 1 ? c : (grp == 2 ? 3 * hU + hfree : 3 * hfree + hV);
-    const int ra = ss / 3, rb = ss - 3 * ra;
-    const int openU = (hU != 2 && ra != hU) ? beta : 0, openV = (hV != 2 && rb != hV) ? beta : 0;
-    const int sc = grp == 1   ? delta * shift_of(hU, hV) + valU + valV + openU + openV
-                   : grp == 2 ? delta * (v0 + v1) + valV + openV
-                              : delta * (u0 + u1) + valU + openU;
-    const int pi = i - o0, pj = j - o1, pk = k - o2, pl = l - o3;
+    const PointScores mu = point_scores<D1>(A, pd, in, mu1tab, i, j, k, l);
+    const AffineCandidate g = affine_candidate(st, c, beta, gamma, delta, mu.mu1, mu.mu2);  // this lane's candidate
+    const int pi = i - g.o0, pj = j - g.o1, pk = k - g.o2, pl = l - g.o3;
     const bool ok = c < 15 && pi >= 0 && pj >= 0 && pk >= 0 && pl >= 0 && abs(pk - pi) <= SR &&
                     abs(pl - pj) <= SR;  // pyx:133-141
-    const int ld = ok ? cell(pi, pj, pk - pi + SR, pl - pj + SR, ss) : 0;
+    const int ld = ok ? cell(pi, pj, pk - pi + SR, pl - pj + SR, g.ss) : 0;
     // pyx:554-565: cases reproducing the cell; look-ahead adds the offset AND the source state
-    const int r0 = ra >= 1, r1 = ra != 1, r2 = rb >= 1, r3 = rb != 1;
-    const int t0 = d0 + (o0 - o2) + (r0 - r2), t1 = d1 + (o1 - o3) + (r1 - r3);
-    const int key = (ok && ld + sc == cur) ? ((abs(t0) + abs(t1)) << 16 | abs(t1) << 8 | c) : BIG;
+    const int t0 = d0 + g.inc0, t1 = d1 + g.inc1;
+    const int key = (ok && ld + g.sc == cur) ? ((abs(t0) + abs(t1)) << 16 | abs(t1) << 8 | c) : BIG;
     const int kmin = __builtin_amdgcn_readfirstlane(wave_min16(key));
     if (kmin == BIG) break;  // pyx:570-571 -> "incomplete traceback"
     const int pick = kmin & 63;
-    const int code = __builtin_amdgcn_readlane(o0 * 8 + o1 * 4 + o2 * 2 + o3, pick);
-    st = __builtin_amdgcn_readlane(ss, pick);
+    const int code = __builtin_amdgcn_readlane(g.o0 * 8 + g.o1 * 4 + g.o2 * 2 + g.o3, pick);
+    st = __builtin_amdgcn_readlane(g.ss, pick);
     cur = __builtin_amdgcn_readlane(ld, pick);
     const int q0 = (code >> 3) & 1, q1 = (code >> 2) & 1, q2 = (code >> 1) & 1, q3 = code & 1;
     d0 += q0 - q2;  // pyx:566: only the offset moves the running shift
@@ -180,15 +245,14 @@ __device__ __forceinline__ int walk_affine(const DeviceBatch& A, const PairDesc&
 }
 
 // Non-affine walk (pyx:513-531): lane c < 13 = case c; it ends, complete, when no case reproduces the cell (the origin)
-// or on a free start.  w.st, w.d0 and w.d1 are unused.
+// or on a free start.  w.st, w.d0 and w.d1 are unused.  The hit search calls it; traceback_linear_kernel states the same
+// loop in its own body (see there), so a change to a rule here is made there too.
 template <bool D1, typename Cell, typename Leave>
 __device__ __forceinline__ int walk_linear(const DeviceBatch& A, const PairDesc& pd, const TraceInputs& in, const int32_t* mu1tab,
                                            int SR, int c, bool fit, bool ovl, bool local, Cell&& cell, Leave&& leave,
                                            uint8_t* out, int cap, WalkPoint& w) {
   constexpr int BIG = 0x7fffffff;
-  const int m = pd.m;
   const int gamma = A.gamma, delta = A.delta;
-  const uint8_t *sa = in.sa, *ca = in.ca, *sb = in.sb, *cb = in.cb;
   // offsets of the thirteen cases as bit masks o0*8+o1*4+o2*2+o3 (pyx:233-248), per lane
   constexpr int OFF[16] = {15, 10, 5, 12, 3, 8, 4, 2, 1, 11, 7, 14, 13, 0, 0, 0};
   int code_c = 0;
@@ -208,15 +272,8 @@ __device__ __forceinline__ int walk_linear(const DeviceBatch& A, const PairDesc&
     if (ovl && j == 0 && l == 0 && i == k && cur == 0) break;  // overlap: and on column 0, start_a = i
     if (local && i == k && j == l && cur == 0) break;          // local: a free start, (start_a, start_b) = (i, j)
     if (leave(i, j, k, l)) { how = WALK_LEFT; break; }
-    const int mu1 = (i >= 1 && j >= 1)
-                        ? (D1 ? mu1tab[(int64_t)(i - 1) * m + (j - 1)] : in.s1[sa[i - 1] * A.k1 + sb[j - 1]])
-                        : 0;
-    const int mu2 = (k >= 1 && l >= 1)
-                        ? ((D1 ? (A.dense_forms & 1) != 0 : A.dense_tab != nullptr)
-                               ? A.dense_tab[pd.tab_off + (int64_t)(k - 1) * m + (l - 1)]
-                               : in.s2[ca[k - 1] * A.k2 + cb[l - 1]])
-                        : 0;
-    const int sc = kconst + (use1 ? mu1 : 0) + (use2 ? mu2 : 0);
+    const PointScores mu = point_scores<D1>(A, pd, in, mu1tab, i, j, k, l);
+    const int sc = kconst + (use1 ? mu.mu1 : 0) + (use2 ? mu.mu2 : 0);
     const int pi = i - o0, pj = j - o1, pk = k - o2, pl = l - o3;
     const bool ok = c < 13 && pi >= 0 && pj >= 0 && pk >= 0 && pl >= 0 && abs(pk - pi) <= SR && abs(pl - pj) <= SR;
     const int ld = ok ? cell(pi, pj, pk - pi + SR, pl - pj + SR) : 0;
@@ -254,10 +311,8 @@ __global__ void __launch_bounds__(64) traceback_affine_kernel(const DeviceBatch 
   const int pid = A.order[blockIdx.x];
   const PairDesc pd = A.pairs[pid];
   const int n = pd.n, m = pd.m;
-  const int beta = A.beta, gamma = A.gamma, delta = A.delta;
   const int32_t* lay = A.layers;
   const int c = threadIdx.x;  // candidate lane
-  constexpr int BIG = 0x7fffffff;
   constexpr int W = 2 * S + 1, RR = Geo<S>::RR;
   extern __shared__ __align__(16) int32_t smem[];
 
@@ -288,127 +343,47 @@ __global__ void __launch_bounds__(64) traceback_affine_kernel(const DeviceBatch 
     return lay[pd.layer_off + Rec<S, 9, true>::dword((int64_t)sp * pd.P + pj + 2 * ilp + a, a, b * 9 + ss)];
   };
 
-  int i = n, j = m, k = n, l = m, d0 = 0, d1 = 0, len = 0, complete = 0;
-  int st = 0, cur = 0;
   constexpr bool FIT_FORM = !STRIP && !WIDE && !LEVEL;  // fit alignments: the tiled full-storage forms
   const bool fit = FIT_FORM && A.fit;
   const bool ovl = fit && (A.fit & FREE_A_ENDS);  // overlap alignments: A's end gaps are free as well
   const bool local = FIT_FORM && A.local;  // local alignments: the same forms
+  WalkPoint w{n, m, n, m, 0, 0, 0, 0, 0};
   if (!(STRIP || LEVEL) || !ts.started) {
-    if (local) {  // the walk starts at the end local_finish_kernel decoded: (end_a, end_b, end_a, end_b)
-      i = k = A.local_span[4 * (int64_t)pid + 1];
-      j = l = A.local_span[4 * (int64_t)pid + 3];
-    }
-    if (fit) {  // the walk starts at the best end cell: (n, end_b, n, end_b), or (overlap) also (end_a, m, end_a, m)
-      int ea, eb;
-      free_end_scan(n, m, ovl, c, [&](int pi, int pj) {
-        int e = cell(pi, pj, SR, SR, 0);
-        for (int q = 1; q < 9; ++q) e = max(e, cell(pi, pj, SR, SR, q));
-        return e;
-      }, &ea, &eb);
-      i = k = ea;
-      j = l = eb;
-      if (c == 0 && !ovl) {
-        A.fit_span[2 * pid] = -1;
-        A.fit_span[2 * pid + 1] = eb;
-      }
-      if (c == 0 && ovl) {  // (start_a, end_a, start_b, end_b), as local_finish_kernel leaves them
-        int32_t* span = A.local_span + 4 * (int64_t)pid;
-        span[0] = -1, span[1] = ea, span[2] = -1, span[3] = eb;
-      }
-    }
-    // pyx:573-582: best end layer, first one with the least shift
-    const int endv = c < 9 ? cell(i, j, SR, SR, c) : -BIG;
-    const int best = __builtin_amdgcn_readfirstlane(-wave_min16(-endv));
-    if (c == 0) A.scores[pid] = best;
+    free_end_start(A, pid, n, m, fit, ovl, local, c, [&](int pi, int pj) {
+      int e = cell(pi, pj, SR, SR, 0);
+      for (int q = 1; q < 9; ++q) e = max(e, cell(pi, pj, SR, SR, q));
+      return e;
+    }, &w.i, &w.j);
+    w.k = w.i, w.l = w.j;
+    affine_end_state(cell, w.i, w.j, SR, c, &w.cur, &w.st);
+    if (c == 0) A.scores[pid] = w.cur;
     if (!DO_TRACE) return;
-    const int skey = (c < 9 && endv == best) ? (shift_of(c / 3, c % 3) << 4 | c) : BIG;
-    st = __builtin_amdgcn_readfirstlane(wave_min16(skey)) & 15;
-    cur = best;
   } else {
-    i = ts.i; j = ts.j; k = ts.k; l = ts.l; st = ts.st; cur = ts.cur; d0 = ts.d0; d1 = ts.d1; len = ts.len;
+    w = WalkPoint{ts.i, ts.j, ts.k, ts.l, ts.st, ts.cur, ts.d0, ts.d1, ts.len};
   }
   const TraceInputs in = stage_trace_inputs<D1>(A, pd, smem);
-  const uint8_t *sa = in.sa, *ca = in.ca, *sb = in.sb, *cb = in.cb;
   const int32_t* const mu1tab = D1 ? mu1_table(A, pd) : nullptr;
 
   uint8_t* out = A.trace + pd.trace_off;
-  bool finished = true;  // STRIP: false when the walk merely left this strip
-  // lane-constant part of the candidate: its group and, for groups 2/3, the free half h
-  const int grp = c < 9 ? 1 : (c < 12 ? 2 : 3);
-  const int hfree = grp == 2 ? 2 - (c - 9) : 2 - (c - 12);  // h = M, X, Y in the generator's order
-  while (true) {
-    if (i == 0 && j == 0 && k == 0 && l == 0 && st == 8) { complete = 1; break; }
-    if (fit && i == 0 && k == 0 && j == l && st == 8 && cur == 0) { complete = 1; break; }  // fit: a free start, start_b = j
-    if (ovl && j == 0 && l == 0 && i == k && st == 8 && cur == 0) { complete = 1; break; }  // overlap: and on column 0, start_a = i
-    if (local && i == k && j == l && st == 8 && cur == 0) { complete = 1; break; }  // local: a free start, (start_a, start_b) = (i, j)
-    if (STRIP && i < Qlo * RR) { finished = false; break; }  // above the re-swept strips: next round
-    if (LEVEL && seg > 0 && i + j + k + l < seg_base + WIDE_SEG_OVERLAP) { finished = false; break; }  // a candidate may lie below the scratch
-    const int hU = st / 3, hV = st - 3 * hU;
-    const int u0 = hU >= 1, u1 = hU != 1, v0 = hV >= 1, v1 = hV != 1;
-    const int mu1 = (i >= 1 && j >= 1)
-                        ? (D1 ? mu1tab[(int64_t)(i - 1) * m + (j - 1)] : in.s1[sa[i - 1] * A.k1 + sb[j - 1]])
-                        : 0;
-    const int mu2 = (k >= 1 && l >= 1)
-                        ? ((D1 ? (A.dense_forms & 1) != 0 : A.dense_tab != nullptr)
-                               ? A.dense_tab[pd.tab_off + (int64_t)(k - 1) * m + (l - 1)]
-                               : in.s2[ca[k - 1] * A.k2 + cb[l - 1]])
-                        : 0;
-    const int valU = hU == 2 ? mu1 : gamma, valV = hV == 2 ? mu2 : gamma;
-
-    // this lane's candidate: offset, source state, score (pyx:84-131)
-    const int o0 = grp == 2 ? 0 : u0, o1 = grp == 2 ? 0 : u1;
-    const int o2 = grp == 3 ? 0 : v0, o3 = grp == 3 ? 0 : v1;
-    const int ss = grp == 1 ? c : (grp == 2 ? 3 * hU + hfree : 3 * hfree + hV);
-    const int ra = ss / 3, rb = ss - 3 * ra;
-    const int openU = (hU != 2 && ra != hU) ? beta : 0, openV = (hV != 2 && rb != hV) ? beta : 0;
-    const int sc = grp == 1   ? delta * shift_of(hU, hV) + valU + valV + openU + openV
-                   : grp == 2 ? delta * (v0 + v1) + valV + openV
-                              : delta * (u0 + u1) + valU + openU;
-    const int pi = i - o0, pj = j - o1, pk = k - o2, pl = l - o3;
-    const bool ok = c < 15 && pi >= 0 && pj >= 0 && pk >= 0 && pl >= 0 && abs(pk - pi) <= SR &&
-                    abs(pl - pj) <= SR;  // pyx:133-141
-    const int ld = ok ? cell(pi, pj, pk - pi + SR, pl - pj + SR, ss) : 0;
-    // pyx:554-565: cases reproducing the cell; look-ahead adds the offset AND the source state
-    const int r0 = ra >= 1, r1 = ra != 1, r2 = rb >= 1, r3 = rb != 1;
-    const int t0 = d0 + (o0 - o2) + (r0 - r2), t1 = d1 + (o1 - o3) + (r1 - r3);
-    const int key = (ok && ld + sc == cur) ? ((abs(t0) + abs(t1)) << 16 | abs(t1) << 8 | c) : BIG;
-    const int kmin = __builtin_amdgcn_readfirstlane(wave_min16(key));
-    if (kmin == BIG) break;  // pyx:570-571 -> "incomplete traceback"
-    const int pick = kmin & 63;
-    const int code = __builtin_amdgcn_readlane(o0 * 8 + o1 * 4 + o2 * 2 + o3, pick);
-    st = __builtin_amdgcn_readlane(ss, pick);
-    cur = __builtin_amdgcn_readlane(ld, pick);
-    const int q0 = (code >> 3) & 1, q1 = (code >> 2) & 1, q2 = (code >> 1) & 1, q3 = code & 1;
-    d0 += q0 - q2;  // pyx:566: only the offset moves the running shift
-    d1 += q1 - q3;
-    if (c == 0 && len < pd.trace_cap) out[len] = (uint8_t)code;
-    ++len;
-    i -= q0; j -= q1; k -= q2; l -= q3;
-  }
-  if ((STRIP || LEVEL) && !finished) {  // hand over to the next round
+  const int how = walk_affine<D1>(A, pd, in, mu1tab, SR, c, fit, ovl, local, cell, [&](int i, int j, int k, int l) {
+    return (STRIP && i < Qlo * RR) ||  // above the re-swept strips: next round
+           (LEVEL && seg > 0 && i + j + k + l < seg_base + WIDE_SEG_OVERLAP);  // a candidate may lie below the scratch
+  }, out, pd.trace_cap, w);
+  if (how == WALK_LEFT) {  // hand over to the next round
     if (c == 0) {
       TraceState nx;
-      nx.i = i; nx.j = j; nx.k = k; nx.l = l; nx.st = st; nx.cur = cur; nx.d0 = d0; nx.d1 = d1;
-      nx.len = len; nx.strip = LEVEL ? seg - 1 : Qlo - 1; nx.started = 1; nx.done = 0;
+      nx.i = w.i; nx.j = w.j; nx.k = w.k; nx.l = w.l; nx.st = w.st; nx.cur = w.cur; nx.d0 = w.d0; nx.d1 = w.d1;
+      nx.len = w.len; nx.strip = LEVEL ? seg - 1 : Qlo - 1; nx.started = 1; nx.done = 0;
       A.tstate[pid] = nx;
     }
     return;
   }
-  if (len > pd.trace_cap) len = pd.trace_cap;
-  __builtin_amdgcn_s_waitcnt(0);  // lane 0's byte stores before the wave-wide reversal
-  __syncthreads();
-  for (int x = c; x < len / 2; x += 64) {  // pyx:586 reversed
-    const uint8_t t = out[x];
-    out[x] = out[len - 1 - x];
-    out[len - 1 - x] = t;
-  }
+  const int len = min(w.len, pd.trace_cap);
+  reverse_trace(out, len, c);
   if (c == 0) {
     A.trace_len[pid] = len;
-    A.complete[pid] = complete;
-    if (fit && !ovl && complete) A.fit_span[2 * pid] = j;
-    if (ovl && complete) A.local_span[4 * (int64_t)pid] = i, A.local_span[4 * (int64_t)pid + 2] = j;
-    if (local && complete) A.local_span[4 * (int64_t)pid] = i, A.local_span[4 * (int64_t)pid + 2] = j;
+    A.complete[pid] = how == WALK_COMPLETE;
+    if (how == WALK_COMPLETE) publish_free_starts(A, pid, fit, ovl, local, w.i, w.j);
     if (STRIP || LEVEL) {
       ts.done = 1;
       ts.started = 1;
@@ -429,10 +404,8 @@ __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch 
   const int pid = A.order[blockIdx.x];
   const PairDesc pd = A.pairs[pid];
   const int n = pd.n, m = pd.m;
-  const int gamma = A.gamma, delta = A.delta;
   const int32_t* lay = A.layers;
   const int c = threadIdx.x;
-  constexpr int BIG = 0x7fffffff;
   constexpr int W = 2 * S + 1, RR = Geo<S>::RR;
   extern __shared__ __align__(16) int32_t smem[];
   TraceState ts{};
@@ -460,29 +433,25 @@ __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch 
   const bool fit = FIT_FORM && A.fit;
   const bool ovl = fit && (A.fit & FREE_A_ENDS);  // overlap alignments: A's end gaps are free as well
   const bool local = FIT_FORM && A.local;  // local alignments: the same forms
-  int iend = n, jend = m;
-  if (local) {  // the walk starts at the end local_finish_kernel decoded: (end_a, end_b, end_a, end_b)
-    iend = A.local_span[4 * (int64_t)pid + 1];
-    jend = A.local_span[4 * (int64_t)pid + 3];
+  WalkPoint w{n, m, n, m, 0, 0, 0, 0, 0};
+  if (CONT && ts.started) {
+    w.i = ts.i; w.j = ts.j; w.k = ts.k; w.l = ts.l; w.cur = ts.cur; w.len = ts.len;
+  } else {
+    free_end_start(A, pid, n, m, fit, ovl, local, c, [&](int pi, int pj) { return cell(pi, pj, SR, SR); }, &w.i, &w.j);
+    w.k = w.i, w.l = w.j;
+    w.cur = cell(w.i, w.j, SR, SR);
+    if (c == 0) A.scores[pid] = w.cur;  // pyx:471
   }
-  if (fit) {  // the walk starts at the best end cell: (n, end_b, n, end_b), or (overlap) also (end_a, m, end_a, m)
-    free_end_scan(n, m, ovl, c, [&](int pi, int pj) { return cell(pi, pj, SR, SR); }, &iend, &jend);
-    if (c == 0 && !ovl) {
-      A.fit_span[2 * pid] = -1;
-      A.fit_span[2 * pid + 1] = jend;
-    }
-    if (c == 0 && ovl) {  // (start_a, end_a, start_b, end_b), as local_finish_kernel leaves them
-      int32_t* span = A.local_span + 4 * (int64_t)pid;
-      span[0] = -1, span[1] = iend, span[2] = -1, span[3] = jend;
-    }
-  }
-  int cur = (CONT && ts.started) ? ts.cur : cell(iend, jend, SR, SR);
-  if (c == 0 && !(CONT && ts.started)) A.scores[pid] = cur;  // pyx:471
   if (!DO_TRACE) return;
   const TraceInputs in = stage_trace_inputs<D1>(A, pd, smem);
-  const uint8_t *sa = in.sa, *ca = in.ca, *sb = in.sb, *cb = in.cb;
   const int32_t* const mu1tab = D1 ? mu1_table(A, pd) : nullptr;
 
+  uint8_t* out = A.trace + pd.trace_off;
+  // The column loop is walk_linear's, stated here a second time: with the call in its place the 1024 x 1024 one-layer
+  // batch walked 2 % slower than the parent's kernel on the device, with this text it does not.
+  // A change to a rule of the one-layer walk is made in both.
+  constexpr int BIG = 0x7fffffff;
+  const int gamma = A.gamma, delta = A.delta;
   // offsets of the thirteen cases as bit masks o0*8+o1*4+o2*2+o3 (pyx:233-248), per lane
   constexpr int OFF[16] = {15, 10, 5, 12, 3, 8, 4, 2, 1, 11, 7, 14, 13, 0, 0, 0};
   int code_c = 0;
@@ -494,26 +463,16 @@ __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch 
   const int use1 = (c == 0 || c == 3 || c == 11 || c == 12), use2 = (c == 0 || c == 4 || c == 9 || c == 10);
   const int gD = gamma + delta;
   const int kconst = c == 0 ? 0 : (c <= 2 ? 2 * gamma : (c <= 4 ? delta : gD));
-
-  uint8_t* out = A.trace + pd.trace_off;
-  int i = iend, j = jend, k = iend, l = jend, len = 0;
-  if (CONT && ts.started) { i = ts.i; j = ts.j; k = ts.k; l = ts.l; len = ts.len; }
+  int i = w.i, j = w.j, k = w.k, l = w.l, cur = w.cur, len = w.len;
   bool finished = true;
   while (true) {
     if (fit && i == 0 && k == 0 && j == l && cur == 0) break;  // fit: a free start, start_b = j
     if (ovl && j == 0 && l == 0 && i == k && cur == 0) break;  // overlap: and on column 0, start_a = i
     if (local && i == k && j == l && cur == 0) break;          // local: a free start, (start_a, start_b) = (i, j)
-    if (STRIP && i < Qlo * RR) { finished = false; break; }
+    if (STRIP && i < Qlo * RR) { finished = false; break; }  // above the re-swept strips: next round
     if (LEVEL && seg > 0 && i + j + k + l < seg_base + WIDE_SEG_OVERLAP) { finished = false; break; }
-    const int mu1 = (i >= 1 && j >= 1)
-                        ? (D1 ? mu1tab[(int64_t)(i - 1) * m + (j - 1)] : in.s1[sa[i - 1] * A.k1 + sb[j - 1]])
-                        : 0;
-    const int mu2 = (k >= 1 && l >= 1)
-                        ? ((D1 ? (A.dense_forms & 1) != 0 : A.dense_tab != nullptr)
-                               ? A.dense_tab[pd.tab_off + (int64_t)(k - 1) * m + (l - 1)]
-                               : in.s2[ca[k - 1] * A.k2 + cb[l - 1]])
-                        : 0;
-    const int sc = kconst + (use1 ? mu1 : 0) + (use2 ? mu2 : 0);
+    const PointScores mu = point_scores<D1>(A, pd, in, mu1tab, i, j, k, l);
+    const int sc = kconst + (use1 ? mu.mu1 : 0) + (use2 ? mu.mu2 : 0);
     const int pi = i - o0, pj = j - o1, pk = k - o2, pl = l - o3;
     const bool ok = c < 13 && pi >= 0 && pj >= 0 && pk >= 0 && pl >= 0 && abs(pk - pi) <= SR && abs(pl - pj) <= SR;
     const int ld = ok ? cell(pi, pj, pk - pi + SR, pl - pj + SR) : 0;
@@ -526,7 +485,7 @@ __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch 
     ++len;
     i -= (code >> 3) & 1; j -= (code >> 2) & 1; k -= (code >> 1) & 1; l -= code & 1;
   }
-  if (CONT && !finished) {
+  if (CONT && !finished) {  // hand over to the next round
     if (c == 0) {
       TraceState nx{};
       nx.i = i; nx.j = j; nx.k = k; nx.l = l; nx.cur = cur; nx.len = len;
@@ -536,19 +495,11 @@ __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch 
     return;
   }
   if (len > pd.trace_cap) len = pd.trace_cap;
-  __builtin_amdgcn_s_waitcnt(0);
-  __syncthreads();
-  for (int x = c; x < len / 2; x += 64) {
-    const uint8_t t = out[x];
-    out[x] = out[len - 1 - x];
-    out[len - 1 - x] = t;
-  }
+  reverse_trace(out, len, c);
   if (c == 0) {
     A.trace_len[pid] = len;
     A.complete[pid] = 1;
-    if (fit && !ovl) A.fit_span[2 * pid] = j;
-    if (ovl) A.local_span[4 * (int64_t)pid] = i, A.local_span[4 * (int64_t)pid + 2] = j;
-    if (local) A.local_span[4 * (int64_t)pid] = i, A.local_span[4 * (int64_t)pid + 2] = j;
+    publish_free_starts(A, pid, fit, ovl, local, i, j);
     if (CONT) {
       ts.done = 1;
       ts.started = 1;

@@ -91,7 +91,11 @@ def same_results(got, base):
 
 def check_against_oracle(got, spec, wants, pairs=None, params=None, affine=None):
     """Every pair: the profile is the oracle's, the log replays, hit 0 is the batch's own alignment, and (``pairs`` given:
-    LOOKUP scores) every hit's trace, re-scored on B[start:end], gives its score."""
+    LOOKUP scores) every hit's trace, re-scored on B[start:end], gives its score.  (Affine: search and traceback kernel
+    call one walk, walk_affine, so hit 0's comparison holds the search's end choice and start state to the kernel's.
+    One-layer: traceback_linear_kernel keeps a copy of walk_linear's column loop, and hit 0 == the batch's trace is what
+    ties that copy to the function the search calls.  The walks' rules themselves are held to the oracle by the traces of
+    tests/test_gpu_fit.py and the other modes' tests.)"""
     start, end = got["spans"]
     traces, complete = got["traces"]
     if pairs is not None:

@@ -88,6 +88,31 @@ def test_one_layer_recurrence(s, k, monkeypatch):
     same(pairs, dict(synth.PROTEIN_PARAMS, max_shift=s, **LIN))
 
 
+@pytest.mark.parametrize("ov", [{}, LIN], ids=["affine", "one-layer"])
+def test_three_strips_one_per_round_against_the_oracle(ov, monkeypatch):
+    """51 rows at max_shift 1 are three strips of 20, and BIALIGN_RESW_K=1 re-sweeps one per round: the walk leaves a strip
+    twice and goes on from the pair's TraceState each time.  Score, trace and completeness flag equal the oracle's.
+    That one strip at a time is in the scratch shows in the batch's memory: a pair's region is its LEAN records plus
+    BIALIGN_RESW_K strips of scratch, so it grows from K = 1 to 2 and again to 3 -- and with one strip of scratch the
+    pair's three strips take three rounds."""
+    from bialign_amd.batch import make_batch
+    from bialign_amd.engine import trace_codes_to_columns
+    from oracle import oracle
+    pair, params = synth.protein_pair(1980, 50, 44), dict(synth.PROTEIN_PARAMS, max_shift=1, **ov)
+    size = {}
+    for k in ("3", "2", "1"):
+        monkeypatch.setenv("BIALIGN_RESW_K", k)
+        b = make_batch([pair], params, lean_trace=True)
+        size[k] = b.info["hbm_layer_bytes"]
+        b.close()
+    assert size["1"] < size["2"] < size["3"]   # the last batch made, K = 1, has the least scratch: one strip
+    got = run([pair], params, lean_trace=True)
+    ref = oracle.solve(*pair, params)
+    assert int(got[0][0]) == ref["score"]
+    assert trace_codes_to_columns(np.array(got[1][0], dtype=np.uint8)) == oracle.trace_to_lists(ref["trace"])
+    assert got[2][0] == bool(ref["complete"])
+
+
 def test_one_layer_dense_and_golden():
     rng = np.random.default_rng(10)
     shapes = [(130, 75), (75, 130), (300, 280)]

@@ -1,7 +1,7 @@
 // Host-side proof for the affine traceback's short-chain kernel (bialign_trace_fast.hpp), from the kernels' own headers.
 // Stand-alone program (tests/test_trace_fast_host.py compiles and runs it, host code only).  Per shape it checks
-//   1. every entry of the candidate table against the generic kernel's per-column expressions (copied below from
-//      traceback_affine_kernel): offset code, source state, score for arbitrary mu1 / mu2, look-ahead, band-column guard;
+//   1. every entry of the candidate table against the generic walk's own candidate rule (affine_candidate, the function
+//      walk_affine calls per column): offset code, source state, score for arbitrary mu1 / mu2, look-ahead, band-column guard;
 //   2. the carried row (strip, il, row offset) against a fresh division, down every row and along random walks, and, at
 //      EVERY lattice point and every (state, candidate) the kernel would load for, the guard mask against the generic
 //      kernel's guard and base + 32-bit offset against
@@ -28,33 +28,6 @@ static uint32_t mix(uint64_t x) {
   return (uint32_t)x;
 }
 
-// ---- the generic kernel's expressions for candidate lane c of state st (traceback_affine_kernel's loop body)
-struct Generic {
-  int o0, o1, o2, o3, ss, sc, inc0, inc1;
-  bool lane;  // c < 15
-};
-static int shift_of_h(int hU, int hV) { return hU == hV ? 0 : ((hU == 2 || hV == 2) ? 1 : 2); }
-static Generic generic(int st, int c, int beta, int gamma, int delta, int mu1, int mu2) {
-  const int grp = c < 9 ? 1 : (c < 12 ? 2 : 3);
-  const int hfree = grp == 2 ? 2 - (c - 9) : 2 - (c - 12);
-  const int hU = st / 3, hV = st - 3 * hU;
-  const int u0 = hU >= 1, u1 = hU != 1, v0 = hV >= 1, v1 = hV != 1;
-  const int valU = hU == 2 ? mu1 : gamma, valV = hV == 2 ? mu2 : gamma;
-  Generic g;
-  g.o0 = grp == 2 ? 0 : u0, g.o1 = grp == 2 ? 0 : u1;
-  g.o2 = grp == 3 ? 0 : v0, g.o3 = grp == 3 ? 0 : v1;
-  g.ss = grp == 1 ? c : (grp == 2 ? 3 * hU + hfree : 3 * hfree + hV);
-  const int ra = g.ss / 3, rb = g.ss - 3 * ra;
-  const int openU = (hU != 2 && ra != hU) ? beta : 0, openV = (hV != 2 && rb != hV) ? beta : 0;
-  g.sc = grp == 1   ? delta * shift_of_h(hU, hV) + valU + valV + openU + openV
-         : grp == 2 ? delta * (v0 + v1) + valV + openV
-                    : delta * (u0 + u1) + valU + openU;
-  const int r0 = ra >= 1, r1 = ra != 1, r2 = rb >= 1, r3 = rb != 1;
-  g.inc0 = (g.o0 - g.o2) + (r0 - r2), g.inc1 = (g.o1 - g.o3) + (r1 - r3);
-  g.lane = c < 15;
-  return g;
-}
-
 template <int S>
 static void check_table() {
   using TF = TraceFast<S>;
@@ -71,7 +44,7 @@ static void check_table() {
           }
           for (int t = 0; t < 3; ++t) {
             const int mu1 = (int)(mix(t * 7 + 1) % 2001) - 1000, mu2 = (int)(mix(t * 13 + 5) % 2001) - 1000;
-            const Generic g = generic(st, c, p[0], p[1], p[2], mu1, mu2);
+            const AffineCandidate g = affine_candidate(st, c, p[0], p[1], p[2], mu1, mu2);
             const int code = g.o0 * 8 + g.o1 * 4 + g.o2 * 2 + g.o3;
             if ((int)(e.lo & 15) != code) bad("code", S, 0, 0, st, b0, c, e.lo & 15);
             const int b = b0 + g.o1 - g.o3;
@@ -117,7 +90,7 @@ static void run_case(int n, int m, bool cells) {
         const uint32_t lo = e.lo;
         const bool ok = (lo & deny) == 0;
         // the generic kernel's guard (pyx:133-141)
-        const Generic g = generic(st, std::min(c, 14), 0, 0, 0, 0, 0);
+        const AffineCandidate g = affine_candidate(st, std::min(c, 14), 0, 0, 0, 0, 0);
         const int pi = i - g.o0, pj = j - g.o1, pk = k - g.o2, pl = l - g.o3;
         const bool gok = c < 15 && pi >= 0 && pj >= 0 && pk >= 0 && pl >= 0 && std::abs(pk - pi) <= S && std::abs(pl - pj) <= S;
         if (ok != gok) bad("guard", S, n, m, i, j, st, c);

@@ -23,7 +23,8 @@ the DMA section (what follows the unpack up to the last DMA's m0 restore), and e
     python tools/isa_hot_path.py --traceback k.s [kernel-name-substring] [top-N]
 
 Traceback mode: the column loop of an affine traceback kernel (default: traceback_affine_fast_kernelILi1E; the generic
-one is traceback_affine_kernelILi1ELb1ELb0ELb0ELb1ELb0ELb0E) is the depth-1 loop that holds the pick's v_readlane.  One
+one is traceback_affine_kernelILi1ELb1ELb0ELb0ELb1ELb0ELb0E, whose loop is walk_affine's, inlined) is the depth-1 loop that
+holds the pick's v_readlane.  One
 path is printed, the common one of a column: through the candidates' global loads and the pick, with no 64-bit multiply-add
 where the loop has a path without one (the short-chain kernel's side path through full records divides and multiplies in
 64 bits; the generic kernel does so in every column) and without the trace buffer's flush."""
