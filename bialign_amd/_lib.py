@@ -70,6 +70,9 @@ class NullSpec(ctypes.Structure):
     _fields_ = [("replicas", ctypes.c_int32), ("seed", ctypes.c_uint32)]
 
 
+NULL_MONO, NULL_DINUCLEOTIDE = 0, 1  # BIALIGN_NULL_MONO, BIALIGN_NULL_DINUCLEOTIDE: bialign_batch_set_null_model
+
+
 class NullStats(ctypes.Structure):
     """bialign_null_stats: one pair's replica scores reduced to exact integers."""
     _fields_ = [("sum", ctypes.c_int64), ("sumsq", ctypes.c_int64), ("min", ctypes.c_int32),
@@ -161,6 +164,8 @@ SYMBOLS = [
      [ctypes.c_void_p, ctypes.POINTER(Params), ctypes.POINTER(Scoring), ctypes.POINTER(Pairs),
       ctypes.POINTER(NullSpec), ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p)]),
     ("bialign_batch_dump_null_tables", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, c_i32p, c_i32p]),
+    ("bialign_batch_set_null_model", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
+    ("bialign_batch_get_null_model", ctypes.c_int, [ctypes.c_void_p, c_i32p]),
 ]
 
 #: Declared in include/bialign.h as well, but kept apart from SYMBOLS: tests/test_capi_symbols.py collects the header's

@@ -13,6 +13,9 @@ own pairs, rank 0 additionally a ``#scores`` line with all gathered scores.
 ``--zscore R`` adds one line behind each pair's block: where the score lies among the scores of A against R shuffles
 of B (``bialign_amd.significance``; the shuffles are made and scored on the GPU),
 ``ZSCORE: <z> (mean <mean>, sd <sd>, <n_ge>/<R> shuffles >= score)``.  Without the option the output is unchanged.
+``--zscore_shuffle {mono,dinucleotide}`` names the null model of those shuffles (``mono``, the default, keeps B's letter
+composition; ``dinucleotide`` keeps the count of every ordered pair of neighbouring letters, the accepted null for nucleic
+acids); given the option, the output opens with a header line ``#zscore_shuffle\t<model>``.  Not without ``--zscore``.
 
 ``--fit`` aligns every pair's molecule A with the best-scoring substring of its molecule B (fit alignments, free end
 gaps in B: include/bialign.h, BIALIGN_BATCH_FIT).  The alignment is decoded on that substring, one extra line
@@ -72,6 +75,10 @@ def build_parser():
     p.add_argument("--zscore", type=int, default=0, metavar="R",
                    help="Also print each pair's z-score against R shuffles of molecule B (1..65535), as a "
                         "'ZSCORE:' line behind the pair's block.")
+    p.add_argument("--zscore_shuffle", choices=("mono", "dinucleotide"), default=None,
+                   help="With --zscore: the null model of the shuffles. mono (the default) keeps molecule B's letter "
+                        "composition, dinucleotide the count of every ordered pair of neighbouring letters. "
+                        "Names the model in a '#zscore_shuffle' header line.")
     p.add_argument("--fit", action="store_true",
                    help="Fit alignments: molecule A against the best substring of molecule B (B's end gaps are free); "
                         "prints the substring as a 'B span' line behind 'SCORE:'.")
@@ -201,8 +208,10 @@ def _main(argv=None):
     if args.overlap and (args.fit or args.local):
         parser.error("--overlap excludes --fit and --local")
     hits = check_hit_options(parser, args)
+    if args.zscore_shuffle and not args.zscore:
+        parser.error("--zscore_shuffle needs --zscore")
     params = {k: v for k, v in vars(args).items()
-              if k not in ("pairs", "verbose", "score_only", "zscore", "zscore_seed", "fit", "local", "overlap", "hits", "hit_min_score")}
+              if k not in ("pairs", "verbose", "score_only", "zscore", "zscore_seed", "zscore_shuffle", "fit", "local", "overlap", "hits", "hit_min_score")}
     if args.zscore:
         from .significance import check_null
         check_null((args.zscore, args.zscore_seed))
@@ -213,6 +222,8 @@ def _main(argv=None):
     rank, local_rank, world = init_from_env()
     costs = [pair_cost((r[1], r[4]), params["max_shift"]) for r in records]  # shards balanced by lattice cells
     mine = shard(len(records), rank, world, costs)
+    if args.zscore_shuffle and rank == 0:
+        print(f"#zscore_shuffle\t{args.zscore_shuffle}")
     scores = []
     if len(mine):
         batch = make_batch([(r[1], r[4], r[2], r[5]) for r in (records[p] for p in mine)], params,
@@ -227,7 +238,7 @@ def _main(argv=None):
             from .significance import zscores
             z = zscores([(r[1], r[4], r[2], r[5]) for r in (records[p] for p in mine)], params, replicas=args.zscore,
                         seed=args.zscore_seed, observed=scores, engine=default_engine(local_rank), fit=args.fit, local=args.local,
-                        overlap=args.overlap)
+                        overlap=args.overlap, shuffle=args.zscore_shuffle or "mono")
         if args.score_only:
             for t, p in enumerate(mine):
                 print(f"pair {p}\t{records[p][0]}\t{records[p][3]}\t{int(scores[t])}" + (f"\t{int(end_b[t])}" if args.fit else "") +

@@ -1062,6 +1062,30 @@ int bialign_batch_get_null_info(const bialign_batch* b, bialign_null_info* info)
   return BIALIGN_OK;
 }
 
+int bialign_batch_set_null_model(bialign_batch* b, int32_t model) {
+  if (!b) return fail(BIALIGN_E_INVALID, "NULL argument");
+  if (!b->null_R) return fail(BIALIGN_E_INVALID, "not a null batch (bialign_batch_create_null)");
+  if (model != BIALIGN_NULL_MONO && model != BIALIGN_NULL_DINUCLEOTIDE)
+    return fail(BIALIGN_E_INVALID, "unknown null model %d (BIALIGN_NULL_MONO, BIALIGN_NULL_DINUCLEOTIDE)", model);
+  if (model == BIALIGN_NULL_DINUCLEOTIDE) {
+    if (b->dense1)
+      return fail(BIALIGN_E_UNSUPPORTED, "the dinucleotide model shuffles B's sequence letters: with mu1 in DENSE form B has none");
+    if (b->null_max_m > BIALIGN_NULL_DINUCLEOTIDE_MAX_LEN)  // (bialign_null.hpp checks the bound against its LDS layout)
+      return fail(BIALIGN_E_UNSUPPORTED, "the dinucleotide model keeps a molecule's edge list in LDS: longest B molecule %d exceeds %d",
+                  b->null_max_m, BIALIGN_NULL_DINUCLEOTIDE_MAX_LEN);
+  }
+  if (int rc = bialign_batch_wait(b)) return rc;
+  b->null_model = model;
+  return BIALIGN_OK;
+}
+
+int bialign_batch_get_null_model(const bialign_batch* b, int32_t* model) {
+  if (!b || !model) return fail(BIALIGN_E_INVALID, "NULL argument");
+  if (!b->null_R) return fail(BIALIGN_E_INVALID, "not a null batch (bialign_batch_create_null)");
+  *model = b->null_model;
+  return BIALIGN_OK;
+}
+
 // What the three dumps below share once their own arguments are checked: the replica is in range, the batch idle and
 // uploaded, and virtual pair *v = pair * R + replica shuffled anew on the engine's stream.
 static int null_dump_begin(bialign_batch* b, int32_t pair, int32_t replica, int* v) {

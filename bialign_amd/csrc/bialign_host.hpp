@@ -136,6 +136,7 @@ struct bialign_batch : bialign::BatchPlan {  // the plan (bialign_plan.hpp), and
   DevBuf<bialign_null_stats> d_null_stats;  // ... and its result
   hipEvent_t null_evs[4] = {nullptr, nullptr, nullptr, nullptr};  // around the shuffle launch of a run, around the reduction
   double shuffle_ms = 0, stats_ms = 0;      // HIP-event times (not part of fill_ms)
+  int32_t null_model = BIALIGN_NULL_MONO;   // bialign_batch_set_null_model: which permutation the shuffle kernels make
   DevBuf<TraceState> d_tstate;
   // Hit search (bialign_batch_set_hits, bialign_hits.hpp): the spec (max_walks resolved) and the result buffers of the whole
   // batch, reset ahead of every run.  hits_on false: a run touches none of this.

@@ -18,14 +18,25 @@ static Args shuffle_args(const bialign_batch* b, int first, int count) {
   return a;
 }
 
+// CAP of the dinucleotide model's step 2; BIALIGN_NULL_TREE_CAP: tests, a smaller one (0: every replica takes the fallback)
+static int32_t null_tree_cap() {
+  const char* e = getenv("BIALIGN_NULL_TREE_CAP");
+  return e ? std::clamp(atoi(e), 0, NULL_TREE_CAP) : NULL_TREE_CAP;
+}
+
 // The two wave-per-pair kernels: one wave per virtual pair, the index array of the batch's longest B in LDS
-// (bialign_batch_create_null_features / _dense refuse longer ones than NULL_FEAT_MAX_M)
+// (bialign_batch_create_null_features / _dense refuse longer ones than NULL_FEAT_MAX_M); under the dinucleotide model the
+// whole layout of null_dinuc_perm_to_lds (bialign_batch_set_null_model refuses longer ones than NULL_DINUC_MAX_M)
 template <class Args>
-static int launch_wave_shuffle(void (*kernel)(Args), const char* what, const bialign_batch* b, const Args& a) {
-  if (b->null_max_m < 1 || b->null_max_m > NULL_FEAT_MAX_M)
-    return fail(BIALIGN_E_UNSUPPORTED, "%s shuffle: longest B molecule %d outside 1..%d", what, b->null_max_m, NULL_FEAT_MAX_M);
-  const size_t lds = ((size_t)b->null_max_m * sizeof(uint16_t) + 15) / 16 * 16;
-  return launch(kernel, dim3((unsigned)std::min(a.count, NULL_FEAT_MAX_GRID)), dim3(64), lds, b->eng->stream, a);
+static int launch_wave_shuffle(void (*kernel)(Args), const char* what, const bialign_batch* b, Args a) {
+  const bool dinuc = b->null_model == BIALIGN_NULL_DINUCLEOTIDE;
+  const int max_m = dinuc ? NULL_DINUC_MAX_M : NULL_FEAT_MAX_M;
+  if (b->null_max_m < 1 || b->null_max_m > max_m)
+    return fail(BIALIGN_E_UNSUPPORTED, "%s shuffle: longest B molecule %d outside 1..%d", what, b->null_max_m, max_m);
+  a.model = b->null_model;
+  a.tree_cap = null_tree_cap();
+  const size_t bytes = dinuc ? (size_t)null_dinuc_lds(b->null_max_m) : (size_t)b->null_max_m * sizeof(uint16_t);
+  return launch(kernel, dim3((unsigned)std::min(a.count, NULL_FEAT_MAX_GRID)), dim3(64), (bytes + 15) / 16 * 16, b->eng->stream, a);
 }
 
 // FEATURE-form null batch
@@ -44,13 +55,14 @@ static int launch_shuffle_features(bialign_batch* b, int first, int count) {
 }
 
 // DENSE-form null batch: the finished permutations go to d_null_perm
+// LOOKUP-form null batch under the dinucleotide model: the same kernel for the gathered codes alone, no permutations kept
 static int launch_shuffle_index(bialign_batch* b, int first, int count) {
   ShuffleIndexArgs a = shuffle_args<ShuffleIndexArgs>(b, first, count);
   a.src_seq = b->dense1 ? nullptr : b->d_null_seq.p;
   a.src_cls = b->dense ? nullptr : b->d_null_cls.p;
   a.dst_seq = b->d_seq_b.p;
   a.dst_cls = b->d_cls_b.p;
-  a.dst_perm = b->d_null_perm.p;
+  a.dst_perm = b->null_dense ? b->d_null_perm.p : nullptr;
   return launch_wave_shuffle(shuffle_index_kernel, "index", b, a);
 }
 
@@ -81,7 +93,7 @@ int launch_permute_tables(bialign_batch* b, int first, int count) {
 int launch_shuffle_null(bialign_batch* b, int first, int count) {
   if (!b->null_R || count < 1) return BIALIGN_OK;
   if (b->feat) return launch_shuffle_features(b, first, count);
-  if (b->null_dense) return launch_shuffle_index(b, first, count);
+  if (b->null_dense || b->null_model == BIALIGN_NULL_DINUCLEOTIDE) return launch_shuffle_index(b, first, count);
   ShuffleArgs a = shuffle_args<ShuffleArgs>(b, first, count);
   a.src_seq = b->d_null_seq.p;
   a.src_cls = b->d_null_cls.p;

@@ -11,7 +11,9 @@
 // codes (shuffle_index_kernel), through which permute_tables_kernel gathers the columns of the real pairs' tables into
 // each chunk's table scratch (below).
 //
-// The permutation is the one include/bialign.h states (normative there; bialign_amd/significance.py mirrors it).
+// The permutation is the one include/bialign.h states (normative there; bialign_amd/significance.py mirrors it): THE
+// PERMUTATION (BIALIGN_NULL_MONO, null_perm_to_lds and shuffle_codes_kernel) or, where bialign_batch_set_null_model asked
+// for it, THE DINUCLEOTIDE PERMUTATION (null_dinuc_perm_to_lds, through the two wave-per-pair kernels in every form).
 //
 // Mapping of shuffle_codes_kernel: one thread per virtual pair.  It copies B into its own slice of the replica buffers and
 // runs the Fisher-Yates swaps there in place (swapping the values is the same as gathering through the permuted
@@ -146,13 +148,16 @@ __global__ __launch_bounds__(NULL_BLOCK) void null_stats_kernel(NullStatsArgs A)
 // molecules the engine takes; registers + readlane need none.)
 // Vector loads and stores, 64-bit offsets, no atomics.  m = 1: the chain is empty, the identity.
 // What the wave-per-pair kernels' arguments share with ShuffleArgs, field for field (the launchers fill them in one place,
-// bialign_null.hip).  ShuffleArgs itself keeps its layout: extending this would move shuffle_codes_kernel's argument loads.
+// bialign_null.hip), and behind them the null model, which only these kernels have.  ShuffleArgs itself keeps its layout:
+// extending it would move shuffle_codes_kernel's argument loads.
 struct ShuffleBase {
   const PairDesc* pairs;    // the VIRTUAL pairs: m, and seq_b = start of the replica's slice in the dst_* buffers
   const int64_t* src_off;   // [real pairs] start of pair p's B in the src_* buffers
   int32_t first, count;     // virtual pairs first .. first + count
   int32_t replicas;
   uint32_t seed;
+  int32_t model;            // BIALIGN_NULL_MONO: null_perm_to_lds; BIALIGN_NULL_DINUCLEOTIDE: null_dinuc_perm_to_lds
+  int32_t tree_cap;         // ... and its CAP, 0..NULL_TREE_CAP
 };
 
 struct ShuffleFeatArgs : ShuffleBase {
@@ -186,6 +191,196 @@ __device__ __forceinline__ void null_perm_to_lds(uint32_t h, int32_t m, int32_t 
   __syncthreads();
 }
 
+// ---- THE DINUCLEOTIDE PERMUTATION (include/bialign.h, whose step numbers the comments below use): the sibling of
+// null_perm_to_lds, one wave per virtual pair, perm left in the same LDS array.  The letters are B's sequence codes.
+//
+// LDS of a molecule of m residues, mp = m rounded up to even, behind one another:
+//   perm uint16[mp] | L uint16[mp] | first uint32[256] | off, cnt, last, nxt uint16[256] each | map, intree uint8[256] each
+//   | B uint8[m]
+// = 4 * mp + NULL_DINUC_FIXED + m bytes (null_dinuc_lds): within a workgroup's 160 KiB up to m = NULL_DINUC_MAX_M.
+//
+// Where each step runs:
+//   letters  all lanes stage the codes into B; an LDS atomicMin per residue leaves every code's first position; a ballot
+//            and prefix popcount over blocks of 64 positions numbers the first occurrences in order (map), B is renamed
+//            in place.  K letters.
+//   1        per letter a ballot over blocks of 64 edges and a prefix popcount: a stable fill of L, and cnt / off fall out
+//            of the running write position.  K * ceil((m - 1) / 64) wave steps.
+//   2        a wave-uniform serial chain of LDS reads: every value read goes through readfirstlane (lane 0's view, which
+//            wrote it), lane 0 stores.  At most tree_cap draws, the marking walks at most K steps each.
+//   3        per letter the element at last[x] moves to the list's end, 64 elements shifting at a time, then the swaps of
+//            the chain take their draws 64 at a time from registers by readlane, as null_perm_to_lds does.
+//   4        the walk, serial like 2: three dependent LDS reads per position (nxt = off + ptr, L, B).
+// Every loop is bounded by m, K <= 256 or tree_cap.  No global memory but the m code loads; no global atomics.
+constexpr int NULL_LETTERS = 256;    // a sequence code is a uint8
+constexpr int NULL_TREE_CAP = 4096;  // CAP
+constexpr int NULL_DINUC_FIXED = NULL_LETTERS * (4 + 4 * 2 + 2 * 1);
+constexpr int NULL_LDS_MAX = 160 * 1024;
+__host__ __device__ constexpr int64_t null_dinuc_lds(int64_t m) { return 4 * ((m + 1) & ~int64_t(1)) + NULL_DINUC_FIXED + m; }
+constexpr int NULL_DINUC_MAX_M = BIALIGN_NULL_DINUCLEOTIDE_MAX_LEN;
+static_assert(null_dinuc_lds(NULL_DINUC_MAX_M) <= NULL_LDS_MAX && null_dinuc_lds(NULL_DINUC_MAX_M + 1) > NULL_LDS_MAX,
+              "NULL_DINUC_MAX_M is the longest molecule the layout admits");
+static_assert(NULL_DINUC_MAX_M >= 30000 && NULL_DINUC_MAX_M <= 65535, "include/bialign.h promises 30000; L and perm are uint16");
+
+// in [0, bound)
+__host__ __device__ inline uint32_t null_uni(uint32_t h, uint32_t salt, uint32_t bound) {
+  return (uint32_t)(((uint64_t)null_mix(h + salt) * (uint64_t)bound) >> 32);
+}
+
+// a[i] as lane 0 sees it, in every lane (wave-uniform control flow only)
+template <class T>
+__device__ __forceinline__ int32_t null_wave_ld(const T* a, int32_t i) {
+  return __builtin_amdgcn_readfirstlane((int32_t)a[i]);
+}
+
+__device__ __forceinline__ void null_dinuc_perm_to_lds(uint32_t h, int32_t m, int32_t lane, const uint8_t* __restrict__ codes,
+                                                       int32_t tree_cap, uint16_t* perm) {
+  if (m <= 2) {  // (wave-uniform, as everything that steers a branch or a loop below)
+    for (int32_t x = lane; x < m; x += 64) perm[x] = (uint16_t)x;
+    __syncthreads();
+    return;
+  }
+  const int32_t mp = (m + 1) & ~1;
+  uint16_t* const L = perm + mp;
+  uint32_t* const first = reinterpret_cast<uint32_t*>(L + mp);
+  uint16_t* const off = reinterpret_cast<uint16_t*>(first + NULL_LETTERS);
+  uint16_t* const cnt = off + NULL_LETTERS;
+  uint16_t* const last = cnt + NULL_LETTERS;
+  uint16_t* const nxt = last + NULL_LETTERS;
+  uint8_t* const map = reinterpret_cast<uint8_t*>(nxt + NULL_LETTERS);
+  uint8_t* const intree = map + NULL_LETTERS;
+  uint8_t* const B = intree + NULL_LETTERS;
+  const uint64_t below = ((uint64_t)1 << lane) - 1;  // the lanes ahead of this one
+
+  // letters: renumbered 0, 1, 2, ... in order of first occurrence
+  for (int32_t c = lane; c < NULL_LETTERS; c += 64) {
+    first[c] = 0xFFFFFFFFu;
+    intree[c] = 0;
+  }
+  for (int32_t x = lane; x < m; x += 64) B[x] = codes[x];
+  __syncthreads();
+  for (int32_t x = lane; x < m; x += 64) atomicMin(&first[B[x]], (uint32_t)x);
+  __syncthreads();
+  int32_t K = 0;
+  for (int32_t xb = 0; xb < m; xb += 64) {
+    const int32_t x = xb + lane;
+    const bool opens = x < m && first[B[x]] == (uint32_t)x;
+    const uint64_t mask = __ballot(opens);
+    if (opens) map[B[x]] = (uint8_t)(K + __popcll(mask & below));
+    K += __popcll(mask);
+  }
+  __syncthreads();
+  for (int32_t x = lane; x < m; x += 64) B[x] = map[B[x]];
+  __syncthreads();
+
+  // 1. edges: L sorted by (tail, e); cnt, off; nxt = off + ptr of step 4
+  int32_t w = 0;
+  for (int32_t x = 0; x < K; ++x) {
+    const int32_t o = w;
+    for (int32_t eb = 0; eb < m - 1; eb += 64) {
+      const int32_t e = eb + lane;
+      const bool mine = e < m - 1 && B[e] == x;
+      const uint64_t mask = __ballot(mine);
+      if (mine) L[w + __popcll(mask & below)] = (uint16_t)e;  // w + ... < m - 1: every edge has one tail
+      w += __popcll(mask);
+    }
+    if (lane == 0) {
+      off[x] = (uint16_t)o;
+      cnt[x] = (uint16_t)(w - o);
+      nxt[x] = (uint16_t)o;
+    }
+  }
+  __syncthreads();
+  const int32_t z = null_wave_ld(B, m - 1);
+
+  // 2. last exits
+  if (lane == 0) intree[z] = 1;
+  int32_t s = 0;
+  bool gave_up = false;
+  for (int32_t x = 0; x < K && !gave_up; ++x) {
+    if (null_wave_ld(cnt, x) == 0 || null_wave_ld(intree, x)) continue;
+    int32_t u = x;
+    while (!null_wave_ld(intree, u)) {  // (u != z has an exit: cnt[u] >= 1)
+      if (s >= tree_cap) {
+        gave_up = true;
+        break;
+      }
+      const int32_t l = (int32_t)null_uni(h, 0x80000000u + (uint32_t)s, (uint32_t)null_wave_ld(cnt, u));
+      if (lane == 0) last[u] = (uint16_t)l;
+      ++s;
+      u = null_wave_ld(B, null_wave_ld(L, null_wave_ld(off, u) + l) + 1);
+    }
+    if (gave_up) break;
+    u = x;
+    for (int32_t g = 0; g < K && !null_wave_ld(intree, u); ++g) {  // (a path along last[] into the tree: no letter twice)
+      if (lane == 0) intree[u] = 1;
+      u = null_wave_ld(B, null_wave_ld(L, null_wave_ld(off, u) + null_wave_ld(last, u)) + 1);
+    }
+  }
+  if (gave_up)  // the molecule's own last exits
+    for (int32_t x = lane; x < K; x += 64)
+      if (x != z && cnt[x] > 0) last[x] = (uint16_t)(cnt[x] - 1);
+  __syncthreads();
+
+  // 3. order of exits
+  for (int32_t x = 0; x < K; ++x) {
+    const int32_t c = null_wave_ld(cnt, x);
+    if (c == 0) continue;
+    const int32_t o = null_wave_ld(off, x);
+    uint16_t* const Lx = L + o;  // letter x's list
+    int32_t r = c;
+    if (x != z) {  // the last exit to the list's end, the others keep their order
+      const int32_t l = null_wave_ld(last, x);
+      const int32_t keep = null_wave_ld(Lx, l);
+      for (int32_t ib = l; ib < c - 1; ib += 64) {
+        const int32_t i = ib + lane;
+        const uint16_t v = i < c - 1 ? Lx[i + 1] : 0;
+        __syncthreads();
+        if (i < c - 1) Lx[i] = v;
+        __syncthreads();
+      }
+      if (lane == 0) Lx[c - 1] = (uint16_t)keep;
+      r = c - 1;
+    }
+    for (int32_t tb = (r - 1) & ~63; tb >= 0; tb -= 64) {  // (r = 0: tb = -64, no step)
+      const uint32_t d = null_uni(h, (uint32_t)(o + tb + lane), (uint32_t)(tb + lane + 1));  // lane k: the draw of t = tb + k
+      const int32_t khi = r - 1 - tb < 63 ? r - 1 - tb : 63, klo = tb == 0 ? 1 : 0;
+      for (int32_t k = khi; k >= klo; --k) {
+        const int32_t t = tb + k;                                    // r - 1 down to 1
+        const int32_t j = __builtin_amdgcn_readlane((int32_t)d, k);  // <= t < r: inside the letter's list
+        const uint16_t pt = Lx[t], pj = Lx[j];
+        if (lane == 0) {
+          Lx[t] = pj;
+          Lx[j] = pt;
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  // 4. walk
+  if (lane == 0) perm[0] = 0;
+  int32_t cur = null_wave_ld(B, 0);
+  for (int32_t pos = 1; pos < m; ++pos) {
+    const int32_t q = null_wave_ld(nxt, cur);
+    const int32_t e = null_wave_ld(L, q);
+    const int32_t to = e + 1 < m ? e + 1 : m - 1;  // (e <= m - 2 by construction; the consumers index global memory with it)
+    if (lane == 0) {
+      nxt[cur] = (uint16_t)(q + 1);
+      perm[pos] = (uint16_t)to;
+    }
+    cur = null_wave_ld(B, to);
+  }
+  __syncthreads();
+}
+
+// The permutation of virtual pair (p, r) under the launch's model, left in perm for every lane of the wave
+__device__ __forceinline__ void null_model_perm_to_lds(const ShuffleBase& A, int32_t p, int32_t r, int32_t m, int32_t lane,
+                                                       const uint8_t* codes, uint16_t* perm) {
+  const uint32_t h = null_hash(A.seed, (uint32_t)p, (uint32_t)r);
+  if (A.model == BIALIGN_NULL_DINUCLEOTIDE) null_dinuc_perm_to_lds(h, m, lane, codes, A.tree_cap, perm);
+  else null_perm_to_lds(h, m, lane, perm);
+}
+
 __global__ __launch_bounds__(64) void shuffle_features_kernel(ShuffleFeatArgs A) {
   extern __shared__ uint16_t null_perm[];  // [longest m of the launch]
   const int32_t lane = (int32_t)threadIdx.x;
@@ -195,8 +390,7 @@ __global__ __launch_bounds__(64) void shuffle_features_kernel(ShuffleFeatArgs A)
     const PairDesc& pd = A.pairs[v];
     const int32_t m = __builtin_amdgcn_readfirstlane(pd.m);
     const int64_t src = A.src_off[p], dst = pd.seq_b;
-    const uint32_t h = null_hash(A.seed, (uint32_t)p, (uint32_t)r);
-    null_perm_to_lds(h, m, lane, null_perm);
+    null_model_perm_to_lds(A, p, r, m, lane, A.src_seq + src, null_perm);
     // (source and replica buffers are distinct allocations: the four loads of a residue go out together)
     const uint8_t* __restrict__ const ss = A.src_seq + src;
     const double* __restrict__ const su = A.src_up + src;
@@ -237,7 +431,8 @@ __global__ __launch_bounds__(64) void shuffle_features_kernel(ShuffleFeatArgs A)
 struct ShuffleIndexArgs : ShuffleBase {
   const uint8_t *src_seq, *src_cls;  // the uploaded B codes; nullptr: mu1 (seq) / mu2 (cls) is dense
   uint8_t *dst_seq, *dst_cls;        // the replica buffers
-  uint16_t* dst_perm;                // the replicas' permutations
+  uint16_t* dst_perm;                // the replicas' permutations; nullptr: a LOOKUP-form null batch under the
+                                     // dinucleotide model, which wants the gathered codes only
 };
 
 __global__ __launch_bounds__(64) void shuffle_index_kernel(ShuffleIndexArgs A) {
@@ -249,12 +444,10 @@ __global__ __launch_bounds__(64) void shuffle_index_kernel(ShuffleIndexArgs A) {
     const PairDesc& pd = A.pairs[v];
     const int32_t m = __builtin_amdgcn_readfirstlane(pd.m);
     const int64_t src = A.src_off[p], dst = pd.seq_b;
-    const uint32_t h = null_hash(A.seed, (uint32_t)p, (uint32_t)r);
-    null_perm_to_lds(h, m, lane, null_perm);
-    uint16_t* __restrict__ const dp = A.dst_perm + dst;
+    null_model_perm_to_lds(A, p, r, m, lane, A.src_seq + src, null_perm);  // (the dinucleotide model has src_seq: the host's check)
     for (int32_t x = lane; x < m; x += 64) {
       const int32_t s = null_perm[x];  // < m
-      dp[x] = (uint16_t)s;
+      if (A.dst_perm) A.dst_perm[dst + x] = (uint16_t)s;
       if (A.src_seq) A.dst_seq[dst + x] = A.src_seq[src + s];
       if (A.src_cls) A.dst_cls[dst + x] = A.src_cls[src + s];
     }

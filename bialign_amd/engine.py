@@ -307,6 +307,24 @@ class Batch:
         check(lib.bialign_batch_get_null_info(self._h, ctypes.byref(ni)))
         return dict(shuffle_ms=ni.shuffle_ms, stats_ms=ni.stats_ms, replica_bytes=ni.replica_bytes)
 
+    def set_null_model(self, model):
+        """Null batch: the null model of the replicas from the next run on -- ``"mono"`` / 0 (THE PERMUTATION) or
+        ``"dinucleotide"`` / 1 (THE DINUCLEOTIDE PERMUTATION of include/bialign.h).  A refused model (BialignError)
+        leaves the batch as it was."""
+        self._need_null()
+        from .significance import SHUFFLES
+        number = SHUFFLES.index(model) if model in SHUFFLES else model
+        check(lib.bialign_batch_set_null_model(self._h, int(number)))
+
+    @property
+    def null_model(self):
+        """Null batch: the name of the null model in force, ``"mono"`` or ``"dinucleotide"``."""
+        self._need_null()
+        from .significance import SHUFFLES
+        model = ctypes.c_int32()
+        check(lib.bialign_batch_get_null_model(self._h, ctypes.byref(model)))
+        return SHUFFLES[model.value]
+
     def dump_null_codes(self, pair, replica):
         """Null batch, test hook: (sequence codes, class codes) of one replica of one pair's B as the sweep reads them."""
         self._need_null()

@@ -13,7 +13,9 @@ outside as ``mu2_dense`` -- have it in DENSE form: ``null_dense_batch`` / ``zsco
 (bialign_batch_create_null_dense), a residue of B carrying its column of every table.
 
 ``permutation``, ``shuffle_b``, ``shuffle_features`` and ``shuffle_tables`` restate the header's permutation in plain Python: the
-documented way to reproduce any replica on the host.  Nothing in this module loads the HIP library before its
+documented way to reproduce any replica on the host.  ``shuffle="dinucleotide"`` on any of the functions below takes the
+header's second null model, which keeps the count of every ordered pair of neighbouring letters of B
+(``dinucleotide_permutation`` restates it); the default ``"mono"`` keeps single-letter composition only.  Nothing in this module loads the HIP library before its
 arguments are checked.
 """
 import numpy as np
@@ -47,30 +49,126 @@ def permutation(seed, pair, replica, m):
     return np.array(perm, dtype=np.int64)
 
 
+SHUFFLES = ("mono", "dinucleotide")  # BIALIGN_NULL_MONO, BIALIGN_NULL_DINUCLEOTIDE
+TREE_CAP = 4096  # CAP of THE DINUCLEOTIDE PERMUTATION: draws of step 2 per replica
+
+
+def check_shuffle(shuffle):
+    """``shuffle=`` of the functions below -> the model's number in the C ABI; anything but the two names: ValueError."""
+    if not isinstance(shuffle, str) or shuffle not in SHUFFLES:
+        raise ValueError(f"shuffle must be one of {SHUFFLES}, got {shuffle!r}")
+    return SHUFFLES.index(shuffle)
+
+
+def dinucleotide_permutation(seed, pair, replica, letters, tree_cap=TREE_CAP):
+    """The permutation that replica ``replica`` of pair ``pair`` applies to a B molecule whose letters are ``letters``
+    (a str or any sequence of hashable items) under ``seed`` in the dinucleotide model: ``shuffled[x] =
+    original[perm[x]]`` has exactly the original's count of every ordered pair of neighbouring letters
+    (include/bialign.h, THE DINUCLEOTIDE PERMUTATION).  ``tree_cap``: CAP, 0..4096."""
+    return _dinucleotide(seed, pair, replica, letters, tree_cap)[0]
+
+
+def _dinucleotide(seed, pair, replica, letters, tree_cap=TREE_CAP):
+    """``dinucleotide_permutation`` -> (perm, draws of step 2, whether step 2 gave up); the comments name the header's steps."""
+    seed, pair, replica, cap = int(seed), int(pair), int(replica), int(tree_cap)
+    if not 0 <= seed <= _M32:
+        raise ValueError("seed must be in 0..2**32-1")
+    if pair < 0 or replica < 0 or len(letters) < 1:
+        raise ValueError("pair and replica must be >= 0, letters must hold at least one")
+    if not 0 <= cap <= TREE_CAP:
+        raise ValueError(f"tree_cap must be in 0..{TREE_CAP}")
+    h = _mix((_mix((_mix(seed ^ 0x9E3779B9) + pair) & _M32) + replica) & _M32)
+
+    def uni(salt, bound):
+        return (_mix((h + salt) & _M32) * bound) >> 32
+
+    number = {}
+    B = [number.setdefault(c, len(number)) for c in letters]  # letters renumbered by first occurrence
+    m, K = len(B), len(number)
+    if m <= 2:
+        return np.arange(m, dtype=np.int64), 0, False
+    # 1. edges
+    cnt = [0] * K
+    for e in range(m - 1):
+        cnt[B[e]] += 1
+    off = [sum(cnt[:x]) for x in range(K)]
+    L = sorted(range(m - 1), key=lambda e: (B[e], e))
+    z = B[m - 1]
+    # 2. last exits
+    tree, last, s, gave_up = {z}, [0] * K, 0, False
+    for x in range(K):
+        if cnt[x] == 0 or x in tree or gave_up:
+            continue
+        u = x
+        while u not in tree:
+            if s == cap:
+                gave_up = True
+                break
+            last[u] = uni(0x80000000 + s, cnt[u])
+            s += 1
+            u = B[L[off[u] + last[u]] + 1]
+        if not gave_up:
+            u = x
+            while u not in tree:
+                tree.add(u)
+                u = B[L[off[u] + last[u]] + 1]
+    if gave_up:
+        last = [cnt[x] - 1 for x in range(K)]
+    # 3. order of exits
+    for x in range(K):
+        if cnt[x] == 0:
+            continue
+        o, r = off[x], cnt[x]
+        if x != z:
+            L[o:o + r] = L[o:o + last[x]] + L[o + last[x] + 1:o + r] + [L[o + last[x]]]
+            r -= 1
+        for t in range(r - 1, 0, -1):
+            j = uni(o + t, t + 1)
+            L[o + t], L[o + j] = L[o + j], L[o + t]
+    # 4. walk
+    perm, cur, ptr = [0] * m, B[0], [0] * K
+    for pos in range(1, m):
+        e = L[off[cur] + ptr[cur]]
+        ptr[cur] += 1
+        perm[pos] = e + 1
+        cur = B[e + 1]
+    return np.array(perm, dtype=np.int64), s, gave_up
+
+
+def _perm(shuffle, seed, pair, replica, letters):
+    """The permutation of a B molecule with these letters under either model."""
+    if check_shuffle(shuffle):
+        return dinucleotide_permutation(seed, pair, replica, letters)
+    return permutation(seed, pair, replica, len(letters))
+
+
 #: RNA: the letter a position's structure class is written with in a shuffled molecule (scoring.RNA_UNP, _DOWN, _UP)
 _RNA_CLASS_LETTERS = ".()"
 
 
-def shuffle_b(pair_tuple, seed, pair, replica, rna=False):
+def shuffle_b(pair_tuple, seed, pair, replica, rna=False, shuffle="mono"):
     """``(seqA, seqB, strA, strB)`` -> the same with molecule B as replica ``replica`` of pair ``pair`` has it: the
     residues of B permuted, each with its structure annotation.  Proteins: the structure letter moves with the residue.
     ``rna=True``: what moves is the position's structure *class* (unpaired, pairs to the right, pairs to the left --
     ``scoring.rna_classes``), written ``.``, ``(``, ``)``; such a string lists classes per position and is in general
-    no balanced dot-bracket structure."""
+    no balanced dot-bracket structure.  ``shuffle="dinucleotide"``: the dinucleotide model, its letters B's sequence
+    string (the structure letters travel with their positions and are no part of the letter)."""
     seq_a, seq_b, str_a, str_b = pair_tuple
     if len(seq_b) != len(str_b):
         raise ValueError("Provided structure and sequence must have the same length.")
-    perm = permutation(seed, pair, replica, len(seq_b)).tolist()
+    perm = _perm(shuffle, seed, pair, replica, seq_b).tolist()
     if rna:
         from .scoring import rna_classes
         str_b = "".join(_RNA_CLASS_LETTERS[c] for c in rna_classes(str_b).tolist())
     return seq_a, "".join(seq_b[x] for x in perm), str_a, "".join(str_b[x] for x in perm)
 
 
-def shuffle_features(seq, feats, seed, pair, replica):
+def shuffle_features(seq, feats, seed, pair, replica, shuffle="mono"):
     """``(seq, (up, down, unp))`` of a B molecule as replica ``replica`` of pair ``pair`` has it in a FEATURE-form null
     batch: a plain gather through ``permutation`` -- the letter and its three numbers land at the same index, and the
-    numbers are moved, not recomputed (float64, bit for bit the source's).  -> ``(str, (up, down, unp))``."""
+    numbers are moved, not recomputed (float64, bit for bit the source's).  -> ``(str, (up, down, unp))``.
+    ``shuffle="dinucleotide"``: through ``dinucleotide_permutation`` of ``seq``."""
+    check_shuffle(shuffle)
     seq = str(seq)
     try:
         up, down, unp = feats
@@ -79,18 +177,21 @@ def shuffle_features(seq, feats, seed, pair, replica):
     planes = tuple(np.asarray(f, dtype=np.float64) for f in (up, down, unp))
     if any(f.shape != (len(seq),) for f in planes):
         raise ValueError("every feature must hold one number per residue")
-    perm = permutation(seed, pair, replica, len(seq))
+    perm = _perm(shuffle, seed, pair, replica, seq)
     return "".join(seq[x] for x in perm.tolist()), tuple(np.ascontiguousarray(f[perm]) for f in planes)
 
 
-def shuffle_tables(table, seed, pair, replica):
+def shuffle_tables(table, seed, pair, replica, shuffle="mono", letters=None):
     """A pair's (len A, len B) table -- dense mu1 or mu2 -- as replica ``replica`` of pair ``pair`` has it in a
     DENSE-form null batch: ``table[:, permutation(seed, pair, replica, len B)]``, the columns moved with B's residues, the
-    values untouched."""
+    values untouched.  ``shuffle="dinucleotide"`` needs ``letters``, B's sequence: a table has no letters of its own."""
+    dinucleotide = check_shuffle(shuffle)
     table = np.asarray(table)
     if table.ndim != 2 or table.shape[1] < 1:
         raise ValueError("table must have shape (len A, len B)")
-    return np.ascontiguousarray(table[:, permutation(seed, pair, replica, table.shape[1])])
+    if dinucleotide and (letters is None or len(letters) != table.shape[1]):
+        raise ValueError('shuffle="dinucleotide" needs letters=, B\'s sequence, one letter per column')
+    return np.ascontiguousarray(table[:, _perm(shuffle, seed, pair, replica, letters if dinucleotide else range(table.shape[1]))])
 
 
 def check_dense_tables(tables, lens_a, lens_b, name):
@@ -157,20 +258,35 @@ def _check_pairs(pairs, replicas, seed):
     return pairs, replicas, seed
 
 
-def null_batch(pairs, params, replicas, seed=0, engine=None, hbm_budget_bytes=0, recurrence=0, fit=False, local=False, overlap=False):
+def null_batch(pairs, params, replicas, seed=0, engine=None, hbm_budget_bytes=0, recurrence=0, fit=False, local=False, overlap=False,
+               shuffle="mono"):
     """A null batch of ``pairs`` (``(seqA, seqB, strA, strB)`` each, as ``batch.make_batch`` takes them): every pair
     against ``replicas`` shuffles of its B.  -> ``engine.Batch``; ``run()`` it, then ``null_scores()`` /
     ``null_stats()``.  ``fit``: the replicas are scored as fit alignments (engine.Batch) -- the mode the observed
     scores they are compared with must have been scored in.  ``local``: likewise, as local alignments; excludes ``fit``.
-    ``overlap``: likewise, as overlap alignments; excludes both."""
+    ``overlap``: likewise, as overlap alignments; excludes both.  ``shuffle``: the null model, ``"mono"`` (THE
+    PERMUTATION) or ``"dinucleotide"`` (THE DINUCLEOTIDE PERMUTATION; ``Batch.set_null_model``)."""
+    null_model = check_shuffle(shuffle)
     _check_mode(fit, local, overlap)
     pairs, replicas, seed = _check_pairs(pairs, replicas, seed)
     from .batch import encode_flat
     from .engine import Batch, default_engine  # loads the HIP library (no CPU fallback)
     model, fb = encode_flat(pairs, params)
-    return Batch(engine or default_engine(), fb, None, model.s1, model.s2,
-                 params["gap_opening_cost"], params["gap_cost"], params["shift_cost"], params["max_shift"],
-                 hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence, null=(replicas, seed), fit=fit, local=local, overlap=overlap)
+    return _with_model(Batch(engine or default_engine(), fb, None, model.s1, model.s2,
+                             params["gap_opening_cost"], params["gap_cost"], params["shift_cost"], params["max_shift"],
+                             hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence, null=(replicas, seed), fit=fit, local=local,
+                             overlap=overlap), null_model)
+
+
+def _with_model(batch, null_model):
+    """A fresh null batch under the null model of that number (a batch that is refused the model is closed)."""
+    if null_model:
+        try:
+            batch.set_null_model(null_model)
+        except Exception:
+            batch.close()
+            raise
+    return batch
 
 
 def zscores_from_stats(score, stats):
@@ -214,11 +330,14 @@ def _zscores(npairs, observed, score_batch, null_batch):
     return zscores_from_stats(observed, _run_and_close(null_batch(), lambda nb: nb.null_stats(observed)))
 
 
-def zscores(pairs, params, replicas=100, seed=0, observed=None, engine=None, hbm_budget_bytes=0, recurrence=0, fit=False, local=False, overlap=False):
+def zscores(pairs, params, replicas=100, seed=0, observed=None, engine=None, hbm_budget_bytes=0, recurrence=0, fit=False, local=False, overlap=False,
+            shuffle="mono"):
     """z-scores of the pairs' optimal scores against ``replicas`` shuffles of each pair's B (``zscores_from_stats``).
     ``observed``: the pairs' real scores if the caller has them; else a score-only batch computes them first.
     ``fit``: fit alignments (engine.Batch) -- observed scores and replicas alike (``observed``, if given, must be fit
-    scores then).  ``local``: likewise, local alignments; excludes ``fit``.  ``overlap``: likewise, overlap alignments; excludes both."""
+    scores then).  ``local``: likewise, local alignments; excludes ``fit``.  ``overlap``: likewise, overlap alignments; excludes both.
+    ``shuffle``: the null model of the replicas, as for ``null_batch``; the observed scores do not depend on it."""
+    check_shuffle(shuffle)
     _check_mode(fit, local, overlap)
     pairs, replicas, seed = _check_pairs(pairs, replicas, seed)
     common = dict(engine=engine, hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence, fit=fit, local=local, overlap=overlap)
@@ -226,7 +345,7 @@ def zscores(pairs, params, replicas=100, seed=0, observed=None, engine=None, hbm
     def score_batch():
         from .batch import make_batch
         return make_batch(pairs, params, score_only=True, **common)
-    return _zscores(len(pairs), observed, score_batch, lambda: null_batch(pairs, params, replicas, seed=seed, **common))
+    return _zscores(len(pairs), observed, score_batch, lambda: null_batch(pairs, params, replicas, seed=seed, shuffle=shuffle, **common))
 
 
 def _check_feature_args(molecules, pair_index, replicas, seed):
@@ -249,23 +368,28 @@ def _check_feature_args(molecules, pair_index, replicas, seed):
 
 
 def null_feature_batch(molecules, pair_index, params, replicas, seed=0, engine=None, hbm_budget_bytes=0, recurrence=0,
-                       fit=False, local=False, overlap=False):
+                       fit=False, local=False, overlap=False, shuffle="mono"):
     """A FEATURE-form null batch: ``molecules`` (``(seq, (up, down, unp))`` each) and ``pair_index`` as
     ``batch.make_feature_batch`` takes them, every pair against ``replicas`` shuffles of its B -- letters and
     features, made on the GPU from the one uploaded copy of every molecule.  -> ``engine.Batch``; ``run()`` it, then
-    ``null_scores()`` / ``null_stats()``.  ``fit``, ``local``, ``overlap``: as for ``null_batch``."""
+    ``null_scores()`` / ``null_stats()``.  ``fit``, ``local``, ``overlap``, ``shuffle``: as for ``null_batch`` (the
+    dinucleotide model's letters are the sequence letters; the three numbers travel with their positions)."""
+    null_model = check_shuffle(shuffle)
     _check_mode(fit, local, overlap)
     molecules, pair_index, replicas, seed = _check_feature_args(molecules, pair_index, replicas, seed)
     from .batch import make_feature_batch
-    return make_feature_batch(molecules, pair_index, params, engine=engine, hbm_budget_bytes=hbm_budget_bytes,
-                              recurrence=recurrence, score_only=True, null=(replicas, seed), fit=fit, local=local, overlap=overlap)
+    return _with_model(make_feature_batch(molecules, pair_index, params, engine=engine, hbm_budget_bytes=hbm_budget_bytes,
+                                          recurrence=recurrence, score_only=True, null=(replicas, seed), fit=fit, local=local,
+                                          overlap=overlap), null_model)
 
 
 def zscores_features(molecules, pair_index, params, replicas=100, seed=0, observed=None, engine=None, hbm_budget_bytes=0,
-                     recurrence=0, fit=False, local=False, overlap=False):
+                     recurrence=0, fit=False, local=False, overlap=False, shuffle="mono"):
     """``zscores`` for RNA molecules with real-valued structure features: z-scores of the pairs' optimal scores
     against ``replicas`` shuffles of each pair's B (``zscores_from_stats``).  ``observed``: the pairs' real scores if
-    the caller has them; else ``make_feature_batch(score_only=True)`` computes them first.  ``fit``, ``local``, ``overlap``: as for ``zscores``."""
+    the caller has them; else ``make_feature_batch(score_only=True)`` computes them first.  ``fit``, ``local``, ``overlap``,
+    ``shuffle``: as for ``zscores``."""
+    check_shuffle(shuffle)
     _check_mode(fit, local, overlap)
     molecules, pair_index, replicas, seed = _check_feature_args(molecules, pair_index, replicas, seed)
     common = dict(engine=engine, hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence, fit=fit, local=local, overlap=overlap)
@@ -274,28 +398,33 @@ def zscores_features(molecules, pair_index, params, replicas=100, seed=0, observ
         from .batch import make_feature_batch
         return make_feature_batch(molecules, pair_index, params, score_only=True, **common)
     return _zscores(len(pair_index), observed, score_batch,
-                    lambda: null_feature_batch(molecules, pair_index, params, replicas, seed=seed, **common))
+                    lambda: null_feature_batch(molecules, pair_index, params, replicas, seed=seed, shuffle=shuffle, **common))
 
 
 def null_dense_batch(pairs, params, replicas, seed=0, mu1_dense=None, mu2_dense=None, engine=None, hbm_budget_bytes=0,
-                     recurrence=0, fit=False, local=False, overlap=False):
+                     recurrence=0, fit=False, local=False, overlap=False, shuffle="mono"):
     """A DENSE-form null batch: ``pairs`` and their tables as ``batch.make_batch`` takes them (one integer table of shape
     (len A, len B) per pair in ``mu1_dense`` and / or ``mu2_dense``), every pair against ``replicas`` shuffles of its B --
     the tables' columns, and the codes of a form left in LOOKUP form, permuted on the GPU from the one uploaded copy.
-    -> ``engine.Batch``; ``run()`` it, then ``null_scores()`` / ``null_stats()``.  ``fit``, ``local``, ``overlap``: as for ``null_batch``."""
+    -> ``engine.Batch``; ``run()`` it, then ``null_scores()`` / ``null_stats()``.  ``fit``, ``local``, ``overlap``, ``shuffle``:
+    as for ``null_batch``.  The dinucleotide model's letters are B's sequence codes, so it needs mu1 in LOOKUP form: a dense
+    mu1 has no letters, and the library refuses (E_UNSUPPORTED)."""
+    null_model = check_shuffle(shuffle)
     _check_mode(fit, local, overlap)
     pairs, replicas, seed = check_dense_args(pairs, (replicas, seed), mu1_dense, mu2_dense)
     from .batch import make_batch
-    return make_batch(pairs, params, engine=engine, hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence,
-                      score_only=True, mu1_dense=mu1_dense, mu2_dense=mu2_dense, null_dense=(replicas, seed), fit=fit, local=local, overlap=overlap)
+    return _with_model(make_batch(pairs, params, engine=engine, hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence,
+                                  score_only=True, mu1_dense=mu1_dense, mu2_dense=mu2_dense, null_dense=(replicas, seed), fit=fit,
+                                  local=local, overlap=overlap), null_model)
 
 
 def zscores_dense(pairs, params, replicas=100, seed=0, mu1_dense=None, mu2_dense=None, observed=None, engine=None,
-                  hbm_budget_bytes=0, recurrence=0, fit=False, local=False, overlap=False):
+                  hbm_budget_bytes=0, recurrence=0, fit=False, local=False, overlap=False, shuffle="mono"):
     """``zscores`` for pairs scored through dense tables (a PSSM as ``mu1_dense``, structure scores as ``mu2_dense``):
     z-scores of the pairs' optimal scores against ``replicas`` shuffles of each pair's B (``zscores_from_stats``).
     ``observed``: the pairs' real scores if the caller has them; else ``make_batch(score_only=True)`` with the same
-    tables computes them first.  ``fit``, ``local``, ``overlap``: as for ``zscores``."""
+    tables computes them first.  ``fit``, ``local``, ``overlap``, ``shuffle``: as for ``zscores``."""
+    check_shuffle(shuffle)
     _check_mode(fit, local, overlap)
     pairs, replicas, seed = check_dense_args(pairs, (replicas, seed), mu1_dense, mu2_dense)
     common = dict(mu1_dense=mu1_dense, mu2_dense=mu2_dense, engine=engine, hbm_budget_bytes=hbm_budget_bytes,
@@ -304,4 +433,4 @@ def zscores_dense(pairs, params, replicas=100, seed=0, mu1_dense=None, mu2_dense
     def score_batch():
         from .batch import make_batch
         return make_batch(pairs, params, score_only=True, **common)
-    return _zscores(len(pairs), observed, score_batch, lambda: null_dense_batch(pairs, params, replicas, seed=seed, **common))
+    return _zscores(len(pairs), observed, score_batch, lambda: null_dense_batch(pairs, params, replicas, seed=seed, shuffle=shuffle, **common))

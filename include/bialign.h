@@ -293,7 +293,44 @@ typedef struct bialign_feature_info {
  *     mu1'[(i-1)*m + x] = mu1[(i-1)*m + perm[x]]      (dense mu1)
  *     mu2'[(k-1)*m + x] = mu2[(k-1)*m + perm[x]]      (dense mu2)
  *     seq'[x] = seq_b[perm[x]],  cls'[x] = cls_b[perm[x]]   (whichever of mu1 / mu2 is in LOOKUP form)
- * Values are moved, never recomputed.  A is never shuffled; m = 1 gives the identity. */
+ * Values are moved, never recomputed.  A is never shuffled; m = 1 gives the identity.
+ *
+ * THE DINUCLEOTIDE PERMUTATION (normative; the second null model, bialign_batch_set_null_model).  THE PERMUTATION keeps
+ * B's single-letter composition and nothing else; neighbouring letters of nucleic acids are correlated, and a null that
+ * destroys that inflates z-scores (Altschul & Erickson 1985, Workman & Krogh 1999).  This one keeps the count of every
+ * ordered pair of neighbouring letters exactly.  Same mix and h(seed, p, r); the draw is
+ *     uni(salt, bound) = (uint64(mix(h + salt)) * bound) >> 32       in [0, bound);  h + salt mod 2^32
+ * Letters: B's sequence codes (seq_b), renumbered 0, 1, 2, ... in order of first occurrence in B -- so perm depends on
+ * (seed, p, r) and B's letter pattern only, not on the score model's code order, and the host can restate it from the plain
+ * string.  A position's structure class, its three feature numbers and its table columns are no part of the letter: they
+ * travel with the position, as above.  m <= 2: perm is the identity.  Otherwise
+ *  1. Edges.  Edge e, 0 <= e <= m-2, runs from position e to e+1: tail a(e) = B[e], head b(e) = B[e+1].  cnt[x] = edges
+ *     with tail x, off[x] = sum of cnt[y] over y < x, L = the edges sorted by (tail, e): letter x owns
+ *     L[off[x] .. off[x]+cnt[x]), in increasing e.  z = B[m-1].
+ *  2. Last exits (Wilson's algorithm, capped).  tree = {z}, s = 0.  For the letters x ascending, skipping those with
+ *     cnt[x] = 0 or in the tree:  u = x;  while u is not in the tree: { if s = CAP give up;  last[u] = uni(0x80000000 + s,
+ *     cnt[u]);  s += 1;  u = b(L[off[u] + last[u]]) };  then walk again from x along last[] and add every letter met to
+ *     the tree, until the tree is reached.  (L is still the sorted list here.)  CAP = 4096 draws per replica.  On giving
+ *     up all choices so far are dropped and last[x] = cnt[x]-1 for every x != z with cnt[x] > 0: the original molecule's
+ *     own last exits, which always form a tree.
+ *  3. Order of exits.  For the letters x ascending with cnt[x] > 0:  if x != z, element last[x] is taken out of x's list
+ *     (the others keep their order) and put at the list's end, and r = cnt[x]-1;  if x = z, r = cnt[x].  Then for
+ *     t = r-1 down to 1: swap(L[off[x] + t], L[off[x] + uni(off[x] + t, t+1)]).
+ *  4. Walk.  perm[0] = 0, cur = B[0], all ptr[] = 0.  For pos = 1 .. m-1:  e = L[off[cur] + ptr[cur]];  ptr[cur] += 1;
+ *     perm[pos] = e+1;  cur = b(e).
+ * Replica r of pair p is seq'[x] = seq_b[perm[x]], and classes, features and table columns go through the same perm.
+ * Guarantees: perm is a permutation with perm[0] = 0; the replica has exactly B's count of every ordered letter pair, hence
+ * B's count of every letter and B's first and last letter.  Without the cap every such sequence is equally likely
+ * (Altschul-Erickson, BEST theorem); the capped fallback is valid but not uniform.  (Over 2460 random molecules --
+ * alphabets of 1, 2, 4 and 20 letters, lengths 1 to 2000, a skewed composition per length -- the largest s was 181: the
+ * fallback was never taken.)  The cap is there so that no loop on the device is unbounded.
+ * Which letter carries the property: LOOKUP and FEATURE form, and DENSE form with mu1 in LOOKUP form, the sequence code;
+ * a dense mu1 has no letters, and the model is refused.  The kernel keeps the edge list and perm (uint16 each), the
+ * renumbered letters (uint8) and 3584 bytes of per-letter arrays in one workgroup's 160 KiB of LDS: 5 * len_b + 3584 bytes,
+ * so len_b <= BIALIGN_NULL_DINUCLEOTIDE_MAX_LEN. */
+#define BIALIGN_NULL_MONO 0
+#define BIALIGN_NULL_DINUCLEOTIDE 1
+#define BIALIGN_NULL_DINUCLEOTIDE_MAX_LEN 32050
 typedef struct bialign_null_spec {
   int32_t replicas; /* R, 1..65535 */
   uint32_t seed;
@@ -537,6 +574,16 @@ int bialign_batch_get_null_info(const bialign_batch* b, bialign_null_info* info)
 /* Test hook: the codes of one replica of one pair's B as the sweep reads them (len_b bytes each; the shuffle kernel is
  * run for that replica). */
 int bialign_batch_dump_null_codes(bialign_batch* b, int32_t pair, int32_t replica, uint8_t* seq, uint8_t* cls);
+
+/* The null model of a null batch of any form (added symbols: no existing struct or function changes): BIALIGN_NULL_MONO,
+ * THE PERMUTATION, which a batch has until told otherwise, or BIALIGN_NULL_DINUCLEOTIDE, THE DINUCLEOTIDE PERMUTATION.
+ * Valid between runs (a pending run is waited for); the model holds from the next run on, and the three dumps
+ * (dump_null_codes / _features / _tables) follow it.  Refused before any device call, the batch keeping its model: not a
+ * null batch, or an unknown model: BIALIGN_E_INVALID; BIALIGN_NULL_DINUCLEOTIDE on a DENSE-form null batch whose mu1 is
+ * dense (B has no letters), or with a B molecule of more than BIALIGN_NULL_DINUCLEOTIDE_MAX_LEN residues:
+ * BIALIGN_E_UNSUPPORTED.  Under BIALIGN_NULL_MONO a LOOKUP-form null batch takes B of any length, as before. */
+int bialign_batch_set_null_model(bialign_batch* b, int32_t model);
+int bialign_batch_get_null_model(const bialign_batch* b, int32_t* model);
 
 /* A null batch with mu2 in FEATURE form: the union of bialign_batch_create_features and bialign_batch_create_null (new in
  * ABI 10 as added symbols: no existing struct or function changes).  B's codes and features are uploaded once; the GPU
