@@ -75,12 +75,13 @@ int launch_fill(bialign_batch* b, const DeviceBatch& v, int first, int count) {
   });
 }
 
-// Local alignments: behind a sweep, the pairs' keys become their scores and ends (bialign_local.hpp)
-int launch_local_finish(const bialign_batch* b, const DeviceBatch& v, int first, int count) {
+// Batches with an end key (BatchPlan::end_key: local, score-only overlap): behind a sweep, the pairs' keys become their
+// scores and ends (bialign_free_ends.hpp)
+int launch_end_key_finish(const bialign_batch* b, const DeviceBatch& v, int first, int count) {
   constexpr int BLOCK = 256;
   DeviceBatch w = v;
   w.order = v.order + first;
-  return launch(local_finish_kernel<BLOCK>, dim3((count + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, b->eng->stream, w, count);
+  return launch(end_key_finish_kernel<BLOCK>, dim3((count + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, b->eng->stream, w, count);
 }
 
 // Lean traceback of one chunk: as many (re-sweep, walk) rounds as its longest pair has strips.
@@ -331,7 +332,7 @@ int upload_inputs(bialign_batch* b, const bialign_scoring* sc, const bialign_pai
   }
   HIP_TRY(b->d_scores.alloc(pr->npairs));
   if (b->free_ends()) HIP_TRY(b->d_span.alloc(4 * (size_t)pr->npairs));
-  if (b->end_key()) HIP_TRY(b->d_local_key.alloc((size_t)pr->npairs));
+  if (b->end_key()) HIP_TRY(b->d_end_key.alloc((size_t)pr->npairs));
   if (b->lean_trace || b->level_trace) HIP_TRY(b->d_tstate.alloc(pr->npairs));
   HIP_TRY(b->d_tlen.alloc(pr->npairs));
   HIP_TRY(b->d_complete.alloc(pr->npairs));
@@ -637,7 +638,7 @@ static int enqueue_run(bialign_batch* b, uint32_t flags) {
   HIP_TRY(hipMemsetAsync(b->d_err.p, 0, sizeof(int32_t), st));  // the flag is per run
   if (b->free_ends()) HIP_TRY(hipMemsetAsync(b->d_span.p, 0xff, sizeof(int32_t) * b->d_span.n, st));  // spans: -1 until a kernel writes them
   if (b->end_key())  // keys: zero, below every key a sweep folds in
-    HIP_TRY(hipMemsetAsync(b->d_local_key.p, 0, sizeof(unsigned long long) * b->npairs, st));
+    HIP_TRY(hipMemsetAsync(b->d_end_key.p, 0, sizeof(unsigned long long) * b->npairs, st));
   b->hits_pending = false;
   if (b->hits_on) {  // hit search: its results are per run, like the spans
     while ((int)b->hit_evs.size() < 2 * nchunks) {
@@ -666,7 +667,7 @@ static int enqueue_run(bialign_batch* b, uint32_t flags) {
     }
     HIP_TRY(hipEventRecord(b->evs[3 * c], st));
     int rc = launch_fill(b, v, first, count);
-    if (rc == BIALIGN_OK && b->end_key()) rc = launch_local_finish(b, v, first, count);  // scores and ends (local: in every storage mode)
+    if (rc == BIALIGN_OK && b->end_key()) rc = launch_end_key_finish(b, v, first, count);  // scores and ends (local: in every storage mode)
     if (rc) return rc;
     HIP_TRY(hipEventRecord(b->evs[3 * c + 1], st));
     if (!b->lean) {  // (with LEAN records the sweep itself wrote the scores)

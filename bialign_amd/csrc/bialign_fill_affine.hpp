@@ -45,7 +45,7 @@ __device__ __forceinline__ void store_chunk(int32_t* p, v4i v, bool wt) {
 //   PACK: interior steps store packed records, the others full records in the pair's second region (Pack<S>).
 //   DENSE1: mu1(i,j) from the pair's dense table (Mu1Feed) instead of s1 and the sequence codes, which are then not staged.
 //   LOCAL (local alignments, BIALIGN_BATCH_LOCAL): the lanes with a = 0 floor state 8 of their b = 0 point -- the lattice
-//   point (i, j, i, j) -- against 0 in every step, keep the best E of their row in registers (LocalBest) and fold it into
+//   point (i, j, i, j) -- against 0 in every step, keep the best E of their row in registers (RowBest) and fold it into
 //   the pair's key when they change strip and at the end.  Every line of it sits behind `if constexpr (LOCAL)`.
 template <int S, bool BETA_NONPOS, int TW, bool XCU, bool DENSE = false, bool LEAN = false, bool RESW = false,
           bool PACK = false, bool DENSE1 = false, bool LOCAL = false>
@@ -122,7 +122,7 @@ __global__ void __launch_bounds__(64 * TW) fill_affine_kernel(const DeviceBatch 
   uint8_t* cb = sb + (DENSE1 ? 0 : mpad);                   // cls B,       [l-1+PADB]
 
   for (int t = threadIdx.x; t < TW * PERW; t += 64 * TW) smem[t] = SENT;
-  if (threadIdx.x < LDS_PROG_WORDS) prog_lds[threadIdx.x] = prog_word_init(threadIdx.x, A.fit);
+  if (threadIdx.x < LDS_PROG_WORDS) prog_lds[threadIdx.x] = prog_word_init(threadIdx.x, A.free_ends);
   for (int t = threadIdx.x; t < k1 * k1; t += 64 * TW) s1[t] = A.s1[t];
   for (int t = threadIdx.x; t < k2 * k2; t += 64 * TW) s2[t] = A.s2[t];
   if (!DIET)
@@ -330,7 +330,7 @@ __global__ void __launch_bounds__(64 * TW) fill_affine_kernel(const DeviceBatch 
     fetch_codes();
   }
   int fit_best = SENT, fit_j = 0;  // LEAN fit batches: the best end cell of row n so far and its column
-  LocalBest loc;                                    // LOCAL: this lane's row (i, ., i, .)
+  RowBest loc;                                      // LOCAL: this lane's row (i, ., i, .)
   const bool loc_lane = live && !ghost && aa == S;  // ... if it holds one
 
   // One step of the sweep.  INTERIOR steps (every lane's lattice points have all
@@ -549,8 +549,13 @@ __global__ void __launch_bounds__(64 * TW) fill_affine_kernel(const DeviceBatch 
       }
 #pragma unroll
       for (int q = 0; q < 9; ++q) outv[bb * 9 + q] = M[q];
-      if (LEAN && !LOCAL && bb == S) {  // score-only: the end cell (n,m,n,m) is all the host wants (pyx:509)
-        if (!A.fit) {
+      // score-only: the end cells are all the host wants.  This is lean_end_rule (bialign_free_ends.hpp: the rule, its
+      // tie-break and the reasons stand there) in this kernel's own text, for a measured reason: the max_shift 4 and 5
+      // instances sit at the 512-VGPR limit with 84 .. 660 bytes of scratch, and with the call 9 of those 17 gained 4 ..
+      // 32 bytes (8 lost some) and the max_shift 4 overlap sweep (256 pairs x 512, cross-CU team of 2) took 75.03 .. 75.41
+      // ms, median 75.20, against 74.85 .. 75.11.  With this text they keep their registers.
+      if (LEAN && !LOCAL && bb == S) {
+        if (!A.free_ends) {
           if (live && !ghost && aa == S && i == n && jj == m) {
             int best = M[0];
 #pragma unroll
@@ -558,27 +563,23 @@ __global__ void __launch_bounds__(64 * TW) fill_affine_kernel(const DeviceBatch 
             A.scores[pid] = best;
           }
         } else if (live && !ghost && aa == S && i == n && (INTERIOR || (jj >= 0 && jj <= m))) {
-          // fit: row n has one owner, the lane of (n, j, n, j), which passes over the columns in order (interior steps
-          // included): the best end cell and the smallest column that attains it stay in its registers
           int best = M[0];
 #pragma unroll
           for (int q = 1; q < 9; ++q) best = imax(best, M[q]);
           if (best > fit_best) fit_best = best, fit_j = jj;
-          if (!INTERIOR && jj == m) {  // (a boundary step: an interior step's owner lanes stay left of column m - S)
-            if (A.fit & FREE_A_ENDS) {  // overlap: row n's best goes into the pair's key, beside the other rows' end cells
-              atomicMax(A.local_key + pid, local_key_of(fit_best, n, fit_j, m));
+          if (!INTERIOR && jj == m) {
+            if (A.free_ends & FREE_A_ENDS) {
+              atomicMax(A.end_key + pid, end_key_of(fit_best, n, fit_j, m));
             } else {
               A.scores[pid] = fit_best;
-              A.fit_span[2 * pid + 1] = fit_j;
+              A.span[2 * pid + 1] = fit_j;
             }
           }
-        } else if (!INTERIOR && (A.fit & FREE_A_ENDS) && live && !ghost && aa == S && act_row && jj == m) {
-          // overlap: (i, m, i, m), i < n, is an end cell too; its row's owner folds it into the pair's key, which
-          // local_finish_kernel decodes.  (A boundary step: an interior step's owner lanes stay left of column m - S.)
+        } else if (!INTERIOR && (A.free_ends & FREE_A_ENDS) && live && !ghost && aa == S && act_row && jj == m) {
           int best = M[0];
 #pragma unroll
           for (int q = 1; q < 9; ++q) best = imax(best, M[q]);
-          atomicMax(A.local_key + pid, local_key_of(best, i, m, m));
+          atomicMax(A.end_key + pid, end_key_of(best, i, m, m));
         }
       }
       if (PACK && INTERIOR) {
@@ -758,7 +759,7 @@ __global__ void __launch_bounds__(64 * TW) fill_affine_kernel(const DeviceBatch 
     ++jj;
     if (!RESW && !INTERIOR && jj == P) {  // a re-sweep ends inside its one strip; an interior step never ends a strip (phase <= m - S)
       jj = 0;
-      if constexpr (LOCAL) loc.fold(A.local_key + pid, i, m);
+      if constexpr (LOCAL) loc.fold(A.end_key + pid, i, m);
       ++strip;
       rec_base += (T - 1) * P;
       set_row(strip);
@@ -800,7 +801,7 @@ __global__ void __launch_bounds__(64 * TW) fill_affine_kernel(const DeviceBatch 
       ++g;
     }
   }
-  if constexpr (LOCAL) loc.fold(A.local_key + pid, i, m);
+  if constexpr (LOCAL) loc.fold(A.end_key + pid, i, m);
   if (PACK && __builtin_amdgcn_ballot_w64(live && !ghost && (unsigned)pk_all > 0xffffu) != 0 && L == 0) atomicOr(A.errflag, 2);
   if (XCU || TW > 1) {  // everything this wave wrote is acknowledged: release the partner for good
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -70,7 +70,7 @@ __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch 
   uint8_t* cb = sb + (DENSE1 ? 0 : mpad);
 
   for (int t = threadIdx.x; t < TW * PERW; t += 64 * TW) smem[t] = SENT;
-  if (threadIdx.x < LDS_PROG_WORDS) prog[threadIdx.x] = prog_word_init(threadIdx.x, A.fit);
+  if (threadIdx.x < LDS_PROG_WORDS) prog[threadIdx.x] = prog_word_init(threadIdx.x, A.free_ends);
   for (int t = threadIdx.x; t < k1 * k1; t += 64 * TW) s1[t] = A.s1[t];
   for (int t = threadIdx.x; t < k2 * k2; t += 64 * TW) s2[t] = A.s2[t];
   for (int t = threadIdx.x; t < n; t += 64 * TW) {
@@ -171,7 +171,7 @@ __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   int vm_younger = 0;  // see the affine kernel
   int fit_best = SENT, fit_j = 0;  // LEAN fit batches: the best end cell of row n so far and its column
-  LocalBest loc;                                    // LOCAL: this lane's row (i, ., i, .)
+  RowBest loc;                                      // LOCAL: this lane's row (i, ., i, .)
   const bool loc_lane = live && !ghost && aa == S;  // ... if it holds one
 
   for (int g = 0; g < H; ++g) {
@@ -265,20 +265,11 @@ __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch 
 
     const int rec = g + rec_base;
     if constexpr (LOCAL) loc.see(loc_lane && tile_act, outv[S], jj);  // E(i, j) = the value of (i, j, i, j)
-    if (LEAN && !LOCAL && !A.fit && live && !ghost && aa == S && i == n && jj == m) A.scores[pid] = outv[S];  // pyx:471
-    if (LEAN && !LOCAL && A.fit && live && !ghost && aa == S && i == n && jj >= 0 && jj <= m) {
-      // fit: row n has one owner, the lane of (n, j, n, j), which passes over the columns in order: the best end cell
-      // and the smallest column that attains it stay in its registers
-      if (outv[S] > fit_best) fit_best = outv[S], fit_j = jj;
-      if (jj == m && !(A.fit & FREE_A_ENDS)) {
-        A.scores[pid] = fit_best;
-        A.fit_span[2 * pid + 1] = fit_j;
-      }
-    }
-    if (LEAN && !LOCAL && (A.fit & FREE_A_ENDS) && live && !ghost && aa == S && act_row && jj == m)
-      // overlap: the end cells are (i, m), i < n, and row n.  Every row's owner folds its own at column m -- row n's its
-      // best -- into the pair's key, which local_finish_kernel decodes
-      atomicMax(A.local_key + pid, i == n ? local_key_of(fit_best, n, fit_j, m) : local_key_of(outv[S], i, m, m));
+    // score-only: the end cells are all the host wants (pyx:471).  This kernel has no interior variant of a step.  (Row
+    // n's owner is on an active row -- set_row's act_row is live && 0 <= i, k <= n, and k = i where aa == S -- so the
+    // rule's two folds at column m amount to one fold behind `act_row && jj == m` that selects on i == n.)
+    if (LEAN && !LOCAL)
+      lean_end_rule<false>(A, pid, n, m, live && !ghost && aa == S, act_row, i, jj, fit_best, fit_j, [&] { return outv[S]; });
     const int pad_idx = L < W ? L : (L >= R * W ? W + (L - R * W) : 64);
     const bool pad_lane = !LEAN && pad_idx < R_::SLP - R_::SL;  // spare lanes owning a pad slot (Rec::SLP)
     const bool do_store = __builtin_amdgcn_ballot_w64(tile_act && !ghost) != 0 &&
@@ -319,13 +310,13 @@ __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch 
     ++jj;
     if (!RESW && jj == P) {
       jj = 0;
-      if constexpr (LOCAL) loc.fold(A.local_key + pid, i, m);
+      if constexpr (LOCAL) loc.fold(A.end_key + pid, i, m);
       ++strip;
       rec_base += (T - 1) * P;
       set_row(strip);
     }
   }
-  if constexpr (LOCAL) loc.fold(A.local_key + pid, i, m);
+  if constexpr (LOCAL) loc.fold(A.end_key + pid, i, m);
   if (T > 1) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (L == 0) prog_put(0x7fffffff);

@@ -93,7 +93,7 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
   uint8_t* cb = sb + mpad;                                  // cls B,       [l-1+PADB]
 
   for (int t = threadIdx.x; t < NW * PERW + SENTBLK; t += 64 * NW) smem[t] = SENT;
-  if (threadIdx.x < LDS_PROG_WORDS) smem[NW * PERW + SENTBLK + threadIdx.x] = prog_word_init(threadIdx.x, A.fit);
+  if (threadIdx.x < LDS_PROG_WORDS) smem[NW * PERW + SENTBLK + threadIdx.x] = prog_word_init(threadIdx.x, A.free_ends);
   if (!LEAN)
     for (int t = threadIdx.x; t < GF::OFFTAB_DW; t += 64 * NW) offtab[t] = (int32_t)GF::lane_offset(t >> 6, t & 63);
   for (int t = threadIdx.x; t < k1 * k1; t += 64 * NW) s1[t] = A.s1[t];
@@ -428,41 +428,15 @@ __global__ void __launch_bounds__(64 * TW * PPW, 3) fill_affine_slim_kernel(cons
 #pragma unroll
         for (int q = 0; q < 9; ++q) outv[PACKED ? 0 : bb * 9 + q] = M[q];
       }
-      if (LEAN && bb == S) {  // score-only: the end cell (n,m,n,m) is all the host wants (pyx:509)
-        // (an interior step is never at column m; its jj is not the column either: see s_adv)
-        if (!INTERIOR && live && !ghost && aa == S && i == n && jj == m && !A.fit) {
+      if (LEAN && bb == S)  // score-only: the end cells are all the host wants
+        // (an interior step's jj is not the column: see s_adv)
+        lean_end_rule<INTERIOR>(A, pid, n, m, live && !ghost && aa == S, act_row, i, INTERIOR ? jj + s_adv : jj, fit_best,
+                                fit_j, [&] {
           int best = M[0];
 #pragma unroll
           for (int q = 1; q < 9; ++q) best = imax(best, M[q]);
-          A.scores[pid] = best;
-        }
-        if (A.fit) {
-          // fit: row n has one owner, the lane of (n, j, n, j), which passes over the columns in order (interior steps
-          // included): the best end cell and the smallest column that attains it stay in its registers
-          const int col = INTERIOR ? jj + s_adv : jj;
-          if (live && !ghost && aa == S && i == n && (INTERIOR || (col >= 0 && col <= m))) {
-            int best = M[0];
-#pragma unroll
-            for (int q = 1; q < 9; ++q) best = imax(best, M[q]);
-            if (best > fit_best) fit_best = best, fit_j = col;
-            if (!INTERIOR && col == m) {
-              if (A.fit & FREE_A_ENDS) {  // overlap: row n's best goes into the pair's key, beside the other rows' end cells
-                atomicMax(A.local_key + pid, local_key_of(fit_best, n, fit_j, m));
-              } else {
-                A.scores[pid] = fit_best;
-                A.fit_span[2 * pid + 1] = fit_j;
-              }
-            }
-          } else if (!INTERIOR && (A.fit & FREE_A_ENDS) && live && !ghost && aa == S && act_row && col == m) {
-            // overlap: (i, m, i, m), i < n, is an end cell too; its row's owner folds it into the pair's key, which
-            // local_finish_kernel decodes.  (A boundary step: an interior step's owner lanes stay left of column m - S.)
-            int best = M[0];
-#pragma unroll
-            for (int q = 1; q < 9; ++q) best = imax(best, M[q]);
-            atomicMax(A.local_key + pid, local_key_of(best, i, m, m));
-          }
-        }
-      }
+          return best;
+        });
       if (PACKED) {
         // packed record (Pack<S>): dword 0 = base, then the low halves of all values but the anchor; a piece of it leaves
         // as soon as its last value exists

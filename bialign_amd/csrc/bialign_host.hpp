@@ -89,7 +89,7 @@ struct bialign_batch : bialign::BatchPlan {  // the plan (bialign_plan.hpp), and
   // free ends (BatchPlan::free_ends): [npairs][4] spans, -1 ahead of every run.  Fit: the first 2 * npairs words as
   // [npairs][2] = (start_b, end_b); local and overlap: (start_a, end_a, start_b, end_b)
   DevBuf<int32_t> d_span;
-  DevBuf<unsigned long long> d_local_key;  // BatchPlan::end_key: [npairs] best-end keys, zeroed ahead of every run
+  DevBuf<unsigned long long> d_end_key;  // BatchPlan::end_key: [npairs] best-end keys, zeroed ahead of every run
   int last_team = 1;  // waves per pair of the last fill launch (negative: cross-CU team)
   // Cross-CU teams need every workgroup of the launch resident at once.  The grid is sized from the
   // occupancy the runtime reports for the actual kernel (xcu_resident, cached per LEAN flavour) and
@@ -199,12 +199,13 @@ struct bialign_batch : bialign::BatchPlan {  // the plan (bialign_plan.hpp), and
     v.prio_mode = getenv("BIALIGN_PRIO") ? atoi(getenv("BIALIGN_PRIO")) : 1;
     v.spin_limit = 1 << 20;  // waves of one workgroup are co-resident by construction: a timeout there is a bug
     // whose end gaps are free in the sweeps of the global recurrence: B's (fit), both molecules' (overlap)
-    v.fit = mode == bialign::AlignMode::Fit       ? bialign::FREE_B_ENDS
-            : mode == bialign::AlignMode::Overlap ? bialign::FREE_B_ENDS | bialign::FREE_A_ENDS
-                                                  : 0;
+    v.free_ends = mode == bialign::AlignMode::Fit       ? bialign::FREE_B_ENDS
+                  : mode == bialign::AlignMode::Overlap ? bialign::FREE_B_ENDS | bialign::FREE_A_ENDS
+                                                        : 0;
     v.local = mode == bialign::AlignMode::Local;
-    v.fit_span = v.local_span = d_span.p;
-    v.local_key = d_local_key.p;
+    v.reserved0 = nullptr;
+    v.span = d_span.p;
+    v.end_key = d_end_key.p;
     return v;
   }
 };

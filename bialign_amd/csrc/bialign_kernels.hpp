@@ -46,7 +46,7 @@
 #include "bialign_types.hpp"
 #include "bialign_feed.hpp"
 #include "bialign_affine_point.hpp"
-#include "bialign_local.hpp"
+#include "bialign_free_ends.hpp"
 #include "bialign_fill_affine.hpp"
 #include "bialign_fill_slim.hpp"
 #include "bialign_fill_linear.hpp"

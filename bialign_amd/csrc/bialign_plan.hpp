@@ -86,7 +86,7 @@ struct BatchPlan {
   // sweeps of its own (launch_fill_*_local, best-end keys behind them): no packed records, slim kernel or cross-CU team
   // (decide_pack, slim_available, team_shape); beta <= 0 in the affine recurrence
   bool own_sweeps() const { return mode == AlignMode::Local; }
-  // its sweeps raise the pair's best-end key (bialign_local.hpp), which local_finish_kernel decodes behind them: local
+  // its sweeps raise the pair's best-end key (bialign_free_ends.hpp), which end_key_finish_kernel decodes behind them: local
   // alignments always, overlap alignments where no traceback prologue scans the end cells (SCORE_ONLY).  It sizes and
   // zeroes the key buffer, launches the finish kernel and bounds n + m (the key's position is 32 bits wide)
   bool end_key() const { return mode == AlignMode::Local || (mode == AlignMode::Overlap && lean); }
@@ -603,10 +603,10 @@ inline int plan_pairs(const bialign_pairs* pr, const NullPlan* nul, int64_t colm
     if ((2 * ((int64_t)n + m) + 8) * colmax >= (1 << 28))
       return fail(BIALIGN_E_RANGE, "pair %d: scores may leave the int32 safety window (n+m=%d, column bound %lld)", shown(p),
                   n + m, (long long)colmax);
-    // the end's position in the pair's key is 32 bits (bialign_local.hpp); an overlap batch is held to the bound in full
+    // the end's position in the pair's key is 32 bits (bialign_free_ends.hpp); an overlap batch is held to the bound in full
     // storage too, so that what the mode accepts does not depend on the storage
-    if ((b.end_key() || b.mode == AlignMode::Overlap) && n + m >= LOCAL_MAX_NM)
-      return fail(BIALIGN_E_UNSUPPORTED, "pair %d: %s takes n + m < %d (n+m=%d)", shown(p), b.mode_name(), LOCAL_MAX_NM, n + m);
+    if ((b.end_key() || b.mode == AlignMode::Overlap) && n + m >= END_KEY_MAX_NM)
+      return fail(BIALIGN_E_UNSUPPORTED, "pair %d: %s takes n + m < %d (n+m=%d)", shown(p), b.mode_name(), END_KEY_MAX_NM, n + m);
     if (nul) {  // the reduction's int64 sum of squares: replicas * bound^2 with the window's bound on |score| (< 2^28)
       const int64_t bound = (2 * ((int64_t)n + m) + 8) * colmax;
       if (bound > 0 && bound * bound > INT64_MAX / nul->replicas)

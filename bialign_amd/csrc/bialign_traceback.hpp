@@ -61,8 +61,8 @@ __device__ __forceinline__ int wave_min64(int v) {  // min over the wave's 64 la
   return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
              min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
 }
-// Fit and overlap alignments (DeviceBatch::fit), end rule of the full-storage tracebacks.  The end cells in position
-// order: x < n -> (x, m), else (n, x - n), for x = 0 .. n + m; that is the order by (i, j), and the order of local_key_of.
+// Fit and overlap alignments (DeviceBatch::free_ends), end rule of the full-storage tracebacks.  The end cells in position
+// order: x < n -> (x, m), else (n, x - n), for x = 0 .. n + m; that is the order by (i, j), and the order of end_key_of.
 // An overlap batch takes all of them, a fit batch those of row n (x >= n).  The wave's lanes stride over the positions,
 // read each cell's value through the kernel's own cell addressing (end_cell(i, j)), and reduce to the best one and the
 // smallest position that attains it.  Column m and row n are scanned by a loop each, so that a fit batch runs the loop
@@ -149,24 +149,24 @@ __host__ __device__ __forceinline__ AffineCandidate affine_candidate(int st, int
   return g;
 }
 
-// Start of a walk in the free-end modes: the end local_finish_kernel decoded (LOCAL), or the best end cell by
+// Start of a walk in the free-end modes: the end that end_key_finish_kernel decoded (LOCAL), or the best end cell by
 // free_end_scan over end_value(i, j), the kernel's best layer value at (i, j, i, j) (FIT, OVERLAP); the spans are set to
 // (start -1, the end) in the mode's layout.  A global batch leaves (*end_a, *end_b) alone.
 template <typename EndValue>
 __device__ __forceinline__ void free_end_start(const DeviceBatch& A, int pid, int n, int m, bool fit, bool ovl, bool local, int c,
                                                EndValue&& end_value, int* end_a, int* end_b) {
   if (local) {
-    *end_a = A.local_span[4 * (int64_t)pid + 1];
-    *end_b = A.local_span[4 * (int64_t)pid + 3];
+    *end_a = A.span[4 * (int64_t)pid + 1];
+    *end_b = A.span[4 * (int64_t)pid + 3];
   }
   if (fit) {
     free_end_scan(n, m, ovl, c, end_value, end_a, end_b);
     if (c == 0 && !ovl) {
-      A.fit_span[2 * pid] = -1;
-      A.fit_span[2 * pid + 1] = *end_b;
+      A.span[2 * pid] = -1;
+      A.span[2 * pid + 1] = *end_b;
     }
-    if (c == 0 && ovl) {  // (start_a, end_a, start_b, end_b), as local_finish_kernel leaves them
-      int32_t* span = A.local_span + 4 * (int64_t)pid;
+    if (c == 0 && ovl) {  // (start_a, end_a, start_b, end_b), as end_key_finish_kernel leaves them
+      int32_t* span = A.span + 4 * (int64_t)pid;
       span[0] = -1, span[1] = *end_a, span[2] = -1, span[3] = *end_b;
     }
   }
@@ -175,9 +175,9 @@ __device__ __forceinline__ void free_end_start(const DeviceBatch& A, int pid, in
 // One test per mode: `ovl || local` is a third flag that lives through the column loop, two SGPRs that take the packed
 // affine kernels from 100 to 102 and so from eight waves to seven.
 __device__ __forceinline__ void publish_free_starts(const DeviceBatch& A, int pid, bool fit, bool ovl, bool local, int i, int j) {
-  if (fit && !ovl) A.fit_span[2 * pid] = j;
-  if (ovl) A.local_span[4 * (int64_t)pid] = i, A.local_span[4 * (int64_t)pid + 2] = j;
-  if (local) A.local_span[4 * (int64_t)pid] = i, A.local_span[4 * (int64_t)pid + 2] = j;
+  if (fit && !ovl) A.span[2 * pid] = j;
+  if (ovl) A.span[4 * (int64_t)pid] = i, A.span[4 * (int64_t)pid + 2] = j;
+  if (local) A.span[4 * (int64_t)pid] = i, A.span[4 * (int64_t)pid + 2] = j;
 }
 
 // pyx:586 reversed: lane 0 stored the columns end -> start; the wave swaps them into start -> end order in place
@@ -344,8 +344,8 @@ __global__ void __launch_bounds__(64) traceback_affine_kernel(const DeviceBatch 
   };
 
   constexpr bool FIT_FORM = !STRIP && !WIDE && !LEVEL;  // fit alignments: the tiled full-storage forms
-  const bool fit = FIT_FORM && A.fit;
-  const bool ovl = fit && (A.fit & FREE_A_ENDS);  // overlap alignments: A's end gaps are free as well
+  const bool fit = FIT_FORM && A.free_ends;
+  const bool ovl = fit && (A.free_ends & FREE_A_ENDS);  // overlap alignments: A's end gaps are free as well
   const bool local = FIT_FORM && A.local;  // local alignments: the same forms
   WalkPoint w{n, m, n, m, 0, 0, 0, 0, 0};
   if (!(STRIP || LEVEL) || !ts.started) {
@@ -430,8 +430,8 @@ __global__ void __launch_bounds__(64) traceback_linear_kernel(const DeviceBatch 
     return lay[pd.layer_off + Rec<S, 1, true>::dword((int64_t)sp * pd.P + pj + 2 * ilp + a, a, b)];
   };
   constexpr bool FIT_FORM = !STRIP && !WIDE && !LEVEL;  // fit alignments: the tiled full-storage forms
-  const bool fit = FIT_FORM && A.fit;
-  const bool ovl = fit && (A.fit & FREE_A_ENDS);  // overlap alignments: A's end gaps are free as well
+  const bool fit = FIT_FORM && A.free_ends;
+  const bool ovl = fit && (A.free_ends & FREE_A_ENDS);  // overlap alignments: A's end gaps are free as well
   const bool local = FIT_FORM && A.local;  // local alignments: the same forms
   WalkPoint w{n, m, n, m, 0, 0, 0, 0, 0};
   if (CONT && ts.started) {

@@ -8,23 +8,9 @@ constexpr int32_t SENT = -(1 << 30) - (1 << 29);    // "guard failed" marker
 constexpr int32_t THRESH = -(1 << 30) - (1 << 28);  // below: no valid case
 constexpr int NCOL = 65;                            // 64 lanes + 1 sentinel column
 constexpr int PROG_WORDS = 256;                     // cross-CU teams: progress words per pair = largest team
-constexpr int LDS_PROG_WORDS = 16;                  // in-workgroup teams: progress words of a workgroup, in LDS
-// The last of them (teams have at most twelve waves) holds the floor under the value at the lattice points (0, j, 0, j):
-// 0 in a fit batch (DeviceBatch::fit: a path may start there), else the sentinel, under which no value of a lattice point
-// lies.  The sweeps' prologue writes it; boundary steps read it back where row 0 is computed, so the mode costs the
-// interior loops neither a register nor an instruction.
-constexpr int FIT_FLOOR_WORD = LDS_PROG_WORDS - 1;
-// The one before it holds the same floor for the lattice points (i, 0, i, 0): 0 in an overlap batch (DeviceBatch::fit bit
-// FREE_A_ENDS), where FIT_FLOOR_WORD is 0 as well, else the sentinel.
-constexpr int COL0_FLOOR_WORD = LDS_PROG_WORDS - 2;
-// DeviceBatch::fit: whose end gaps are free in the sweeps that serve the global recurrence.  FIT sets FREE_B_ENDS, OVERLAP both.
-constexpr int32_t FREE_B_ENDS = 1, FREE_A_ENDS = 2;
-// the prologue's value of progress word t (threads 0 .. LDS_PROG_WORDS-1): the two floor words, zero for the teams' words
-__device__ __forceinline__ int32_t prog_word_init(int t, int32_t fit) {
-  if (t == FIT_FLOOR_WORD) return (fit & FREE_B_ENDS) ? 0 : SENT;
-  if (t == COL0_FLOOR_WORD) return (fit & FREE_A_ENDS) ? 0 : SENT;
-  return 0;
-}
+// in-workgroup teams: progress words of a workgroup, in LDS (teams have at most twelve waves; the last two words are the
+// free-end modes' floor words, bialign_free_ends.hpp)
+constexpr int LDS_PROG_WORDS = 16;
 constexpr int XCH_ROWS = 12;                        // affine sweeps: exchange rows per lattice point that go through LDS
 // Bytes one array of a molecule's codes takes in LDS: whole dwords, `guard` bytes around (B's codes in the sweeps: Geo<S>::PADB)
 __host__ __device__ constexpr int code_pad(int len, int guard = 0) { return (len + 2 * guard + 3) & ~3; }
@@ -84,24 +70,26 @@ struct DeviceBatch {
   // dense_tab (non-null = dense mu2); those built for a dense mu1 read the bits.  (It fills what was the struct's
   // tail padding: the kernel argument block of the existing kernels keeps its size.)
   int32_t dense_forms;
-  // Fit alignments (BIALIGN_BATCH_FIT, DESIGN.md "Fit alignments"): free end gaps in B.  Wave-uniform; the sweeps read it
-  // in their prologue (FIT_FLOOR_WORD, applied in boundary steps where is_origin is tested) and, LEAN forms, where the
-  // end cell's score is written; the generic tracebacks in their prologue and stop test.
-  // fit_span: [npairs][2] = (start_b, end_b), -1 until written.
-  // Overlap alignments (BIALIGN_BATCH_OVERLAP) set FREE_A_ENDS beside FREE_B_ENDS: the same sweeps floor
-  // the points (i, 0, i, 0) too (COL0_FLOOR_WORD), their LEAN forms fold every row's end cell on column m, and row n's best,
-  // into local_key; the generic tracebacks scan both end lines.  Spans: local_span's layout.
-  int32_t fit;
-  // Local alignments (BIALIGN_BATCH_LOCAL, DESIGN.md "Local alignments"): free ends in both molecules.  Wave-uniform; the
-  // sweeps built for it (template parameter LOCAL) do not read it, the generic tracebacks do, beside `fit`.  (It fills
-  // the padding behind `fit`.)
+  // Whose end gaps are free in the sweeps that serve the global recurrence: a mask of FREE_B_ENDS | FREE_A_ENDS
+  // (bialign_free_ends.hpp).  Fit alignments (BIALIGN_BATCH_FIT) set FREE_B_ENDS, overlap alignments
+  // (BIALIGN_BATCH_OVERLAP, section 7e) both bits; global batches set none, and neither do LOCAL batches, whose sweeps are
+  // built for the mode (see `local`).  Wave-uniform; the sweeps read it in their prologue (the floor words, applied in
+  // boundary steps where is_origin is tested) and, LEAN forms, in their end rule (lean_end_rule); the generic tracebacks
+  // in their prologue (they scan row n, in an overlap batch column m too) and stop test.
+  int32_t free_ends;
+  // Local alignments (BIALIGN_BATCH_LOCAL): free ends in both molecules.  Wave-uniform; the
+  // sweeps built for it (template parameter LOCAL) do not read it, the generic tracebacks do, beside `free_ends`.  (It
+  // fills the padding behind `free_ends`.)
   int32_t local;
-  int32_t* fit_span;
-  // local_key: [npairs] the best end of a pair as a 64-bit key (bialign_local.hpp: local_key_of), zeroed ahead of every
-  // run, raised by the sweeps' lanes with atomicMax; local_span: [npairs][4] = (start_a, end_a, start_b, end_b), -1 until
-  // written (ends: local_finish_kernel, starts: the tracebacks).
-  unsigned long long* local_key;
-  int32_t* local_span;
+  void* reserved0;  // null; it keeps the fields behind it at their offsets in the kernels' argument block
+  // [npairs] the best end of a pair as a 64-bit key (bialign_free_ends.hpp: end_key_of), zeroed ahead of every run and
+  // raised with atomicMax by the lanes of the LOCAL sweeps and of the LEAN sweeps of overlap batches; decoded behind
+  // the sweep by end_key_finish_kernel.
+  unsigned long long* end_key;
+  // The pairs' spans, -1 until written.  One layout rule: a fit batch has 2 words per pair, (start_b, end_b); overlap and
+  // local batches have 4, (start_a, end_a, start_b, end_b).  Ends: the LEAN sweeps (fit), end_key_finish_kernel, or the
+  // tracebacks' prologue; starts: the tracebacks.
+  int32_t* span;
 };
 static_assert(sizeof(DeviceBatch) == 256, "DeviceBatch grew: the kernels' argument blocks would change");
 

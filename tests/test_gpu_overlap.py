@@ -179,7 +179,7 @@ def test_full_storage_against_the_oracle(cost, s, ref):
 
 @pytest.mark.parametrize("cost,s", main_cases(), ids=lambda v: str(v))
 def test_score_only_against_the_oracle(cost, s, ref):
-    """The LEAN sweeps fold the end cells into the pair's key themselves; local_finish_kernel decodes it."""
+    """The LEAN sweeps fold the end cells into the pair's key themselves; end_key_finish_kernel decodes it."""
     for kind in ("protein", "rna"):
         todo = [c for c in case_pairs(cost, s) if c[0] == kind]
         if not todo:

@@ -5,7 +5,7 @@ and scaled twins at the edge of the int32 safety window.  There is no tolerance 
 statuses are integers compared for equality with the oracle's.
 
 The copies: free_end_scan (full-storage FIT and OVERLAP), the LEAN branches of fill_affine_kernel, fill_affine_slim_kernel
-and fill_linear_kernel, LocalBest / local_key_of / local_finish_kernel (LOCAL), and the masked argmax of fit_hits_kernel.
+and fill_linear_kernel, RowBest / end_key_of / end_key_finish_kernel (LOCAL), and the masked argmax of fit_hits_kernel.
 
 The oracle runs of every case of this module are made once, in spawn pools (``ref``), and shared: about 240 core-seconds,
 32 s of wall time in a pool of 16, most of it the three pairs of the team shape (tied_ends.BUDGET).
@@ -277,7 +277,7 @@ def test_dense_forms(mode, ref):
 @pytest.mark.parametrize("mode", te.MODES)
 def test_window_edge(mode, ref):
     """Every score times the largest k the safety window admits: the floors, LOCAL's clamp at 0 beside "-infinity" cells,
-    the biased score of local_key_of and the walks' stop rule at 2^22 .. 2^24.  One step further the batch is refused."""
+    the biased score of end_key_of and the walks' stop rule at 2^22 .. 2^24.  One step further the batch is refused."""
     from bialign_amd import _lib
     from bialign_amd.batch import make_batch
     refused = 0
