@@ -201,7 +201,8 @@ int free_hbm(const bialign_batch* b, size_t* free_b) {
 int alloc_layers(bialign_batch* b) {
   bialign_engine* eng = b->eng;
   for (int attempt = 0;; ++attempt) {
-    const size_t layer_dw = (size_t)b->max_chunk_dwords + 16;  // slack: ghost tail pieces are read 16 B wide
+    // (slack: ghost tail pieces are read 16 B wide; behind the layers the wide-band affine sweep's ring, if the plan has one)
+    const size_t layer_dw = (size_t)b->max_chunk_dwords + (size_t)b->max_chunk_ring_dwords + 16;
     DevBuf<int32_t>* slot = nullptr;  // the smallest cached buffer that is large enough
     for (DevBuf<int32_t>* c : {&eng->layer_cache, &eng->layer_cache2})
       if (c->p && c->n >= layer_dw && (!slot || c->n < slot->n)) slot = c;
@@ -220,7 +221,7 @@ int alloc_layers(bialign_batch* b) {
     (void)hipGetLastError();
     b->d_layers.p = nullptr;
     b->d_layers.n = 0;
-    const int64_t smaller = (int64_t)(b->max_chunk_dwords + b->max_chunk_tab_dwords) * 3 / 4;
+    const int64_t smaller = (int64_t)(b->max_chunk_dwords + b->max_chunk_tab_dwords + b->max_chunk_ring_dwords) * 3 / 4;
     if (attempt >= 3 || smaller < max_pair_need(*b))
       return fail(BIALIGN_E_DEVICE, "hipMalloc of %zu bytes of layer storage failed: %s", layer_dw * 4, hipGetErrorString(err));
     if (int rc = replan_smaller(*b, smaller)) return rc;

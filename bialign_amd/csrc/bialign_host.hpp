@@ -105,8 +105,6 @@ struct bialign_batch : bialign::BatchPlan {  // the plan (bialign_plan.hpp), and
   bool packed_layers = false;   // ... and so did the launch whose layers are in the buffer now
   DevBuf<uint8_t> d_seq_a, d_cls_a, d_seq_b, d_cls_b, d_trace;
   DevBuf<int32_t> d_tab;  // dense forms: all pairs' n x m tables (per pair mu2's, then mu1's; PairDesc::tab_off)
-  DevBuf<int32_t> d_wide_ring;  // wide-band affine sweep: derived values of the last levels (bialign_wide.hpp)
-  DevBuf<int64_t> d_wide_off;   // ... per pair of a launch: offset of its ring
   // FEATURE form of mu2 (bialign_batch_create_features, bialign_mu2_build.hpp): per-residue doubles in HBM, d_tab is
   // per-chunk scratch the builder kernel fills ahead of each chunk's sweep; PairDesc::tab_off is chunk-relative.
   DevBuf<double> d_feat_a, d_feat_b;   // three planes each (up, down, unp), feat_tot_a / feat_tot_b doubles per plane
@@ -193,6 +191,9 @@ struct bialign_batch : bialign::BatchPlan {  // the plan (bialign_plan.hpp), and
     v.dense_tab = (dense || dense1) ? d_tab.p : nullptr;
     v.dense_forms = (dense ? 1 : 0) | (dense1 ? 2 : 0);
     v.scratch = d_layers.p;  // a pair's scratch records follow its LEAN records in the same buffer
+    // the wide-band affine sweep's ring follows the largest chunk's layers there (BatchPlan::ring_dwords; alloc_layers)
+    v.wide_ring = ring_dwords.empty() ? nullptr : d_layers.p + max_chunk_dwords;
+    v.wide_score_only = !ring_dwords.empty() && lean ? 1 : 0;
     v.tstate = d_tstate.p;
     v.resw_k = level_trace ? wide_seg : resw_k;
     v.wide_s = S;

@@ -72,6 +72,13 @@ struct BatchPlan {
   // (no full layers); a pair's region holds checkpoints, the scratch of one segment of wide_seg levels, and the ring.
   bool level_trace = false;
   int wide_seg = 0;
+  // The wide-band affine sweep's ring of derived values outside the LEVEL forms (full storage and SCORE_ONLY;
+  // bialign_wide.hpp): WIDE_RING levels per pair, per-chunk scratch behind the chunk's layers in the same buffer.  It counts
+  // toward the budget like the tables above, not toward pair_dwords; a pair's chunk-relative offset is its
+  // PairDesc::scratch_off.  (The one-layer sweep and the LEVEL forms have no such ring: the vector stays empty.)
+  bool ring_scratch() const { return wide && affine && !level_trace; }
+  std::vector<int64_t> ring_dwords;    // per pair (plan_storage); empty: no ring term
+  int64_t max_chunk_ring_dwords = 0;   // ring dwords of the largest chunk
   int resw_k = 1;           // strips re-swept and walked per round (more when the batch has few pairs)
   // The alignment mode, one per batch (check_inputs).  Fit (BIALIGN_BATCH_FIT): free end gaps in B.  Local (BIALIGN_BATCH_LOCAL):
   // free ends in both molecules.  Overlap (BIALIGN_BATCH_OVERLAP): the global alignment whose end gaps are free in both
@@ -370,40 +377,59 @@ inline size_t lds_need_slim_codes(const SweepInfo& g, int n, int m) { return 2 *
 //   FEATURE-form batches: a pair's mu2 table (BatchPlan::tab_dwords) is per-chunk scratch in a buffer of its own
 // and counts toward the budget with the pair's layers; its tables lie end to end like the layers (PairDesc::tab_off).
 // So do a replica's permuted tables in a DENSE-form null batch.
+//   Wide-band affine batches outside the LEVEL forms: a pair's ring (BatchPlan::ring_dwords) is chunk scratch likewise, end
+// to end from 0 behind the largest chunk's layers (PairDesc::scratch_off), and counts toward the budget.
 // layer_cap / tab_cap: a re-plan within buffers the batch already holds -- neither kind may outgrow its buffer.
 inline int plan_chunks(BatchPlan& b, const std::vector<int64_t>& pair_dwords, int64_t budget_dw, int64_t layer_cap = INT64_MAX,
                        int64_t tab_cap = INT64_MAX) {
   const int npairs = b.npairs;
   const bool feat = b.tab_scratch();  // (FEATURE form, and the DENSE-form null batch: its replicas' permuted tables)
+  const bool ring = !b.ring_dwords.empty();
   auto tab_of = [&](int p) { return feat ? b.tab_dwords[p] : (int64_t)0; };
+  auto ring_of = [&](int p) { return ring ? b.ring_dwords[p] : (int64_t)0; };
   b.order.resize(npairs);
   std::iota(b.order.begin(), b.order.end(), 0);
   b.chunk_begin.assign(1, 0);
   b.max_chunk_dwords = 0;
   b.max_chunk_tab_dwords = 0;
+  b.max_chunk_ring_dwords = 0;
   int64_t total_dw = 0;
   for (int p = 0; p < npairs; ++p) {
-    if (pair_dwords[p] + tab_of(p) > budget_dw) {
+    if (pair_dwords[p] + tab_of(p) + ring_of(p) > budget_dw) {
       // who asks (a real pair, or a replica of real pair p / R), and for what beside its layers
       const char* const who = b.null_R ? ": one replica" : "";
       const char* const tabs = b.null_dense ? "permuted tables" : "mu2 table";
       const long long lay = (long long)pair_dwords[p] * 4, tab = (long long)tab_of(p) * 4, bud = (long long)budget_dw * 4;
       const int shown = b.null_R ? p / b.null_R : p;
+      if (ring) {  // (wide bands: the ring of the affine sweep, beside the tables where those are chunk scratch too)
+        const long long rng = (long long)ring_of(p) * 4;
+        return feat ? fail(BIALIGN_E_NOMEM, "pair %d%s needs %lld bytes of layers, %lld of %s and %lld of the wide-band ring, budget is %lld",
+                           shown, who, lay, tab, tabs, rng, bud)
+                    : fail(BIALIGN_E_NOMEM, "pair %d%s needs %lld bytes of layers and %lld of the wide-band ring, budget is %lld", shown, who,
+                           lay, rng, bud);
+      }
       return feat ? fail(BIALIGN_E_NOMEM, "pair %d%s needs %lld bytes of layers and %lld of %s, budget is %lld", shown, who, lay, tab, tabs, bud)
                   : fail(BIALIGN_E_NOMEM, "pair %d%s needs %lld bytes of layers, budget is %lld", shown, who, lay, bud);
     }
-    total_dw += pair_dwords[p] + tab_of(p);
+    total_dw += pair_dwords[p] + tab_of(p) + ring_of(p);
   }
   const int64_t want_chunks = (total_dw + budget_dw - 1) / budget_dw;
   const int64_t target_dw = std::min(budget_dw, (total_dw + want_chunks - 1) / want_chunks);
-  int64_t used = 0, used_tab = 0;  // layer dwords, table dwords of the chunk so far
+  int64_t used = 0, used_tab = 0, used_ring = 0;  // layer dwords, table dwords, ring dwords of the chunk so far
   for (int p = 0; p < npairs; ++p) {
-    if (used + used_tab > 0 && (used + used_tab + pair_dwords[p] + tab_of(p) > budget_dw || used + used_tab >= target_dw ||
-                                used + pair_dwords[p] > layer_cap || used_tab + tab_of(p) > tab_cap)) {
+    const int64_t all = used + used_tab + used_ring;
+    if (all > 0 && (all + pair_dwords[p] + tab_of(p) + ring_of(p) > budget_dw || all >= target_dw ||
+                    used + pair_dwords[p] > layer_cap || used_tab + tab_of(p) > tab_cap)) {
       b.chunk_begin.push_back(p);
-      used = used_tab = 0;
+      used = used_tab = used_ring = 0;
     }
-    b.pairs[p].scratch_off += used - b.pairs[p].layer_off;  // (relative to the pair's start until the first plan)
+    if (ring) {
+      b.pairs[p].scratch_off = used_ring;  // (chunk-relative in the ring area, not an offset from the pair's layers)
+      used_ring += ring_of(p);
+      b.max_chunk_ring_dwords = std::max(b.max_chunk_ring_dwords, used_ring);
+    } else {
+      b.pairs[p].scratch_off += used - b.pairs[p].layer_off;  // (relative to the pair's start until the first plan)
+    }
     b.pairs[p].layer_off = used;
     used += pair_dwords[p];
     b.max_chunk_dwords = std::max(b.max_chunk_dwords, used);
@@ -672,10 +698,12 @@ inline void decide_pack(BatchPlan& b, int64_t colmax) {
   b.pack = ok;
 }
 
-// What the largest pair needs inside the budget: its layers, and where tables are per-chunk scratch its tables
+// What the largest pair needs inside the budget: its layers, where tables are per-chunk scratch its tables, and the
+// wide-band affine sweep's ring
 inline int64_t max_pair_need(const BatchPlan& b) {
   int64_t mx = 0;
-  for (int p = 0; p < b.npairs; ++p) mx = std::max(mx, b.pair_dwords[p] + (b.tab_scratch() ? b.tab_dwords[p] : 0));
+  for (int p = 0; p < b.npairs; ++p)
+    mx = std::max(mx, b.pair_dwords[p] + (b.tab_scratch() ? b.tab_dwords[p] : 0) + (b.ring_dwords.empty() ? 0 : b.ring_dwords[p]));
   return mx;
 }
 
@@ -694,8 +722,10 @@ inline int plan_storage(BatchPlan& b, int64_t budget_dw) {
   auto max_need = [&]() { return max_pair_need(b); };
   // layer storage per pair in the batch's mode (dwords); a pair's scratch records follow its LEAN records
   auto size_pairs = [&]() {
+    b.ring_dwords.assign(b.ring_scratch() ? b.npairs : 0, 0);  // (the LEVEL forms' ring is part of the pair's region)
     for (int p = 0; p < b.npairs; ++p) {
       PairDesc& d = b.pairs[p];
+      if (b.ring_scratch()) b.ring_dwords[p] = WIDE_RING * wide_ring_level_dwords(d.n, S);
       if (b.wide && b.level_trace) {  // checkpoints, one segment's scratch, the ring (bialign_wide.hpp)
         d.scratch_off = wide_ckpt_dwords(d.n, d.m, S, b.wide_seg, b.NL);  // relative to layer_off until the chunk layout is fixed
         pair_dwords[p] = wide_level_pair_dwords(d.n, d.m, S, b.wide_seg, b.NL);
@@ -774,7 +804,10 @@ inline int plan_storage(BatchPlan& b, int64_t budget_dw) {
 
 // The allocation retry's re-plan under a smaller budget: offsets back to pair-relative, as before the first plan.
 inline int replan_smaller(BatchPlan& b, int64_t budget_dw) {
-  for (PairDesc& d : b.pairs) d.scratch_off -= d.layer_off, d.layer_off = 0;
+  for (PairDesc& d : b.pairs) {
+    if (b.ring_dwords.empty()) d.scratch_off -= d.layer_off;  // (a ring offset is not relative to the layers: plan_chunks sets it anew)
+    d.layer_off = 0;
+  }
   return plan_chunks(b, b.pair_dwords, budget_dw);
 }
 

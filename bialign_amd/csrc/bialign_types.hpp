@@ -25,7 +25,8 @@ struct PairDesc {
   int64_t trace_off;      // byte offset in the trace buffer
   int64_t tab_off;        // dense forms: start of this pair's tables in DeviceBatch::dense_tab (n x m each, mu2's first)
   int64_t scratch_off;    // lean traceback: dword offset of this pair's one-strip scratch records
-                          // (level traceback, bialign_wide.hpp: of its segment scratch; the ring follows it)
+                          // (level traceback, bialign_wide.hpp: of its segment scratch; the ring follows it.  Wide-band affine
+                          // sweep in full storage or SCORE_ONLY: of its ring in DeviceBatch::wide_ring, chunk-relative)
 };
 
 // Lean traceback: where a pair's walk stands between two strips.
@@ -61,8 +62,10 @@ struct DeviceBatch {
   int32_t wide_s;       // wide-band path (max_shift beyond the tiled kernels): the band half-width
   int32_t prio_mode;    // 1 = rotate wave priorities by workgroup age (fill_affine_kernel); BIALIGN_PRIO=0 switches it off
   int32_t spin_limit;   // team hand-off: polls of the partner's progress word before a wave gives up (error flag)
-  int32_t* wide_ring;            // wide-band affine sweep: derived values of the last WIDE_RING levels, all pairs of the launch
-  const int64_t* wide_ring_off;  // ... [pairs in launch]: dword offset of a pair's ring
+  // wide-band affine sweep: derived values of the last WIDE_RING levels, the chunk's pairs end to end (a pair's at its
+  // PairDesc::scratch_off) -- the part of the chunk buffer behind the layers (BatchPlan::ring_dwords)
+  int32_t* wide_ring;
+  const void* reserved1;         // null; it keeps the fields behind it at their offsets in the kernels' argument block
   int32_t wide_score_only;       // ... 1: no layers are stored, the last level's point writes the score
   int32_t launch_pairs;     // fill_affine_slim_kernel: pairs of this launch (a workgroup holds several)
   int32_t slim_code_bytes;  // fill_affine_slim_kernel: LDS bytes of one pair's sequence and class codes

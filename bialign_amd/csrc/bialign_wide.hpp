@@ -295,7 +295,7 @@ __global__ void __launch_bounds__(WIDE_THREADS) fill_wide_affine_kernel(const De
     seg = wide_segment_of(ts, c.n, c.m, C);
   }
   int32_t* const scratch = MODE == WIDE_FULL ? nullptr : A.scratch + pd.scratch_off;
-  int32_t* const ring = MODE == WIDE_FULL ? A.wide_ring + A.wide_ring_off[slot] : scratch + wide_scratch_dwords(c.n, c.m, S, C, 9);
+  int32_t* const ring = MODE == WIDE_FULL ? A.wide_ring + pd.scratch_off : scratch + wide_scratch_dwords(c.n, c.m, S, C, 9);
   __shared__ WideStage stage;
   wide_stage(c, stage);
   const int64_t LV = (int64_t)(n + 1) * W * HW, lvl = wide_ring_level_dwords(n, S);  // points per level, dwords per level (27 LV)

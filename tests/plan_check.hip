@@ -14,7 +14,8 @@
 //          constant of the dense tables), fa=up,down,unp fb=up,down,unp (one feature value per plane and side), sw,
 //          replicas seed (null batch)
 // Answer of a batch: `rc=<code> msg=<message>`, `mode=<0 global|1 fit|2 local> flags=<the flags the planner saw>`, and on
-// success the plan as print_plan() writes it.
+// success the plan as print_plan() writes it, a `size` line per pair, and for plans with a ring term (the wide-band affine
+// sweep outside the LEVEL forms) a `ring` line per pair and `max_chunk_ring_dwords`.
 #include "bialign_plan.hpp"
 
 #include <cstdarg>
@@ -112,6 +113,8 @@ static void print_plan(const BatchPlan& b, const Request& r) {
     }
   }
   std::printf("max_chunk_dwords=%lld max_chunk_tab_dwords=%lld\n", (long long)b.max_chunk_dwords, (long long)b.max_chunk_tab_dwords);
+  // (plans with a ring term only -- the wide-band affine sweep outside the LEVEL forms: the ring area of the largest chunk)
+  if (!b.ring_dwords.empty()) std::printf("max_chunk_ring_dwords=%lld\n", (long long)b.max_chunk_ring_dwords);
   for (size_t c = 0; !b.wide && c + 1 < b.chunk_begin.size(); ++c) {
     const int first = b.chunk_begin[c], count = b.chunk_begin[c + 1] - first;
     const TeamShape ts = team_shape(b, first, count, (int)r.num("num_cu", 256), (int)r.num("resid"), (int)r.num("resid8"));
@@ -227,6 +230,8 @@ static void run_batch(const Request& r) {
   for (int p = 0; p < b.npairs && !r.num("quiet"); ++p)  // what a pair takes inside the budget, and in its full-record form
     std::printf("size %d dwords=%lld tab_dwords=%lld full_dwords=%lld\n", p, (long long)b.pair_dwords[p],
                 (long long)(b.tab_scratch() ? b.tab_dwords[p] : 0), (long long)b.full_dwords[p]);
+  for (int p = 0; p < b.npairs && !b.ring_dwords.empty() && !r.num("quiet"); ++p)  // ... and its ring, where the plan has that term
+    std::printf("ring %d ring_dwords=%lld ring_off=%lld\n", p, (long long)b.ring_dwords[p], (long long)b.pairs[p].scratch_off);
   if (r.num("replan") && b.packed_sizing) {  // as replan_full() does: within the buffers the first plan sized
     const int64_t layer_cap = std::max(b.max_chunk_dwords, *std::max_element(b.full_dwords.begin(), b.full_dwords.end()));
     const int64_t tab_cap = b.max_chunk_tab_dwords;

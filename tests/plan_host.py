@@ -49,6 +49,13 @@ def scoring_words(params, pairs):
                 beta=params["gap_opening_cost"], gamma=params["gap_cost"], delta=params["shift_cost"])
 
 
+def ring_dwords(n, s):
+    """The ring of the wide-band affine sweep outside the LEVEL forms, per pair: 5 levels x 27 derived values x
+    (n + 1) W ceil(W / 2) points, W = 2 s + 1 (bialign_wide.hpp: WIDE_RING, WIDE_SLOT, wide_ring_level_dwords)."""
+    w = 2 * s + 1
+    return 5 * 27 * (n + 1) * w * ((w + 1) // 2)
+
+
 class Plan:
     """One answer: rc, msg, and on success the fields of the plan (after a re-plan: ``replanned`` is the second Plan)."""
 
@@ -56,6 +63,7 @@ class Plan:
         first = re.match(r"rc=(-?\d+) msg=(.*)", lines[0])
         self.rc, self.msg = int(first.group(1)), first.group(2)
         self.fields, self.pairs, self.sizes, self.teams, self.chunks, self.order, self.replanned = {}, [], [], [], [], [], None
+        self.rings = []   # per pair, plans with a ring term only: ring_dwords, ring_off
         for at, ln in enumerate(lines[1:], 1):
             head, _, rest = ln.partition(" ")
             if head == "replan":
@@ -68,6 +76,8 @@ class Plan:
                 self.order = [int(x) for x in rest.split()]
             elif head == "size":
                 self.sizes.append({k: int(v) for k, v in (w.split("=") for w in rest.split()[1:])})
+            elif head == "ring":
+                self.rings.append({k: int(v) for k, v in (w.split("=") for w in rest.split()[1:])})
             elif head == "pair":
                 self.pairs.append({k: int(v) for k, v in (w.split("=") for w in rest.split()[1:])})
             elif head == "team":

@@ -152,3 +152,27 @@ def test_smaller_chunks_when_the_layer_buffer_cannot_be_allocated(monkeypatch):
     assert (b.scores().tolist(), [t.tolist() for t in b.traces()[0]]) == want
     b.close()
     eng.close()
+
+
+def test_smaller_chunks_keep_the_wide_band_ring(monkeypatch):
+    """A wide-band SCORE_ONLY batch is all ring (64 bytes of layers a pair, megabytes of ring behind them in the same
+    buffer): the re-plan after a refused allocation cuts by the rings, and the scores are those of the undisturbed run."""
+    from oracle import oracle
+    from bialign_amd.batch import make_batch
+    from bialign_amd.engine import Engine
+    pairs = [synth.protein_pair(2700 + t, 24 + 3 * t, 33) for t in range(8)]
+    params = dict(synth.PROTEIN_PARAMS, max_shift=6)
+    eng = Engine(0)
+    ref = make_batch(pairs, params, engine=eng, score_only=True)
+    ref.run()
+    want = ref.scores().tolist()
+    assert ref.info["nchunks"] == 1
+    ref.close()
+    eng.trim()
+    monkeypatch.setenv("BIALIGN_TEST_FAIL_ALLOC", "1")
+    b = make_batch(pairs, params, engine=eng, score_only=True)
+    assert b.info["nchunks"] >= 2
+    b.run()
+    assert b.scores().tolist() == want == [oracle.solve(*p, params, want_trace=False)["score"] for p in pairs]
+    b.close()
+    eng.close()

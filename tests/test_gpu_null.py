@@ -98,6 +98,21 @@ def test_scores_equal_oracle_wide_band():
     check_scores_vs_oracle(pairs, dict(synth.PROTEIN_PARAMS, max_shift=7), 4, 9)
 
 
+def test_wide_band_rings_are_cut_into_chunks():
+    """The batch of test_scores_equal_oracle_wide_band (20 virtual pairs, rings up to 3.6 MB) under a budget of two rings:
+    several chunks, the same null scores, reductions and z-scores."""
+    from oracle import oracle
+    from wide_ring import check_chunked_null
+    pairs = [synth.protein_pair(4400 + t, n, m) for t, (n, m) in enumerate(SHAPES)]
+    params, R, seed = dict(synth.PROTEIN_PARAMS, max_shift=7), 4, 9
+    want = [[oracle.solve(*sg.shuffle_b(pair, seed, p, r), params, want_trace=False)["score"] for r in range(R)]
+            for p, pair in enumerate(pairs)]
+    observed = np.array([sorted(row)[R // 2] for row in want], dtype=np.int32)
+    check_chunked_null(lambda bud: sg.null_batch(pairs, params, R, seed=seed, hbm_budget_bytes=bud),
+                       lambda bud: sg.zscores(pairs, params, replicas=R, seed=seed, hbm_budget_bytes=bud),
+                       [n for n, _ in SHAPES], 7, want, observed)
+
+
 def test_scores_equal_oracle_rna():
     """RNA: what moves with a residue is its structure class.  A shuffled class string is no dot-bracket structure the
     oracle could parse, so the oracle's own mu1 / mu2 tables of the real pair get their B columns permuted."""

@@ -190,6 +190,27 @@ def test_scores_equal_oracle_wide_band():
     check_scores_vs_oracle(dict(synth.PROTEIN_PARAMS, max_shift=7), "both", 3, 9)
 
 
+def test_wide_band_rings_are_cut_into_chunks():
+    """The batch of test_scores_equal_oracle_wide_band (both tables dense) under a budget of two rings (and 1 MiB: a replica's
+    permuted tables are a few KB): several chunks; the same null scores, reductions and z-scores."""
+    from oracle import oracle
+    from wide_ring import check_chunked_null
+    pairs, mu1, mu2 = scored_pairs()
+    pairs = list(pairs)
+    params, R, seed = dict(synth.PROTEIN_PARAMS, max_shift=7), 3, 9
+    want = []
+    for p, (n, m) in enumerate(SHAPES):
+        o1, o2 = (np.array(t) for t in oracle.mu_tables(*pairs[p], params))
+        o1[1:, 1:], o2[1:, 1:] = mu1[p], mu2[p]
+        cols = [np.concatenate([[0], 1 + sg.permutation(seed, p, r, m)]) for r in range(R)]
+        want.append([oracle.solve_tables(n, m, params, o1[:, c], o2[:, c], want_trace=False)["score"] for c in cols])
+    observed = np.array([sorted(row)[R // 2] for row in want], dtype=np.int32)
+    kw = form_kw("both", mu1, mu2)
+    check_chunked_null(lambda bud: sg.null_dense_batch(pairs, params, R, seed=seed, hbm_budget_bytes=bud, **kw),
+                       lambda bud: sg.zscores_dense(pairs, params, replicas=R, seed=seed, hbm_budget_bytes=bud, **kw),
+                       [n for n, _ in SHAPES], 7, want, observed)
+
+
 def test_scores_equal_oracle_general_beta():
     check_scores_vs_oracle(dict(synth.PROTEIN_PARAMS, gap_opening_cost=100), "mu1", 3, 3)
 

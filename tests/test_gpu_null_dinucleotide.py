@@ -183,6 +183,23 @@ def test_scores_equal_oracle(s, ov):
             assert int(scores[p, r]) == want, (p, r)
 
 
+def test_wide_band_rings_are_cut_into_chunks():
+    """The pairs of test_gpu_null.test_scores_equal_oracle_wide_band (max_shift 7) under the dinucleotide model and a budget
+    of two rings: several chunks, the same null scores as unbudgeted and as the oracle on the mirror's shuffles, the same
+    reductions and z-scores."""
+    from oracle import oracle
+    from wide_ring import check_chunked_null
+    shapes = [(3, 55), (55, 3), (17, 31), (40, 22), (28, 28)]
+    pairs = [synth.protein_pair(4400 + t, n, m) for t, (n, m) in enumerate(shapes)]
+    params, R, seed = dict(synth.PROTEIN_PARAMS, max_shift=7), 4, 9
+    want = [[oracle.solve(*sg.shuffle_b(pair, seed, p, r, shuffle=DI), params, want_trace=False)["score"] for r in range(R)]
+            for p, pair in enumerate(pairs)]
+    observed = np.array([sorted(row)[R // 2] for row in want], dtype=np.int32)
+    check_chunked_null(lambda bud: sg.null_batch(pairs, params, R, seed=seed, shuffle=DI, hbm_budget_bytes=bud),
+                       lambda bud: sg.zscores(pairs, params, replicas=R, seed=seed, shuffle=DI, hbm_budget_bytes=bud),
+                       [n for n, _ in shapes], 7, want, observed)
+
+
 @pytest.mark.parametrize("mode", ["fit", "local"])
 def test_free_end_modes_equal_host_expanded_batch(mode):
     from bialign_amd.batch import make_batch

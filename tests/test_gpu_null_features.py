@@ -171,6 +171,24 @@ def test_scores_equal_oracle_wide_band():
     check_scores_vs_oracle(8200, dict(synth.RNA_PARAMS, max_shift=7), 4, 9)
 
 
+def test_wide_band_rings_are_cut_into_chunks():
+    """The batch of test_scores_equal_oracle_wide_band under a budget of two rings (and 1 MiB: the per-chunk mu2 tables are a
+    few KB): several chunks, each with a builder launch of its own; the same null scores, reductions and z-scores."""
+    from oracle import oracle
+    from wide_ring import check_chunked_null
+    mols, index = shape_molecules(8200)
+    params, R, seed = dict(synth.RNA_PARAMS, max_shift=7), 4, 9
+    want = []
+    for p, ((ia, ib), (n, m, mu2)) in enumerate(zip(index, oracle_tables(8200, params["structure_weight"]))):
+        mu1, _ = oracle.mu_tables(mols[ia][0], mols[ib][0], "." * n, "." * m, params)
+        cols = [np.concatenate([[0], 1 + sg.permutation(seed, p, r, m)]) for r in range(R)]
+        want.append([oracle.solve_tables(n, m, params, mu1[:, c], mu2[:, c], want_trace=False)["score"] for c in cols])
+    observed = np.array([sorted(row)[R // 2] for row in want], dtype=np.int32)
+    check_chunked_null(lambda bud: sg.null_feature_batch(list(mols), list(index), params, R, seed=seed, hbm_budget_bytes=bud),
+                       lambda bud: sg.zscores_features(list(mols), list(index), params, replicas=R, seed=seed, hbm_budget_bytes=bud),
+                       [n for n, _ in SHAPES], 7, want, observed)
+
+
 def test_scores_equal_oracle_general_beta():
     check_scores_vs_oracle(8200, dict(synth.RNA_PARAMS, gap_opening_cost=100), 4, 3)
 

@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 SIX = [(41, 46), (64, 300), (40, 47), (66, 298), (43, 45), (62, 301)]     # P = 64 (no team fits) and P ~ 300 (teams of 2)
 FEATURE_SHAPES = [(50, 61), (44, 58), (61, 50), (47, 66)]
-LEAN_TRACE, LEVEL_TRACE = 2, 4
+SCORE_ONLY, LEAN_TRACE, LEVEL_TRACE = 1, 2, 4
 #: name -> (budget in bytes, expected chunks, expected storage mode)
 TILED = {"one-chunk": (64 << 20, 1, 0), "three-chunks": (12 << 20, 3, 0), "lean": (3 << 20, 6, LEAN_TRACE)}
 
@@ -109,3 +109,57 @@ def test_feature_batch_with_table_scratch_in_two_chunks(exe):
         mu2 = np.zeros((n + 1, m + 1), dtype=np.int32)
         mu2[1:, 1:] = we.host_table(mols[a][1], mols[c][1], params["structure_weight"])
         assert got["scores"][p] == oracle.solve_tables(n, m, params, mu1, mu2, want_trace=False)["score"]
+
+
+def test_wide_score_only_rings_in_chunks(exe):
+    """A wide-band SCORE_ONLY batch under a budget of its largest ring and 1 MiB: the library cuts it where the planner
+    does, by the rings, and still reports layers only."""
+    from oracle import oracle
+    from bialign_amd.batch import make_batch
+    shapes = [(30, 55), (41, 46), (52, 37), (63, 28), (3, 40)]
+    pairs = [synth.protein_pair(7400 + t, n, m) for t, (n, m) in enumerate(shapes)]
+    params = dict(synth.PROTEIN_PARAMS, max_shift=8)
+    budget = 4 * ph.ring_dwords(63, 8) + (1 << 20)
+    plan, = ph.plans(exe, [ph.request(pairs=shapes, budget=budget, flags=SCORE_ONLY, **ph.scoring_words(params, pairs))])
+    assert plan.rc == 0 and plan.storage == SCORE_ONLY and plan.nchunks > 1 and plan.max_chunk_dwords <= 16 * len(shapes)
+    assert plan.max_chunk_ring_dwords >= ph.ring_dwords(63, 8) and 4 * (plan.max_chunk_dwords + plan.max_chunk_ring_dwords) <= budget
+    got = reported(make_batch(pairs, params, score_only=True, hbm_budget_bytes=budget))
+    agree(got, plan, waves=False)        # (the wide path's parts are not team_shape's)
+    assert got["scores"] == [oracle.solve(*p, dict(params), want_trace=False)["score"] for p in pairs]
+
+
+def test_wide_full_storage_in_chunks_and_a_one_pair_launch(exe):
+    """Full storage at max_shift 7, cut into chunks by layers and rings together.  dump_layers re-fills one pair in a launch
+    of its own: a pair that is neither the first of its chunk nor in the first chunk finds its ring at its own offset of
+    the ring area.  A second run reuses the buffer, rings included."""
+    from oracle import oracle
+    from bialign_amd.batch import make_batch
+    from bialign_amd.engine import trace_codes_to_columns
+    shapes = [(30, 28), (5, 41), (41, 5), (1, 1), (17, 18), (36, 36), (2, 30), (24, 9)]
+    pairs = [synth.protein_pair(7500 + t, n, m) for t, (n, m) in enumerate(shapes)]
+    params = dict(synth.PROTEIN_PARAMS, max_shift=7)
+    budget = 18 << 20   # (the largest pair: 14.8 MB of layers and 2.4 MB of ring)
+    plan, = ph.plans(exe, [ph.request(pairs=shapes, budget=budget, **ph.scoring_words(params, pairs))])
+    assert plan.rc == 0 and plan.storage == 0 and plan.nchunks >= 3
+    # the last pair (by offset) of a chunk behind the first that holds several pairs
+    inner = [b - 1 for a, b in zip(plan.chunks[1:], plan.chunks[2:]) if b - a >= 2]
+    assert inner and all(plan.rings[p]["ring_off"] > 0 and plan.pairs[p]["layer_off"] > 0 for p in inner)
+    pick = inner[0]
+    b = make_batch(pairs, params, hbm_budget_bytes=budget)
+    b.run()
+    info = b.current_info()
+    assert (info["nchunks"], info["storage"], info["hbm_layer_bytes"]) == (plan.nchunks, 0, 4 * plan.max_chunk_dwords)
+    scores, (traces, ok) = b.scores().copy(), b.traces()
+    traces = [t.copy() for t in traces]
+    refs = [oracle.solve(*p, params) for p in pairs]
+    assert [int(v) for v in scores] == [r["score"] for r in refs]
+    n, m = shapes[pick]
+    assert trace_codes_to_columns(traces[pick]) == oracle.trace_to_lists(refs[pick]["trace"])
+    layers = b.dump_layers(pick)
+    for g, e in zip(oracle.band_values(layers, n, m, 7), oracle.band_values(refs[pick]["layers"], n, m, 7)):
+        np.testing.assert_array_equal(g, e)
+    b.run()
+    np.testing.assert_array_equal(b.scores(), scores)
+    again, ok2 = b.traces()
+    assert all(np.array_equal(x, y) for x, y in zip(again, traces)) and np.array_equal(ok, ok2)
+    b.close()

@@ -140,6 +140,40 @@ def test_score_only_wide_band_vs_oracle(s, parts, monkeypatch):
         full.close()
 
 
+@pytest.mark.parametrize("s,parts", [(6, None), (8, "3")])
+def test_score_only_rings_are_cut_into_chunks(s, parts, monkeypatch):
+    """The ring of derived values is part of the chunk plan: under a budget of the largest pair's ring and 1 MiB the five
+    pairs of test_score_only_wide_band_vs_oracle (64 bytes of layers each, rings of 0.3 .. 5.3 MB) run in several chunks
+    and score what the unbudgeted batch, the full-storage batch and the oracle score."""
+    from oracle import oracle
+    from bialign_amd import _lib
+    from bialign_amd.batch import make_batch
+    from wide_ring import ring_bytes
+    if parts:
+        monkeypatch.setenv("BIALIGN_WIDE_PARTS", parts)
+    pairs = [synth.protein_pair(3300 + t, 30 + 11 * t, 55 - 9 * t) for t in range(4)] + [synth.protein_pair(3310, 3, 40)]
+    budget = max(ring_bytes(len(p[0]), s) for p in pairs) + (1 << 20)
+    for params in (dict(synth.PROTEIN_PARAMS, max_shift=s), dict(synth.PROTEIN_PARAMS, max_shift=s, gap_opening_cost=70)):
+        b = make_batch(pairs, params, score_only=True, hbm_budget_bytes=budget)
+        whole = make_batch(pairs, params, score_only=True)
+        full = make_batch(pairs, params)
+        print("s", s, "budget", budget, "->", b.info["nchunks"], "chunks")
+        assert b.info["nchunks"] > 1 and whole.info["nchunks"] == 1 == full.info["nchunks"]
+        assert b.info["hbm_layer_bytes"] <= whole.info["hbm_layer_bytes"] == 64 * len(pairs)   # layers: what the figure means
+        for x in (b, whole, full):
+            x.run()
+        np.testing.assert_array_equal(b.scores(), whole.scores())
+        np.testing.assert_array_equal(b.scores(), full.scores())
+        assert [int(x) for x in b.scores()] == [oracle.solve(*p, params, want_trace=False)["score"] for p in pairs]
+        with pytest.raises(_lib.BialignError):
+            b.traces()
+        for x in (b, whole, full):
+            x.close()
+    with pytest.raises(_lib.BialignError) as e:   # below one pair's ring: refused at creation, the ring's bytes named
+        make_batch(pairs, params, score_only=True, hbm_budget_bytes=budget - (1 << 20) - 4)
+    assert e.value.code == _lib.E_NOMEM and f"{budget - (1 << 20)} of the wide-band ring" in str(e.value)
+
+
 def test_cli_takes_max_shift_8():
     """The drop-in CLI with --max_shift 8 (the reference's option has no upper bound, bialign.py:83)."""
     import contextlib, io

@@ -2,12 +2,14 @@
 uploads; tests/plan_check.hip is a stand-alone host program around the same functions.  Here, without a GPU:
 
   * the window mirror of window_edge.py is the code: every case is admitted at its scale and refused one above;
-  * chunk plans are sound (partition, contiguous offsets, budget, maxima, launch order, the full-record re-plan);
+  * chunk plans are sound (partition, contiguous offsets, budget, maxima, launch order, the full-record re-plan), the
+    wide-band affine sweep's ring included: a term of its own beside layers and tables, inside the budget;
   * the storage ladder takes the steps the GPU fallback tests expect, from their inputs;
   * nothing moved: team_shape, plan_chunks, sweep_geometry, lds_need* and cells_of answer tests/plan_expected.txt, the
     table the code gave before it moved into the header;
   * one mode, the rules as before: every combination of FIT / LOCAL with the storage flags, bands, gap opening costs and
-    budgets answers tests/mode_expected.txt, the table the planner gave while it kept the two flags as two booleans;
+    budgets answers tests/mode_expected.txt, the table the planner gave while it kept the two flags as two booleans
+    (its max_shift 6 affine plans: since the ring is planned);
   * the same program under AddressSanitizer and UBSan prints the same; the header calls nothing of HIP."""
 import os
 import re
@@ -101,27 +103,35 @@ CHUNKED = {
     "dense-null-s1": dict(pairs=ragged(14, 5, (30, 80), (30, 80)), s=1, form="mu12", mu1=-11, mu2=700, replicas=4, seed=9),
     "wide-s6": dict(pairs=ragged(15, 12, (10, 40), (10, 40)), s=6, **LOOKUP),
     "wide-s7-level": dict(pairs=ragged(16, 12, (10, 40), (10, 40)), s=7, flags=LEVEL_TRACE, **LOOKUP),
+    "wide-s8-score-only": dict(pairs=ragged(17, 12, (10, 40), (10, 40)), s=8, flags=SCORE_ONLY, **LOOKUP),
+    "wide-s7-null": dict(pairs=ragged(18, 5, (10, 40), (10, 40)), s=7, replicas=4, seed=9, **LOOKUP),
 }
+RINGED = ("wide-s6", "wide-s8-score-only", "wide-s7-null")   # the affine wide-band sweep outside the LEVEL forms: a ring term
+
 
 
 def check_layout(plan, budget_dw, wide, sizes=None, layer_cap=None, tab_cap=None):
     sizes = sizes or [(z["dwords"], z["tab_dwords"]) for z in plan.sizes]
     n = len(plan.pairs)
+    assert len(plan.rings) in (0, n) and (len(plan.rings) == n) == ("max_chunk_ring_dwords" in plan.fields)
+    rings = [z["ring_dwords"] for z in plan.rings] or [0] * n
     cb = plan.chunks
     assert cb[0] == 0 and cb[-1] == n and all(a < b for a, b in zip(cb, cb[1:]))          # a partition, in order
     tabs = any(t for _, t in sizes)
-    max_lay = max_tab = 0
+    max_lay = max_tab = max_ring = 0
     for a, b in zip(cb, cb[1:]):
-        lay = tab = 0
+        lay = tab = ring = 0
         for p in range(a, b):                                                              # contiguous from 0
             assert plan.pairs[p]["layer_off"] == lay and (not tabs or plan.pairs[p]["tab_off"] == tab), (p, plan.pairs[p])
-            lay, tab = lay + sizes[p][0], tab + sizes[p][1]
-        assert lay + tab <= budget_dw
+            assert not plan.rings or plan.rings[p]["ring_off"] == ring == plan.pairs[p]["scratch_off"], (p, plan.rings[p])
+            lay, tab, ring = lay + sizes[p][0], tab + sizes[p][1], ring + rings[p]
+        assert lay + tab + ring <= budget_dw
         assert layer_cap is None or (lay <= layer_cap and tab <= tab_cap)
-        max_lay, max_tab = max(max_lay, lay), max(max_tab, tab)
+        max_lay, max_tab, max_ring = max(max_lay, lay), max(max_tab, tab), max(max_ring, ring)
         key = (lambda p: plan.shape[p][0] + plan.shape[p][1]) if wide else (lambda p: plan.pairs[p]["G"])
         assert plan.order[a:b] == sorted(range(a, b), key=key, reverse=True)              # (sorted() is stable; so is reverse=)
     assert plan.max_chunk_dwords == max_lay and plan.max_chunk_tab_dwords == max_tab
+    assert plan.fields.get("max_chunk_ring_dwords", 0) == max_ring
 
 
 @pytest.mark.parametrize("name", list(CHUNKED))
@@ -133,9 +143,13 @@ def test_chunk_plans_are_sound(exe, name):
     one, = ph.plans(exe, [ph.request(pairs=shapes, replan=1, **case)])
     assert one.rc == 0 and one.nchunks == 1 and one.npairs == len(shapes) * R
     assert one.pack == (name in ("lookup-s1-packed", "feature-s2"))                      # (so the re-plan below is exercised)
-    total = 4 * sum(z["dwords"] + z["tab_dwords"] for z in one.sizes)
+    # the ring term is the formula's, for every pair of a plan that has one -- and only such plans print it
+    vshapes = [s for s in shapes for _ in range(R)]
+    assert [z["ring_dwords"] for z in one.rings] == ([ph.ring_dwords(n, case["s"]) for n, _ in vshapes] if name in RINGED else [])
+    rings = [z["ring_dwords"] for z in one.rings] or [0] * len(vshapes)
+    total = 4 * sum(z["dwords"] + z["tab_dwords"] + r for z, r in zip(one.sizes, rings))
     # the largest pair must still fit, with full records where packed ones have to be able to fall back to them
-    largest = 4 * max((z["full_dwords"] if one.pack else z["dwords"]) + z["tab_dwords"] for z in one.sizes)
+    largest = 4 * max((z["full_dwords"] if one.pack else z["dwords"]) + z["tab_dwords"] + r for z, r in zip(one.sizes, rings))
     # 3/4 of the total: two chunks wanted, the first closes once it holds half; a sixth: six wanted, no fewer than five
     budgets = {1: total, 2: total * 3 // 4, 5: max(total // 6, largest)}
     got = ph.plans(exe, [ph.request(pairs=shapes, replan=1, budget=b, **case) for b in budgets.values()])
@@ -144,8 +158,10 @@ def test_chunk_plans_are_sound(exe, name):
         print(name, "budget", budget, "->", plan.nchunks, "chunks")
         assert (plan.pack, plan.storage) == (one.pack, one.storage)                         # the budget cut chunks, nothing else
         assert plan.nchunks == want if want < 5 else plan.nchunks >= 5
-        plan.shape = [s for s in shapes for _ in range(R)]
+        plan.shape = vshapes
         check_layout(plan, budget // 4, wide)
+        assert (plan.fields.get("max_chunk_ring_dwords", 0) > 0) == (name in RINGED) and plan.rings == [
+            dict(z, ring_off=w["ring_off"]) for z, w in zip(one.rings, plan.rings)]      # (the term itself does not move)
         if name == "dense-null-s1" or name == "feature-s2":
             assert plan.max_chunk_tab_dwords > 0
         if one.pack:   # the re-plan at full-record sizes, inside the buffers of the first plan
@@ -189,6 +205,43 @@ def test_fallback_to_level_trace_for_wide_bands(exe):
     w8 = ph.scoring_words(dict(synth.PROTEIN_PARAMS, max_shift=8), [synth.protein_pair(5601, 60, 60)])
     refused, = ph.plans(exe, [ph.request(pairs=[(60, 60)], budget=1 << 20, **w8)])
     assert refused.rc == ph.E_NOMEM and "budget is 1048576" in refused.msg
+
+
+def test_wide_ring_is_cut_into_chunks_inside_the_budget(exe):
+    """64 score-only pairs of 60 x 60 at max_shift 8 under 16 MiB: 16 dwords of layers each, and a ring of 5 levels =
+    1 259 955 dwords = 5.04 MB each, 322.5 MB in all -- planned as one launch of 4 KiB while the ring was outside the plan.
+    No chunk may hold more than the budget, so there are at least ceil(64 * 4 * (ring + 16) / 16 MiB) = 20 of them (three
+    pairs fit a chunk: 22); a budget below one pair's ring is refused at creation, the ring's bytes in the message."""
+    budget, shapes = 16 << 20, [(60, 60)] * 64
+    ring = ph.ring_dwords(60, 8)
+    assert ring == 1259955
+    plan, = ph.plans(exe, [ph.request(pairs=shapes, s=8, flags=SCORE_ONLY, budget=budget, **LOOKUP)])
+    assert plan.rc == 0 and plan.storage == SCORE_ONLY, plan.msg
+    assert [z["ring_dwords"] for z in plan.rings] == [ring] * 64 and [z["dwords"] for z in plan.sizes] == [16] * 64
+    plan.shape = shapes
+    check_layout(plan, budget // 4, True)
+    for a, b in zip(plan.chunks, plan.chunks[1:]):
+        assert 4 * (b - a) * (ring + 16) <= budget
+    print("64 x (60, 60), s=8, SCORE_ONLY, 16 MiB ->", plan.nchunks, "chunks")
+    assert plan.nchunks >= -(-64 * 4 * (ring + 16) // budget) == 20
+    refused, = ph.plans(exe, [ph.request(pairs=shapes, s=8, flags=SCORE_ONLY, budget=4 * ring, **LOOKUP)])
+    assert refused.rc == ph.E_NOMEM, refused.msg
+    assert refused.msg == f"pair 0 needs 64 bytes of layers and {4 * ring} of the wide-band ring, budget is {4 * ring}"
+
+
+def test_wide_ring_counts_in_the_fallback_to_level_trace(exe):
+    """A full-storage wide pair whose layers fit the budget and whose layers + ring do not is served from checkpointed
+    levels; four bytes more and it keeps its full layers."""
+    shapes = [(40, 44)]
+    roomy, = ph.plans(exe, [ph.request(pairs=shapes, s=6, **LOOKUP)])
+    assert roomy.rc == 0 and roomy.storage == 0
+    layers, ring = 4 * roomy.sizes[0]["dwords"], 4 * roomy.rings[0]["ring_dwords"]
+    assert ring == 4 * ph.ring_dwords(40, 6) and 0 < ring < layers
+    fits, short, bare = ph.plans(exe, [ph.request(pairs=shapes, s=6, budget=b, **LOOKUP) for b in (layers + ring, layers + ring - 4, layers)])
+    assert (fits.storage, fits.nchunks, fits.max_chunk_ring_dwords) == (0, 1, ring // 4)
+    for plan in (short, bare):   # (the layers alone would have fitted)
+        assert plan.rc == 0 and plan.storage == LEVEL_TRACE and not plan.rings and "max_chunk_ring_dwords" not in plan.fields
+        assert 4 * plan.max_chunk_dwords <= layers
 
 
 def test_packed_records_are_dropped_when_the_full_fallback_would_not_fit(exe):
