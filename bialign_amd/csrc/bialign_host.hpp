@@ -531,8 +531,26 @@ bool trace_fast_admits(const PairDesc& d) {
 // of the launch if the workgroup can spare it (BIALIGN_TRACE_LDS: tests, a smaller buffer), else flushed in pieces.
 // 0: the generic kernel serves (BIALIGN_TRACE_FAST=0: tests / A-B; dense mu2; a FIT or LOCAL batch; a pair not admitted).
 constexpr int TRACE_FAST_TBUF_MAX = 16 * 1024;
+// Ring records of the walk's LDS window (TraceWindow<S>), 0: the kernel without the window (BIALIGN_TRACE_WINDOW=0: tests /
+// A-B; the window would not fit).  It is taken where the ring ends within the 64 KB an LDS-DMA's m0 addresses, and where it
+// costs no workgroup that the launch needs resident: as many per CU as without it, or all of the launch at once.
+// BIALIGN_TRACE_WINDOW_K (tests): a shorter ring, down to the one without lead.
 template <int S>
-size_t trace_fast_lds(const bialign_batch* b, int first, int count, int* tbuf) {
+int trace_window_records(const bialign_batch* b, int count, size_t fixed, int tbuf) {
+  using TW = TraceWindow<S>;
+  const char* sw = getenv("BIALIGN_TRACE_WINDOW");
+  if (sw && atoi(sw) == 0) return 0;
+  int k = TW::K;
+  if (const char* e = getenv("BIALIGN_TRACE_WINDOW_K"))
+    while (k > TW::KMIN && k > atoi(e)) k /= 2;
+  const size_t lds = 160 * 1024, with = fixed + TW::lds_bytes(k);
+  if (with > 64 * 1024 || with + 64 > lds) return 0;
+  const size_t res_with = lds / (with + tbuf), res_without = lds / (fixed + tbuf);
+  const size_t needed = ((size_t)count + b->eng->num_cu - 1) / std::max(b->eng->num_cu, 1);
+  return res_with >= std::min(res_without, needed) ? k : 0;
+}
+template <int S>
+size_t trace_fast_lds(const bialign_batch* b, int first, int count, int* tbuf, int* wk) {
   const char* sw = getenv("BIALIGN_TRACE_FAST");  // "0": tests / A-B, the generic kernel only
   if ((sw && atoi(sw) == 0) || b->dense || b->dense1 || b->wide || b->lean) return 0;
   if (b->free_ends()) return 0;  // fit, local and overlap alignments take the generic walk: the short-chain kernel has neither the end rules nor the stop rules
@@ -544,8 +562,11 @@ size_t trace_fast_lds(const bialign_batch* b, int first, int count, int* tbuf) {
   }
   int want = std::min((cap + 63) & ~63, TRACE_FAST_TBUF_MAX);
   if (const char* e = getenv("BIALIGN_TRACE_LDS")) want = std::min(want, std::max(64, atoi(e) & ~63));
-  const size_t fixed = ((b->lds_trace + 15) & ~size_t(15)) + TraceFast<S>::TAB_BYTES;
+  size_t fixed = ((b->lds_trace + 15) & ~size_t(15)) + TraceFast<S>::TAB_BYTES;
   if (fixed + 64 > 160 * 1024) return 0;
+  *wk = 0;
+  if constexpr (TraceWindow<S>::EXISTS) *wk = trace_window_records<S>(b, count, fixed, want);
+  if (*wk) fixed += TraceWindow<S>::lds_bytes(*wk);
   *tbuf = (int)std::min<size_t>(want, (160 * 1024 - fixed) & ~size_t(63));
   return fixed + *tbuf;
 }
@@ -555,11 +576,13 @@ int launch_traceback_affine(const bialign_batch* b, const DeviceBatch& v, int fi
   return with_flags<T_TRACE | T_PACK | T_DENSE1>(trace_flags(b, do_trace), [&](auto flags) -> int {
     constexpr unsigned F = decltype(flags)::value;
     if constexpr (traceback_fast_exists(S, F)) {
-      int tbuf = 0;
-      if (const size_t lds = trace_fast_lds<S>(b, first, count, &tbuf)) {
+      int tbuf = 0, wk = 0;
+      if (const size_t lds = trace_fast_lds<S>(b, first, count, &tbuf, &wk)) {
         DeviceBatch w = v;
         w.order = v.order + first;
-        return launch(traceback_affine_fast_kernel<S>, dim3(count), dim3(64), lds, b->eng->stream, w, count, tbuf);
+        if constexpr (TraceWindow<S>::EXISTS)
+          if (wk) return launch(traceback_affine_fast_kernel<S, true>, dim3(count), dim3(64), lds, b->eng->stream, w, count, tbuf, wk);
+        return launch(traceback_affine_fast_kernel<S, false>, dim3(count), dim3(64), lds, b->eng->stream, w, count, tbuf, 0);
       }
     }
     if constexpr (traceback_exists(true, S, F)) return launch_traceback_kernel(b, traceback_affine_of<S, F>(), do_trace, v, first, count);

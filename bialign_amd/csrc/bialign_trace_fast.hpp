@@ -138,9 +138,106 @@ struct TraceFast {
   }
 };
 
+// ---------------------------------------------------------------------------
+// The walk's LDS window (traceback_affine_fast_kernel<S, true>).  Seen from a point of lane row il >= 2 at record
+// T = j + 2 il + a, slot s = (il - 1) W + a, a column's candidates lie in records T - 3 .. T, slots s - W .. s (Entry:
+// record -(o0 + o1 + o2), slot -(W - 1) o0 - o2), and the pick moves the point by just such a candidate step.  So the
+// records the next columns read are known before any pick: a ring of the last K records of the strip is filled by LDS-DMA
+// D records ahead of T - 3, each record with the WS slots below the walk's slot at the time of issue.  A column all of
+// whose records have landed reads base and halfword dword from the ring instead of HBM; every other column (not
+// Col::fast, lane row 1, the columns after a strip change) takes the global loads: the window never changes a value,
+// only where it is read from.  tests/trace_window_check.hip proves coverage, addresses and the counted waits.
+// ---------------------------------------------------------------------------
 template <int S>
-__global__ void __launch_bounds__(64) traceback_affine_fast_kernel(const DeviceBatch A, int npairs, int tbuf_bytes) {
+struct TraceWindow {
   using TF = TraceFast<S>;
+  using PK = Pack<S>;
+  using R_ = Rec<S, 9>;
+  static constexpr int W = TF::W, RECB = TF::RECB;
+  static constexpr int RECS_PER_COL = 3;        // a column lowers T by o0 + o1 + o2 <= 3 ...
+  static constexpr int SPAN = RECS_PER_COL + 1; // ... and its candidates lie in that many records, T - 3 .. T
+  static constexpr int WS = S == 1 ? 16 : 32;   // slots of a window record: slot sl sits at position sl mod WS (s=1: one DMA instruction per record)
+  // How far the slot can fall while T falls by x records: x = x1 + 2 x0 - da and slot change = -W x0 + da for x0 rows up,
+  // x1 columns left and a band-row change da <= W - 1, so the slot falls by at most W x / 2 + (W - 1)(W - 2) / 2; it never rises.
+  __host__ __device__ static constexpr int drift(int x) { return (W * x + 1) / 2 + (W - 1) * (W - 2) / 2; }
+  // A record issued at (T, s) is at most D + 3 records below T and is read until T has fallen to it: the slots
+  // s - drift(D + 3) - W .. s must fit into WS, less one for the even start (the tail piece is 16 bytes = two slots).
+  __host__ __device__ static constexpr int lead_max() {
+    int d = -1;
+    while (drift(d + 1 + RECS_PER_COL) + W + 2 <= WS) ++d;
+    return d;
+  }
+  static constexpr int D = lead_max() < 4 ? lead_max() : 4;  // records of lead below T - 3 (s=1: 3, s=2: 4, s=3: none)
+  static constexpr bool EXISTS = D >= 0 && (PK::TAILDW == 0 || PK::TAILDW == 2);
+  static constexpr int K = 8, KMIN = SPAN;      // ring records (a power of two >= lead + SPAN); KMIN: no lead (tests)
+  static_assert(!EXISTS || (K >= D + SPAN && (K & (K - 1)) == 0 && (KMIN & (KMIN - 1)) == 0), "ring too short for the lead");
+  static_assert(!EXISTS || WS <= R_::SLP, "a window record is wider than a record");
+  // 16-byte pieces of a window record: NCH chunks of WS slots, then the tails of WS slots; whole DMA instructions
+  static constexpr int NPIECE16 = PK::NCH * WS + WS * PK::TAILDW / 4;
+  static constexpr int NDMA = (NPIECE16 + 63) / 64;
+  static constexpr int RB = NDMA * 1024;        // bytes of a window record
+  static constexpr int TAIL_AT = PK::NCH * WS * 16;
+  static constexpr int WTAB_BYTES = TF::ENTRIES * 4;
+  __host__ __device__ static constexpr int lds_bytes(int k) { return WTAB_BYTES + k * RB; }
+  __host__ __device__ static constexpr int lead(int k) { return k - SPAN < D ? k - SPAN : D; }  // ... of a ring of k records
+  // first slot of the record issued while the walk stands at slot s (even, >= 0; s <= SL - 1 keeps it <= SLP - WS)
+  __host__ __device__ static inline int slot_lo(int s) {
+    const int lo = (s + 2 - WS) & ~1;
+    return lo > 0 ? lo : 0;
+  }
+  // Source of lane `lane` of DMA instruction d: byte offset from the record's start = base + (slot << sh), with
+  // slot = slo + ((u - slo) mod WS), the slot of slo .. slo + WS - 1 that sits at position u.  The tail's lanes move two
+  // slots (u even, sh = 3); the surplus lanes of the last instruction repeat its last useful lane.
+  struct LaneSrc {
+    uint32_t base, u, sh;
+  };
+  __host__ __device__ static inline LaneSrc lane_src(int d, int lane) {
+    const int q = d * 64 + lane < NPIECE16 ? d * 64 + lane : NPIECE16 - 1;
+    const int p = q / WS, u = q - p * WS;
+    if (p < PK::NCH) return LaneSrc{(uint32_t)(p * R_::CH * 4), (uint32_t)u, 4u};
+    return LaneSrc{(uint32_t)(PK::NCH * R_::CH * 4), (uint32_t)(2 * u), 3u};
+  }
+  __host__ __device__ static inline uint32_t src_off(const LaneSrc& c, int slo) {
+    return c.base + (((uint32_t)slo + ((c.u - (uint32_t)slo) & (WS - 1))) << c.sh);
+  }
+  __host__ __device__ static inline uint32_t ring_byte(int r, int k) { return (uint32_t)(r & (k - 1)) * RB; }
+  // What a candidate adds to the column's (T, s): bits 0-11 byte offset of its halfword's dword in a window record at
+  // position 0, 16-17 records below T, 20-23 slots below s.  (Tail or not: Entry::lo bit 16.)
+  __host__ __device__ static inline uint32_t wentry(int st, int b0, int c) {
+    if (c >= 15) return 0;
+    const typename TF::Entry e = TF::entry(st, b0, c, 0, 0, 0);
+    if (((e.lo >> 4) & 15) == TF::NONE) return 0;
+    const int o0 = (e.lo >> 3) & 1, o1 = (e.lo >> 2) & 1, o2 = (e.lo >> 1) & 1, o3 = e.lo & 1;
+    const int v = (b0 + o1 - o3) * 9 + (int)((e.lo >> 4) & 15);
+    uint32_t woff = 0;
+    if (v != PK::ANCHOR) {
+      const int d = PK::hw(v) >> 1;
+      woff = d >= 4 * PK::NCH ? TAIL_AT + (d - 4 * PK::NCH) * 4 : (d >> 2) * WS * 16 + (d & 3) * 4;
+    }
+    return woff | (uint32_t)(o0 + o1 + o2) << 16 | (uint32_t)((W - 1) * o0 + o2) << 20;
+  }
+  // byte offsets, in the ring, of a candidate's base dword and of its halfword's dword for a column at (T, s)
+  __host__ __device__ static inline typename TF::Off addr(uint32_t we, bool tail, int T, int s, int k) {
+    const uint32_t ring = ring_byte(T - (int)((we >> 16) & 3), k), u = (uint32_t)(s - (int)((we >> 20) & 15)) & (WS - 1);
+    return typename TF::Off{ring + u * 16, ring + (we & 0xfffu) + (tail ? u * 8 : u * 16)};
+  }
+  // The records a column at T reads have landed when at most this many of the wave's DMA instructions are outstanding:
+  // those of the records below T - 3, issued later (vector memory operations retire in order).  The kernel has two waits:
+  // the full lead's, which is every column's but for the last ones above record 0 and for a short ring (tests), and 0.
+  __host__ __device__ static inline bool full_lead(int T, int next) { return T - RECS_PER_COL - next == D; }
+  __host__ __device__ static inline int may_pend(int T, int next) { return full_lead(T, next) ? D * NDMA : 0; }
+};
+
+template <int N>
+__device__ __forceinline__ void trace_window_wait() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+template <int S, bool WIN = false>
+__global__ void __launch_bounds__(64) traceback_affine_fast_kernel(const DeviceBatch A, int npairs, int tbuf_bytes, int wk) {
+  using TF = TraceFast<S>;
+  using TW = TraceWindow<S>;
+  static_assert(!WIN || TW::EXISTS, "no window at this max_shift");
   typedef typename TF::Entry Entry;
   const int pid = A.order[blockIdx.x];
   const PairDesc pd = A.pairs[pid];
@@ -162,8 +259,13 @@ __global__ void __launch_bounds__(64) traceback_affine_fast_kernel(const DeviceB
   const TraceInputs in = stage_trace_inputs<false>(A, pd, smem);
   const int staged = ((A.k1 * A.k1 + A.k2 * A.k2) * 4 + 2 * (code_pad(n) + code_pad(m)) + 15) & ~15;
   Entry* const tab = reinterpret_cast<Entry*>(reinterpret_cast<char*>(smem) + staged);
-  uint8_t* const tbuf = reinterpret_cast<uint8_t*>(tab + TF::ENTRIES);
+  // WIN: the window's candidate table and its ring of wk records lie between the table and the trace buffer
+  uint32_t* const wtab = reinterpret_cast<uint32_t*>(tab + TF::ENTRIES);
+  const char* const wring = reinterpret_cast<const char*>(wtab + TF::ENTRIES);
+  uint8_t* const tbuf = WIN ? reinterpret_cast<uint8_t*>(const_cast<char*>(wring) + wk * TW::RB) : reinterpret_cast<uint8_t*>(tab + TF::ENTRIES);
   for (int e = c; e < TF::ENTRIES; e += 64) tab[e] = TF::entry(e / (16 * W), (e >> 4) % W, e & 15, A.beta, A.gamma, A.delta);
+  if constexpr (WIN)
+    for (int e = c; e < TF::ENTRIES; e += 64) wtab[e] = TW::wentry(e / (16 * W), (e >> 4) % W, e & 15);
   __syncthreads();
 
   uint8_t* const out = A.trace + pd.trace_off;
@@ -186,9 +288,42 @@ __global__ void __launch_bounds__(64) traceback_affine_fast_kernel(const DeviceB
     __syncthreads();
     flushed += cnt;
   };
+  // WIN: records wnext .. (the record the strip's window began at) of the strip are in the ring or on their way, issued in
+  // falling order; wlive is false from a strip change until the next pick that leaves the walk in a lane row >= 2.
+#if defined(BIALIGN_EXP) && BIALIGN_EXP == 10
+  int whits = 0;  // columns served from the window, reported in place of the pair's score (tools/trace_window_share.py)
+#endif
+  [[maybe_unused]] int wnext = 0;
+  [[maybe_unused]] bool wlive = false;
+  [[maybe_unused]] const int wlead = TW::lead(wk);
+  [[maybe_unused]] const uint32_t wlds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) int32_t*)smem + (uint32_t)(wring - reinterpret_cast<const char*>(smem));
+  [[maybe_unused]] typename TW::LaneSrc wsrc[TW::NDMA];
+  if constexpr (WIN) {
+#pragma unroll
+    for (int d = 0; d < TW::NDMA; ++d) wsrc[d] = TW::lane_src(d, c);
+  }
+  // the DMAs of record r of the walk's strip, for a walk at slot s (the ghost feed's form: scalar base, lane offsets, m0)
+  [[maybe_unused]] auto wissue = [&](int r, int s) {
+    const char* const base = rowp + prb + (uint32_t)r * (uint32_t)TF::RECB;
+    const uint32_t dst0 = wlds + TW::ring_byte(r, wk);
+    const int slo = TW::slot_lo(s);
+#pragma unroll
+    for (int d = 0; d < TW::NDMA; ++d) {
+      const uint32_t off = TW::src_off(wsrc[d], slo), dst = dst0 + d * 1024;
+      uint32_t keep;
+      asm volatile(
+          "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+          "global_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
+          : "=&s"(keep)
+          : "v"(off), "s"(dst), "s"(base)
+          : "memory");
+    }
+  };
   while (true) {
     if ((i | j | k | l | (st ^ 8)) == 0) { complete = 1; break; }
     const Entry E = tabc[(st * W + (l - j + S)) * 16];
+    [[maybe_unused]] uint32_t we = 0;
+    if constexpr (WIN) we = (wtab + (c < 15 ? c : 15))[(st * W + (l - j + S)) * 16];
     // code bytes and table values of mu1, mu2 (uniform addresses): waited for where sc is formed
     int ca = in.sa[i - 1 + vz], cb = in.sb[j - 1 + vz], cc = in.ca[k - 1 + vz], cd = in.cb[l - 1 + vz];  // (index -1: inside the staged arrays' LDS, unused)
     const uint32_t lo = E.lo;
@@ -199,7 +334,30 @@ __global__ void __launch_bounds__(64) traceback_affine_fast_kernel(const DeviceB
     const bool ok = (lo & deny) == 0;  // pyx:133-141
     const typename TF::Col col = TF::column(pos.strip, pos.il, j, a0, P, m);
     int ld = 0;
-    if (col.fast) {
+    auto value = [&](int base, uint32_t word) {
+      const uint32_t half = (lo >> 17) & 3;
+      const uint32_t e = Pack<S>::offset_of(half == 1 ? word >> 16 : word & 0xffffu, base);
+      int v = base + (int)e;
+      if (((lo >> 19) & 1) && e == 0xffffu) v = NEG;
+      if (half == 2) v = base + 0x8000;
+      return v;
+    };
+    [[maybe_unused]] bool hit = false;
+    [[maybe_unused]] const int wT = j + 2 * pos.il + a0;
+    if constexpr (WIN) hit = col.fast && wlive && pos.il >= 2 && wT - TW::RECS_PER_COL >= wnext;
+    if (WIN && hit) {  // every candidate's record is in the ring once the DMAs of the records below T - 3 alone are pending
+      if constexpr (WIN) {
+#if defined(BIALIGN_EXP) && BIALIGN_EXP == 10
+        ++whits;
+#endif
+        if (TW::full_lead(wT, wnext)) trace_window_wait<TW::D * TW::NDMA>();
+        else trace_window_wait<0>();
+        if (ok) {
+          const typename TF::Off o = TW::addr(we, (lo >> 16) & 1, wT, (pos.il - 1) * W + a0, wk);
+          ld = value(*reinterpret_cast<const int32_t*>(wring + o.base), *reinterpret_cast<const uint32_t*>(wring + o.word));
+        }
+      }
+    } else if (col.fast) {
       if (ok) {
         const bool tail = (lo >> 16) & 1;
         uint32_t ob = col.u16 + (uint32_t)E.da, ow = (tail ? col.u8 : col.u16) + (uint32_t)E.db;
@@ -207,17 +365,14 @@ __global__ void __launch_bounds__(64) traceback_affine_fast_kernel(const DeviceB
           ob += up16;
           ow += tail ? up8 : up16;
         }
-        const int base = *reinterpret_cast<const int32_t*>(rowp + ob);
-        const uint32_t word = *reinterpret_cast<const uint32_t*>(rowp + ow);
-        const uint32_t half = (lo >> 17) & 3;
-        const uint32_t e = Pack<S>::offset_of(half == 1 ? word >> 16 : word & 0xffffu, base);
-        ld = base + (int)e;
-        if (((lo >> 19) & 1) && e == 0xffffu) ld = NEG;
-        if (half == 2) ld = base + 0x8000;
+        ld = value(*reinterpret_cast<const int32_t*>(rowp + ob), *reinterpret_cast<const uint32_t*>(rowp + ow));
       }
     } else if (ok) {  // a candidate may lie in a full record: packed_cell's own arithmetic
       const int o0 = (lo >> 3) & 1, o1 = (lo >> 2) & 1, o2 = (lo >> 1) & 1, o3 = lo & 1;
       ld = packed_load<S>(pbase, packed_addr<S>(pd, i - o0, j - o1, a0 + o0 - o2, (l - j + S) + o1 - o3, (lo >> 4) & 15));
+      // WIN: a use here, so that hipcc waits for these loads inside this path; left pending (in its model) where the path
+      // joins the others, the next write of their register drew a vmcnt(0) into the window's path, and with it every DMA
+      if constexpr (WIN) asm volatile("" ::"v"(ld));
     }
     bool z1 = false, z2 = false;
     if (edge) {
@@ -254,9 +409,25 @@ __global__ void __launch_bounds__(64) traceback_affine_fast_kernel(const DeviceB
     if (q0) {
       const int strip_was = pos.strip;
       pos.step_up(P);
-      if (pos.strip != strip_was) rowp -= prb;
+      if (pos.strip != strip_was) {
+        rowp -= prb;
+        if constexpr (WIN) wlive = false;  // the ring holds the strip below's records
+      }
+    }
+    if constexpr (WIN) {  // the records that entered the lead range, at most three but for the strip's first fill
+      const int a1 = k - i + S, Tn = j + 2 * pos.il + a1;
+      if (!wlive && pos.il >= 2) {
+        wlive = true;
+        wnext = Tn + 1;
+      }
+      if (wlive) {
+        const int low = max(Tn - TW::RECS_PER_COL - wlead, 0);
+        for (int r = wnext - 1; r >= low; --r) wissue(r, (pos.il - 1) * W + a1);
+        wnext = min(wnext, low);
+      }
     }
   }
+  if constexpr (WIN) trace_window_wait<0>();  // no DMA lands in LDS after the wave has ended
   if (len > cap) len = cap;
   if (flushed == 0) {  // the whole trace is in LDS: reversed (pyx:586) and coalesced
     __syncthreads();
@@ -277,6 +448,9 @@ __global__ void __launch_bounds__(64) traceback_affine_fast_kernel(const DeviceB
   if (c == 0) {
     A.trace_len[pid] = len;
     A.complete[pid] = complete;
+#if defined(BIALIGN_EXP) && BIALIGN_EXP == 10
+    if constexpr (WIN) A.scores[pid] = whits;
+#endif
   }
 }
 
