@@ -144,7 +144,7 @@ int replan_full(bialign_batch* b) {
   HIP_TRY(hipStreamSynchronize(st));
   const int64_t need = *std::max_element(b->full_dwords.begin(), b->full_dwords.end());
   if ((int64_t)b->d_layers.n < need + 16) HIP_TRY(b->d_layers.alloc((size_t)need + 16));
-  if (int rc = replan_full_layout(*b, (int64_t)b->d_layers.n - 16, (int64_t)b->d_tab.n)) return rc;
+  if (int rc = replan_full_layout(*b, (int64_t)b->d_layers.n - 16, (int64_t)b->tables.d_tab.n)) return rc;
   HIP_TRY(hipMemcpy(b->d_pairs.p, b->pairs.data(), b->pairs.size() * sizeof(PairDesc), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(b->d_order.p, b->order.data(), b->order.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   return BIALIGN_OK;
@@ -176,12 +176,12 @@ int probe_write_rate(bialign_engine* e, hipStream_t st, int32_t* p, size_t dword
 int alloc_replicas(bialign_batch* b) {
   HIP_TRY(b->d_seq_b.alloc((size_t)b->tot_b));
   HIP_TRY(b->d_cls_b.alloc((size_t)b->tot_b));
-  if (b->feat) HIP_TRY(b->d_feat_b.alloc(3 * (size_t)b->tot_b));  // ... and so the replicas' three planes of features
+  if (b->feat) HIP_TRY(b->tables.d_feat_b.alloc(3 * (size_t)b->tot_b));  // ... and so the replicas' three planes of features
   if (b->null_dense) {  // ... the replicas' permutations, and the real pairs' tables, which stay resident
-    HIP_TRY(b->d_null_perm.alloc((size_t)b->tot_b));
+    HIP_TRY(b->null.d_perm.alloc((size_t)b->tot_b));
     size_t real_dw = 0;
     for (int p = 0; p < b->npairs; p += b->null_R) real_dw += (size_t)b->tab_dwords[p];
-    HIP_TRY(b->d_null_tab.alloc(real_dw));
+    HIP_TRY(b->null.d_tab.alloc(real_dw));
   }
   return BIALIGN_OK;
 }
@@ -235,13 +235,13 @@ int alloc_tables(bialign_batch* b) {
   if (!b->tab_scratch()) return BIALIGN_OK;
   const size_t tab_dw = (size_t)b->max_chunk_tab_dwords;
   if (eng->tab_cache.p && eng->tab_cache.n >= tab_dw) {
-    b->d_tab.swap(eng->tab_cache);
+    b->tables.d_tab.swap(eng->tab_cache);
   } else {
     eng->tab_cache.release();
-    if (b->d_tab.alloc(tab_dw) != hipSuccess) {
+    if (b->tables.d_tab.alloc(tab_dw) != hipSuccess) {
       const hipError_t err = hipGetLastError();
-      b->d_tab.p = nullptr;
-      b->d_tab.n = 0;
+      b->tables.d_tab.p = nullptr;
+      b->tables.d_tab.n = 0;
       return fail(BIALIGN_E_DEVICE, "hipMalloc of %zu bytes of table storage failed: %s", tab_dw * 4, hipGetErrorString(err));
     }
   }
@@ -264,14 +264,13 @@ int upload_inputs(bialign_batch* b, const bialign_scoring* sc, const bialign_pai
   if (nul) {  // B once, as the caller gave it: the shuffle kernel writes d_seq_b / d_cls_b from it ahead of every run's sweeps
     // (codes a dense form replaces are not uploaded: the replicas' codes of that kind are zero like those of any dense batch)
     if (b->dense1) HIP_TRY(hipMemsetAsync(b->d_seq_b.p, 0, std::max<size_t>((size_t)tot_b, 1), st));
-    else HIP_TRY(b->d_null_seq.upload(nul->seq_b, (size_t)nul->tot_b, st));
+    else HIP_TRY(b->null.d_seq.upload(nul->seq_b, (size_t)nul->tot_b, st));
     if (b->dense)  // (FEATURE form too: no classes)
       HIP_TRY(hipMemsetAsync(b->d_cls_b.p, 0, std::max<size_t>((size_t)tot_b, 1), st));
     else
-      HIP_TRY(b->d_null_cls.upload(nul->cls_b, (size_t)nul->tot_b, st));
-    HIP_TRY(b->d_null_off.upload(nul->off_b, (size_t)nul->npairs, st));
-    HIP_TRY(b->d_null_stats.alloc((size_t)nul->npairs));
-    for (hipEvent_t& e : b->null_evs) HIP_TRY(hipEventCreate(&e));
+      HIP_TRY(b->null.d_cls.upload(nul->cls_b, (size_t)nul->tot_b, st));
+    HIP_TRY(b->null.d_off.upload(nul->off_b, (size_t)nul->npairs, st));
+    HIP_TRY(b->null.d_stats.alloc((size_t)nul->npairs));
   } else {
     HIP_TRY(b->d_seq_b.upload(b->dense1 ? zeros.data() : pr->seq_b, tot_b, st));
     HIP_TRY(b->d_cls_b.upload(b->dense ? zeros.data() : pr->cls_b, tot_b, st));
@@ -279,17 +278,17 @@ int upload_inputs(bialign_batch* b, const bialign_scoring* sc, const bialign_pai
   std::vector<int32_t> tabs;
   std::vector<int64_t> mu1_offs;
   if (b->feat) {  // the molecules' features, three planes per side; a dense mu1's tables resident, pair after pair
-    b->feat_tot_a = tot_a;
-    b->feat_tot_b = tot_b;
+    b->tables.feat_tot_a = tot_a;
+    b->tables.feat_tot_b = tot_b;
     const double* src_a[3] = {ft->up_a, ft->down_a, ft->unp_a};
     const double* src_b[3] = {ft->up_b, ft->down_b, ft->unp_b};
-    HIP_TRY(b->d_feat_a.alloc(3 * (size_t)tot_a));
-    // null batch: d_feat_b is the replica planes (allocated above, filled by the shuffle kernel); B's own go beside d_null_seq
-    DevBuf<double>& up_b = nul ? b->d_null_feat : b->d_feat_b;
+    HIP_TRY(b->tables.d_feat_a.alloc(3 * (size_t)tot_a));
+    // null batch: d_feat_b is the replica planes (allocated above, filled by the shuffle kernel); B's own go beside null.d_seq
+    DevBuf<double>& up_b = nul ? b->null.d_feat : b->tables.d_feat_b;
     const int64_t src_tot_b = nul ? nul->tot_b : tot_b;
     HIP_TRY(up_b.alloc(3 * (size_t)src_tot_b));
     for (int f = 0; f < 3; ++f) {
-      HIP_TRY(hipMemcpyAsync(b->d_feat_a.p + (size_t)f * tot_a, src_a[f], (size_t)tot_a * sizeof(double), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(b->tables.d_feat_a.p + (size_t)f * tot_a, src_a[f], (size_t)tot_a * sizeof(double), hipMemcpyHostToDevice, st));
       HIP_TRY(hipMemcpyAsync(up_b.p + (size_t)f * src_tot_b, src_b[f], (size_t)src_tot_b * sizeof(double), hipMemcpyHostToDevice, st));
     }
     if (b->dense1) {
@@ -299,13 +298,13 @@ int upload_inputs(bialign_batch* b, const bialign_scoring* sc, const bialign_pai
       tabs.resize(tot1);
       for (int p = 0; p < pr->npairs; ++p)
         std::memcpy(tabs.data() + mu1_offs[p], pr->mu1_dense + pr->mu1_off[p], (size_t)pr->len_a[p] * pr->len_b[p] * sizeof(int32_t));
-      HIP_TRY(b->d_mu1.upload(tabs.data(), tabs.size(), st));
-      HIP_TRY(b->d_mu1_off.upload(mu1_offs.data(), mu1_offs.size(), st));
+      HIP_TRY(b->tables.d_mu1.upload(tabs.data(), tabs.size(), st));
+      HIP_TRY(b->tables.d_mu1_off.upload(mu1_offs.data(), mu1_offs.size(), st));
     }
   } else if (b->null_dense) {  // the REAL pairs' tables end to end, mu2's, then mu1's; every replica's are made from them per chunk
     const int R = nul->replicas;
     std::vector<int64_t> offs((size_t)nul->npairs);
-    tabs.resize(b->d_null_tab.n);
+    tabs.resize(b->null.d_tab.n);
     int64_t at = 0;
     for (int p = 0; p < nul->npairs; ++p) {
       const size_t v = (size_t)p * R, nm = (size_t)pr->len_a[v] * pr->len_b[v];
@@ -313,8 +312,8 @@ int upload_inputs(bialign_batch* b, const bialign_scoring* sc, const bialign_pai
       if (b->dense) std::memcpy(tabs.data() + at, pr->mu2_dense + pr->mu2_off[v], nm * sizeof(int32_t)), at += (int64_t)nm;
       if (b->dense1) std::memcpy(tabs.data() + at, pr->mu1_dense + pr->mu1_off[v], nm * sizeof(int32_t)), at += (int64_t)nm;
     }
-    if (!tabs.empty()) HIP_TRY(hipMemcpyAsync(b->d_null_tab.p, tabs.data(), tabs.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(b->d_null_tab_off.upload(offs.data(), offs.size(), st));
+    if (!tabs.empty()) HIP_TRY(hipMemcpyAsync(b->null.d_tab.p, tabs.data(), tabs.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(b->null.d_tab_off.upload(offs.data(), offs.size(), st));
   } else if (b->dense || b->dense1) {  // the pairs' tables end to end (PairDesc::tab_off): mu2's, then mu1's
     tabs.resize((size_t)tot_tab);
     for (int p = 0; p < pr->npairs; ++p) {
@@ -323,7 +322,7 @@ int upload_inputs(bialign_batch* b, const bialign_scoring* sc, const bialign_pai
       if (b->dense) std::memcpy(dst, pr->mu2_dense + pr->mu2_off[p], nm * sizeof(int32_t)), dst += nm;
       if (b->dense1) std::memcpy(dst, pr->mu1_dense + pr->mu1_off[p], nm * sizeof(int32_t));
     }
-    HIP_TRY(b->d_tab.upload(tabs.data(), tabs.size(), st));
+    HIP_TRY(b->tables.d_tab.upload(tabs.data(), tabs.size(), st));
   }
   if (getenv("BIALIGN_DEBUG")) {  // placement study: address and plain streaming-write rate of the layer buffer
     const size_t layer_dw = b->d_layers.n;
@@ -346,41 +345,6 @@ int upload_inputs(bialign_batch* b, const bialign_scoring* sc, const bialign_pai
   HIP_TRY(hipEventCreateWithFlags(&b->uploaded, hipEventDisableTiming));
   HIP_TRY(hipEventRecord(b->uploaded, st));
   HIP_TRY(hipStreamSynchronize(st));  // the caller's host arrays may go away now
-  return BIALIGN_OK;
-}
-
-// ---- hit search (bialign_hits.hpp): what a launch is given, and the state its results have ahead of a run
-HitArgs hit_args(const bialign_batch* b, bool search) {
-  HitArgs h{};
-  h.max_hits = b->hit_spec.max_hits, h.max_walks = b->hit_spec.max_walks, h.min_score = b->hit_spec.min_score;
-  h.search = search ? 1 : 0;
-  h.lds_inputs = (int32_t)((b->lds_trace + 15) & ~size_t(15));
-  h.mask_words = b->hit_mask_words;
-  h.prof_off = b->d_hit_prof_off.p;
-  h.profile = b->d_hit_profile.p;
-  h.head = b->d_hit_head.p;
-  h.hits = b->d_hit_rec.p;
-  h.walks = b->d_hit_walks.p;
-  h.trace = b->d_hit_trace.p;
-  return h;
-}
-
-// profile: -infinity; status NOT_SEARCHED, no hits, no walks; records -1
-int reset_hits(bialign_batch* b, hipStream_t st) {
-  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)b->d_hit_profile.p, BIALIGN_NEG_INF, b->d_hit_profile.n, st));
-  HIP_TRY(hipMemsetAsync(b->d_hit_head.p, 0, sizeof(int32_t) * b->d_hit_head.n, st));
-  HIP_TRY(hipMemsetAsync(b->d_hit_rec.p, 0xff, sizeof(int32_t) * b->d_hit_rec.n, st));
-  HIP_TRY(hipMemsetAsync(b->d_hit_walks.p, 0xff, sizeof(int32_t) * b->d_hit_walks.n, st));
-  return BIALIGN_OK;
-}
-
-// the hit getters' common refusals, and the end of a pending run
-int hits_ready(const bialign_batch* b) {
-  if (!b) return fail(BIALIGN_E_INVALID, "NULL batch");
-  if (int rc = bialign_batch_wait(const_cast<bialign_batch*>(b))) return rc;
-  if (!b->hits_on) return fail(BIALIGN_E_INVALID, "no hit search is set on this batch (bialign_batch_set_hits)");
-  if (!b->ran || !b->hits_ran) return fail(BIALIGN_E_INVALID, "bialign_batch_run has not been called since bialign_batch_set_hits");
-  HIP_TRY(hipSetDevice(b->eng->device));
   return BIALIGN_OK;
 }
 
@@ -548,9 +512,9 @@ void bialign_batch_destroy(bialign_batch* b) {
     if (!slot) slot = eng->layer_cache.n <= eng->layer_cache2.n ? &eng->layer_cache : &eng->layer_cache2;
     if (!slot->p || b->d_layers.n > slot->n) slot->swap(b->d_layers);
   }
-  if (b->tab_scratch() && b->d_tab.p && !eng->closing) {  // ... and so the table buffer (the stream is idle here or was never used)
+  if (b->tab_scratch() && b->tables.d_tab.p && !eng->closing) {  // ... and so the table buffer (the stream is idle here or was never used)
     (void)hipStreamSynchronize(eng->stream);
-    if (!eng->tab_cache.p || b->d_tab.n > eng->tab_cache.n) eng->tab_cache.swap(b->d_tab);
+    if (!eng->tab_cache.p || b->tables.d_tab.n > eng->tab_cache.n) eng->tab_cache.swap(b->tables.d_tab);
   }
   delete b;
   if (--eng->live_batches == 0 && eng->closing) bialign_engine_destroy(eng);
@@ -613,86 +577,82 @@ int bialign_batch_get_info(const bialign_batch* b, bialign_batch_info* info) {
   return BIALIGN_OK;
 }
 
-// Enqueue one run of the batch on the engine's stream (all chunks: fill, then traceback).
+// How a run walks back, decided once per run.  Full records: the traceback kernel, which on a fill-only run reads the
+// scores alone.  LEAN records: the sweep itself wrote the scores, and only the round forms walk.
+enum class TraceForm { Kernel, LeanRounds, LevelRounds, None };
+static TraceForm trace_form(const bialign_batch* b, uint32_t flags) {
+  if (!b->lean) return TraceForm::Kernel;
+  if (flags & BIALIGN_RUN_FILL_ONLY) return TraceForm::None;
+  return b->lean_trace ? TraceForm::LeanRounds : (b->level_trace ? TraceForm::LevelRounds : TraceForm::None);
+}
+
+// One chunk of a run, stage by stage: tables, fill, traceback, hits.  Stream order keeps it ahead of the next chunk's.
+static int run_chunk(bialign_batch* b, const DeviceBatch& v, int c, TraceForm form, bool do_trace) {
+  const int first = b->chunk_begin[c], count = b->chunk_begin[c + 1] - first;
+  hipStream_t st = b->eng->stream;
+  StageClock& clk = b->clock;
+  if (b->tab_scratch()) {
+    // FEATURE form: the chunk's mu2 tables, built into the table buffer ahead of the sweep (timed on its own, outside
+    // fill_ms).  They stay until the next chunk's build, which stream order puts behind this chunk's tracebacks -- every
+    // lean re-sweep round included -- so no round has to build them again.  DENSE-form null batch: the chunk's
+    // replicas' tables, the real pairs' with their columns permuted, in the same slot.
+    HIP_TRY(clk.mark(st));
+    if (int rc = b->null_dense ? launch_permute_tables(b, first, count) : launch_build_mu2(b, first, count)) return rc;
+    HIP_TRY(clk.mark(st, Stage::Tables));
+    ++b->tables.build_launches;
+  }
+  HIP_TRY(clk.mark(st));
+  int rc = launch_fill(b, v, first, count);
+  if (rc == BIALIGN_OK && b->end_key()) rc = launch_end_key_finish(b, v, first, count);  // scores and ends (local: in every storage mode)
+  if (rc) return rc;
+  HIP_TRY(clk.mark(st, Stage::Fill));
+  switch (form) {
+    case TraceForm::Kernel: rc = launch_traceback(b, v, first, count, do_trace); break;
+    case TraceForm::LeanRounds: rc = lean_traceback_rounds(b, v, first, count); break;
+    case TraceForm::LevelRounds: rc = level_traceback_rounds(b, v, first, count); break;
+    case TraceForm::None: break;
+  }
+  if (rc) return rc;
+  HIP_TRY(clk.mark(st, Stage::Traceback));  // (it began at the fill's end)
+  if (b->hits.on) {  // behind the chunk's traceback, ahead of the next chunk's sweep: the layers are still the chunk's
+    HIP_TRY(clk.mark(st));
+    if (int rc2 = launch_fit_hits(b, v, hit_args(b, do_trace), first, count)) return rc2;
+    HIP_TRY(clk.mark(st, Stage::Hits));
+  }
+  b->timing.fill_launches += 1;
+  b->timing.traceback_launches += 1;
+  b->timing.waves_per_pair = std::abs(b->last_team);
+  b->timing.cross_cu = b->last_team < 0;
+  return BIALIGN_OK;
+}
+
+// Enqueue one run of the batch on the engine's stream: what is per run, then every chunk.
 static int enqueue_run(bialign_batch* b, uint32_t flags) {
   HIP_TRY(hipSetDevice(b->eng->device));
-  const bool do_trace = !(flags & BIALIGN_RUN_FILL_ONLY) && (!b->lean || b->lean_trace || b->level_trace);
+  const TraceForm form = trace_form(b, flags);
+  const bool do_trace = !(flags & BIALIGN_RUN_FILL_ONLY) && form != TraceForm::None;  // a trace is walked and written
   const DeviceBatch v = b->view();
   hipStream_t st = b->eng->stream;
   b->timing = bialign_timing{};
+  b->clock.reset();
   b->ran = b->ran_trace = false;
   b->used_xcu = b->used_pack = false;
-  const int nchunks = (int)b->chunk_begin.size() - 1;
-  while ((int)b->evs.size() < 3 * nchunks) {
-    hipEvent_t e = nullptr;
-    HIP_TRY(hipEventCreate(&e));
-    b->evs.push_back(e);
-  }
-  while (b->tab_scratch() && (int)b->build_evs.size() < 2 * nchunks) {
-    hipEvent_t e = nullptr;
-    HIP_TRY(hipEventCreate(&e));
-    b->build_evs.push_back(e);
-  }
-  b->build_ms = 0;
-  b->build_launches = 0;
+  b->hits.pending = b->hits.on;  // every chunk's search follows its traceback
+  b->tables.build_launches = 0;
   HIP_TRY(hipStreamWaitEvent(st, b->uploaded, 0));
   HIP_TRY(hipMemsetAsync(b->d_err.p, 0, sizeof(int32_t), st));  // the flag is per run
   if (b->free_ends()) HIP_TRY(hipMemsetAsync(b->d_span.p, 0xff, sizeof(int32_t) * b->d_span.n, st));  // spans: -1 until a kernel writes them
   if (b->end_key())  // keys: zero, below every key a sweep folds in
     HIP_TRY(hipMemsetAsync(b->d_end_key.p, 0, sizeof(unsigned long long) * b->npairs, st));
-  b->hits_pending = false;
-  if (b->hits_on) {  // hit search: its results are per run, like the spans
-    while ((int)b->hit_evs.size() < 2 * nchunks) {
-      hipEvent_t e = nullptr;
-      HIP_TRY(hipEventCreate(&e));
-      b->hit_evs.push_back(e);
-    }
+  if (b->hits.on)  // hit search: its results are per run, like the spans
     if (int rc = reset_hits(b, st)) return rc;
-  }
   if (b->null_R) {  // null batch: the replicas' B codes, all of them ahead of the first sweep (timed on its own, outside fill_ms)
-    HIP_TRY(hipEventRecord(b->null_evs[0], st));
+    HIP_TRY(b->clock.mark(st));
     if (int rc = launch_shuffle_null(b, 0, b->npairs)) return rc;
-    HIP_TRY(hipEventRecord(b->null_evs[1], st));
+    HIP_TRY(b->clock.mark(st, Stage::Shuffle));
   }
-  for (int c = 0; c < nchunks; ++c) {  // stream order keeps chunk c's traceback ahead of chunk c+1's sweep
-    const int first = b->chunk_begin[c], count = b->chunk_begin[c + 1] - first;
-    if (b->tab_scratch()) {
-      // FEATURE form: the chunk's mu2 tables, built into the table buffer ahead of the sweep (timed on its own, outside
-      // fill_ms).  They stay until the next chunk's build, which stream order puts behind this chunk's tracebacks -- every
-      // lean re-sweep round included -- so no round has to build them again.  DENSE-form null batch: the chunk's
-      // replicas' tables, the real pairs' with their columns permuted, in the same slot.
-      HIP_TRY(hipEventRecord(b->build_evs[2 * c], st));
-      if (int rc = b->null_dense ? launch_permute_tables(b, first, count) : launch_build_mu2(b, first, count)) return rc;
-      HIP_TRY(hipEventRecord(b->build_evs[2 * c + 1], st));
-      ++b->build_launches;
-    }
-    HIP_TRY(hipEventRecord(b->evs[3 * c], st));
-    int rc = launch_fill(b, v, first, count);
-    if (rc == BIALIGN_OK && b->end_key()) rc = launch_end_key_finish(b, v, first, count);  // scores and ends (local: in every storage mode)
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(b->evs[3 * c + 1], st));
-    if (!b->lean) {  // (with LEAN records the sweep itself wrote the scores)
-      rc = launch_traceback(b, v, first, count, do_trace);
-      if (rc) return rc;
-    } else if (b->lean_trace && do_trace) {
-      rc = lean_traceback_rounds(b, v, first, count);
-      if (rc) return rc;
-    } else if (b->level_trace && do_trace) {
-      rc = level_traceback_rounds(b, v, first, count);
-      if (rc) return rc;
-    }
-    HIP_TRY(hipEventRecord(b->evs[3 * c + 2], st));
-    if (b->hits_on) {  // behind the chunk's traceback, ahead of the next chunk's sweep: the layers are still the chunk's
-      HIP_TRY(hipEventRecord(b->hit_evs[2 * c], st));
-      if (int rc2 = launch_fit_hits(b, v, hit_args(b, do_trace), first, count)) return rc2;
-      HIP_TRY(hipEventRecord(b->hit_evs[2 * c + 1], st));
-      b->hits_pending = true;
-    }
-    b->timing.fill_launches += 1;
-    b->timing.traceback_launches += 1;
-    b->timing.waves_per_pair = std::abs(b->last_team);
-    b->timing.cross_cu = b->last_team < 0;
-  }
+  for (int c = 0; c + 1 < (int)b->chunk_begin.size(); ++c)
+    if (int rc = run_chunk(b, v, c, form, do_trace)) return rc;
   b->pending = true;
   b->pending_trace = do_trace;
   b->pending_flags = flags;
@@ -705,33 +665,9 @@ int bialign_batch_wait(bialign_batch* b) {
   HIP_TRY(hipSetDevice(b->eng->device));
   for (;;) {
     b->pending = false;
-    const int nchunks = (int)b->chunk_begin.size() - 1;
-    HIP_TRY(hipEventSynchronize(b->evs[3 * nchunks - 1]));  // (a re-planned batch may have fewer chunks than events)
-    for (int c = 0; c < nchunks; ++c) {
-      float f = 0, t = 0;
-      HIP_TRY(hipEventElapsedTime(&f, b->evs[3 * c], b->evs[3 * c + 1]));
-      HIP_TRY(hipEventElapsedTime(&t, b->evs[3 * c + 1], b->evs[3 * c + 2]));
-      b->timing.fill_ms += f;
-      b->timing.traceback_ms += t;
-      if (b->tab_scratch()) {
-        HIP_TRY(hipEventElapsedTime(&f, b->build_evs[2 * c], b->build_evs[2 * c + 1]));
-        b->build_ms += f;
-      }
-    }
-    if (b->null_R) {
-      float f = 0;
-      HIP_TRY(hipEventElapsedTime(&f, b->null_evs[0], b->null_evs[1]));
-      b->shuffle_ms = f;
-    }
-    if (b->hits_pending) {  // the last chunk's search lies behind the event waited for above
-      HIP_TRY(hipEventSynchronize(b->hit_evs[2 * nchunks - 1]));
-      b->search_ms = 0;
-      for (int c = 0; c < nchunks; ++c) {
-        float f = 0;
-        HIP_TRY(hipEventElapsedTime(&f, b->hit_evs[2 * c], b->hit_evs[2 * c + 1]));
-        b->search_ms += f;
-      }
-    }
+    HIP_TRY(b->clock.finish());
+    b->timing.fill_ms = b->clock.ms(Stage::Fill);
+    b->timing.traceback_ms = b->clock.ms(Stage::Traceback);
     int32_t err = 0;
     HIP_TRY(hipMemcpy(&err, b->d_err.p, sizeof err, hipMemcpyDeviceToHost));
     if (!err) break;
@@ -759,7 +695,7 @@ int bialign_batch_wait(bialign_batch* b) {
   b->timing.packed_records = b->used_pack ? 1 : 0;
   b->ran = true;
   b->ran_trace = b->pending_trace;
-  b->hits_ran = b->hits_pending;
+  b->hits.ran = b->hits.pending;
   return BIALIGN_OK;
 }
 
@@ -833,112 +769,6 @@ int bialign_batch_get_traces(const bialign_batch* b, uint8_t* trace, int64_t* tr
   return BIALIGN_OK;
 }
 
-int bialign_batch_set_hits(bialign_batch* b, const bialign_hit_spec* spec) {
-  if (!b) return fail(BIALIGN_E_INVALID, "NULL batch");
-  if (int rc = bialign_batch_wait(b)) return rc;  // a pending run still writes the buffers released below
-  HIP_TRY(hipSetDevice(b->eng->device));
-  b->release_hits();
-  if (!spec) return BIALIGN_OK;
-  if (b->mode != bialign::AlignMode::Fit || b->lean || b->null_R)
-    return fail(BIALIGN_E_UNSUPPORTED, "the hit search needs a FIT batch in full storage (not %s)",
-                b->null_R ? "a null batch" : (b->mode != bialign::AlignMode::Fit ? "a batch without BIALIGN_BATCH_FIT" : "SCORE_ONLY"));
-  if (spec->max_hits < 1 || spec->max_hits > 256) return fail(BIALIGN_E_INVALID, "max_hits must be 1..256, got %d", spec->max_hits);
-  if (spec->min_score < 1) return fail(BIALIGN_E_INVALID, "min_score must be >= 1, got %d", spec->min_score);
-  if (spec->max_walks != 0 && spec->max_walks < spec->max_hits)
-    return fail(BIALIGN_E_INVALID, "max_walks must be 0 (4 * max_hits) or >= max_hits = %d, got %d", spec->max_hits, spec->max_walks);
-  if (spec->reserved != 0) return fail(BIALIGN_E_INVALID, "bialign_hit_spec.reserved must be 0");
-  bialign_hit_spec sp = *spec;
-  if (sp.max_walks == 0) sp.max_walks = 4 * sp.max_hits;
-  int max_m = 0;
-  b->hit_prof_off.assign((size_t)b->npairs + 1, 0);
-  for (int p = 0; p < b->npairs; ++p) {
-    max_m = std::max(max_m, b->pairs[p].m);
-    b->hit_prof_off[p + 1] = b->hit_prof_off[p] + b->pairs[p].m + 1;
-  }
-  b->hit_spec = sp;
-  b->hit_mask_words = (max_m + 32) >> 5;
-  const size_t lds = fit_hits_lds(hit_args(b, true));
-  if (lds > 160 * 1024)
-    return fail(BIALIGN_E_UNSUPPORTED, "the hit search's mask, spans and staged inputs need %zu bytes of LDS (160 KiB at most)", lds);
-  const size_t prof = (size_t)b->hit_prof_off.back(), recs = (size_t)b->npairs * sp.max_hits * 4,
-               walks = (size_t)b->npairs * sp.max_walks * 4, trace = (size_t)sp.max_hits * (size_t)b->trace_bytes;
-  hipStream_t st = b->eng->stream;
-  hipError_t err = b->d_hit_profile.alloc(prof);
-  if (err == hipSuccess) err = b->d_hit_head.alloc(4 * (size_t)b->npairs);
-  if (err == hipSuccess) err = b->d_hit_rec.alloc(recs);
-  if (err == hipSuccess) err = b->d_hit_walks.alloc(walks);
-  if (err == hipSuccess) err = b->d_hit_trace.alloc(trace);
-  if (err == hipSuccess) err = b->d_hit_prof_off.upload(b->hit_prof_off.data(), (size_t)b->npairs, st);
-  if (err == hipSuccess) err = hipStreamSynchronize(st);
-  if (err == hipSuccess && getenv("BIALIGN_TEST_FAIL_HITS_ALLOC")) err = hipErrorOutOfMemory;  // tests: pretend an allocation failed
-  if (err != hipSuccess) {
-    (void)hipGetLastError();
-    b->release_hits();
-    return fail(BIALIGN_E_NOMEM, "hit search: allocating %zu bytes of result buffers failed: %s",
-                (prof + 4 * (size_t)b->npairs + recs + walks) * 4 + trace, hipGetErrorString(err));
-  }
-  b->hit_bytes = (int64_t)((prof + 4 * (size_t)b->npairs + recs + walks) * 4 + trace + (size_t)b->npairs * 8);
-  b->hits_on = true;
-  b->search_ms = 0;
-  return BIALIGN_OK;
-}
-
-int bialign_batch_get_hit_profile(const bialign_batch* b, int32_t pair, int32_t* out) {
-  if (!out) return fail(BIALIGN_E_INVALID, "NULL argument");
-  if (int rc = hits_ready(b)) return rc;
-  if (pair < 0 || pair >= b->npairs) return fail(BIALIGN_E_INVALID, "pair %d out of range", pair);
-  HIP_TRY(hipMemcpy(out, b->d_hit_profile.p + b->hit_prof_off[pair], sizeof(int32_t) * (b->pairs[pair].m + 1), hipMemcpyDeviceToHost));
-  return BIALIGN_OK;
-}
-
-int bialign_batch_get_hits(const bialign_batch* b, int32_t* nhits, int32_t* status, int32_t* start_b, int32_t* end_b,
-                           int32_t* score, int32_t* trace_len, uint8_t* trace, int64_t* trace_off) {
-  if (!nhits || !status || !start_b || !end_b || !score || !trace_len || !trace != !trace_off) return fail(BIALIGN_E_INVALID, "NULL argument");
-  if (int rc = hits_ready(b)) return rc;
-  const int K = b->hit_spec.max_hits;
-  std::vector<int32_t> head(4 * (size_t)b->npairs), rec((size_t)b->npairs * K * 4);
-  HIP_TRY(hipMemcpy(head.data(), b->d_hit_head.p, sizeof(int32_t) * head.size(), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(rec.data(), b->d_hit_rec.p, sizeof(int32_t) * rec.size(), hipMemcpyDeviceToHost));
-  if (trace) HIP_TRY(hipMemcpy(trace, b->d_hit_trace.p, (size_t)K * b->trace_bytes, hipMemcpyDeviceToHost));
-  for (int p = 0; p < b->npairs; ++p) {
-    nhits[p] = head[4 * (size_t)p], status[p] = head[4 * (size_t)p + 2];
-    for (int h = 0; h < K; ++h) {
-      const size_t t = (size_t)p * K + h;
-      start_b[t] = rec[4 * t], end_b[t] = rec[4 * t + 1], score[t] = rec[4 * t + 2], trace_len[t] = rec[4 * t + 3];
-      if (trace_off) trace_off[t] = (int64_t)K * b->pairs[p].trace_off + (int64_t)h * b->pairs[p].trace_cap;
-    }
-  }
-  return BIALIGN_OK;
-}
-
-int bialign_batch_get_hit_walks(const bialign_batch* b, int32_t* nwalks, int32_t* end_b, int32_t* start_b, int32_t* score,
-                                int32_t* accepted) {
-  if (!nwalks || !end_b || !start_b || !score || !accepted) return fail(BIALIGN_E_INVALID, "NULL argument");
-  if (int rc = hits_ready(b)) return rc;
-  const int K = b->hit_spec.max_walks;
-  std::vector<int32_t> head(4 * (size_t)b->npairs), rec((size_t)b->npairs * K * 4);
-  HIP_TRY(hipMemcpy(head.data(), b->d_hit_head.p, sizeof(int32_t) * head.size(), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(rec.data(), b->d_hit_walks.p, sizeof(int32_t) * rec.size(), hipMemcpyDeviceToHost));
-  for (int p = 0; p < b->npairs; ++p) {
-    nwalks[p] = head[4 * (size_t)p + 1];
-    for (int h = 0; h < K; ++h) {
-      const size_t t = (size_t)p * K + h;
-      end_b[t] = rec[4 * t], start_b[t] = rec[4 * t + 1], score[t] = rec[4 * t + 2], accepted[t] = rec[4 * t + 3];
-    }
-  }
-  return BIALIGN_OK;
-}
-
-int bialign_batch_get_hit_info(const bialign_batch* b, bialign_hit_info* info) {
-  if (!b || !info) return fail(BIALIGN_E_INVALID, "NULL argument");
-  if (int rc = bialign_batch_wait(const_cast<bialign_batch*>(b))) return rc;
-  if (!b->hits_on) return fail(BIALIGN_E_INVALID, "no hit search is set on this batch (bialign_batch_set_hits)");
-  info->spec = b->hit_spec;
-  info->buffer_bytes = b->hit_bytes;
-  info->search_ms = b->hits_ran ? b->search_ms : 0;
-  return BIALIGN_OK;
-}
-
 int bialign_batch_dump_layers(bialign_batch* b, int32_t pair, int32_t* out) {
   if (!b || !out) return fail(BIALIGN_E_INVALID, "NULL argument");
   if (pair < 0 || pair >= b->npairs) return fail(BIALIGN_E_INVALID, "pair %d out of range", pair);
@@ -1005,7 +835,7 @@ int bialign_batch_dump_mu2(bialign_batch* b, int32_t pair, int32_t* out) {
     if (int rc = launch_build_mu2(b, pos, 1)) return rc;
   }
   const PairDesc& d = b->pairs[pair];
-  HIP_TRY(hipMemcpyAsync(out, b->d_tab.p + d.tab_off, (size_t)d.n * d.m * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(out, b->tables.d_tab.p + d.tab_off, (size_t)d.n * d.m * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return BIALIGN_OK;
 }
@@ -1014,138 +844,12 @@ int bialign_batch_get_feature_info(const bialign_batch* b, bialign_feature_info*
   if (!b || !info) return fail(BIALIGN_E_INVALID, "NULL argument");
   if (int rc = bialign_batch_wait(const_cast<bialign_batch*>(b))) return rc;
   info->form = b->feat ? BIALIGN_MU2_FEATURE : (b->dense ? BIALIGN_MU2_DENSE : BIALIGN_MU2_LOOKUP);
-  info->build_launches = b->build_launches;
+  info->build_launches = b->tables.build_launches;
   int64_t dense_dw = 0;  // DENSE: every pair's mu2 table is resident
   if (b->dense && !b->tab_scratch())
     for (const PairDesc& d : b->pairs) dense_dw += (int64_t)d.n * d.m;
   info->table_bytes = 4 * (b->tab_scratch() ? b->max_chunk_tab_dwords : dense_dw);
-  info->build_ms = b->build_ms;
-  return BIALIGN_OK;
-}
-
-int bialign_batch_get_null_scores(const bialign_batch* b, int32_t* out) {
-  if (!b || !out) return fail(BIALIGN_E_INVALID, "NULL argument");
-  if (!b->null_R) return fail(BIALIGN_E_INVALID, "not a null batch (bialign_batch_create_null)");
-  if (int rc = bialign_batch_wait(const_cast<bialign_batch*>(b))) return rc;
-  if (!b->ran) return fail(BIALIGN_E_INVALID, "bialign_batch_run has not been called");
-  HIP_TRY(hipSetDevice(b->eng->device));
-  HIP_TRY(hipMemcpy(out, b->d_scores.p, sizeof(int32_t) * b->npairs, hipMemcpyDeviceToHost));
-  return BIALIGN_OK;
-}
-
-int bialign_batch_get_null_stats(const bialign_batch* cb, const int32_t* observed, bialign_null_stats* out) {
-  if (!cb || !out) return fail(BIALIGN_E_INVALID, "NULL argument");
-  if (!cb->null_R) return fail(BIALIGN_E_INVALID, "not a null batch (bialign_batch_create_null)");
-  bialign_batch* b = const_cast<bialign_batch*>(cb);  // (the reduction's buffers and times are the batch's)
-  if (int rc = bialign_batch_wait(b)) return rc;
-  if (!b->ran) return fail(BIALIGN_E_INVALID, "bialign_batch_run has not been called");
-  HIP_TRY(hipSetDevice(b->eng->device));
-  hipStream_t st = b->eng->stream;
-  if (observed) HIP_TRY(b->d_null_obs.upload(observed, (size_t)b->null_npairs, st));
-  HIP_TRY(hipEventRecord(b->null_evs[2], st));
-  if (int rc = launch_null_stats(b, observed ? b->d_null_obs.p : nullptr)) return rc;
-  HIP_TRY(hipEventRecord(b->null_evs[3], st));
-  HIP_TRY(hipMemcpyAsync(out, b->d_null_stats.p, sizeof(bialign_null_stats) * b->null_npairs, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  float f = 0;
-  HIP_TRY(hipEventElapsedTime(&f, b->null_evs[2], b->null_evs[3]));
-  b->stats_ms = f;
-  return BIALIGN_OK;
-}
-
-int bialign_batch_get_null_info(const bialign_batch* b, bialign_null_info* info) {
-  if (!b || !info) return fail(BIALIGN_E_INVALID, "NULL argument");
-  if (!b->null_R) return fail(BIALIGN_E_INVALID, "not a null batch (bialign_batch_create_null)");
-  if (int rc = bialign_batch_wait(const_cast<bialign_batch*>(b))) return rc;
-  info->shuffle_ms = b->shuffle_ms;
-  info->stats_ms = b->stats_ms;
-  info->replica_bytes = (int64_t)(b->d_seq_b.n + b->d_cls_b.n + (b->feat ? b->d_feat_b.n * sizeof(double) : 0) +
-                                  b->d_null_perm.n * sizeof(uint16_t));
-  return BIALIGN_OK;
-}
-
-int bialign_batch_set_null_model(bialign_batch* b, int32_t model) {
-  if (!b) return fail(BIALIGN_E_INVALID, "NULL argument");
-  if (!b->null_R) return fail(BIALIGN_E_INVALID, "not a null batch (bialign_batch_create_null)");
-  if (model != BIALIGN_NULL_MONO && model != BIALIGN_NULL_DINUCLEOTIDE)
-    return fail(BIALIGN_E_INVALID, "unknown null model %d (BIALIGN_NULL_MONO, BIALIGN_NULL_DINUCLEOTIDE)", model);
-  if (model == BIALIGN_NULL_DINUCLEOTIDE) {
-    if (b->dense1)
-      return fail(BIALIGN_E_UNSUPPORTED, "the dinucleotide model shuffles B's sequence letters: with mu1 in DENSE form B has none");
-    if (b->null_max_m > BIALIGN_NULL_DINUCLEOTIDE_MAX_LEN)  // (bialign_null.hpp checks the bound against its LDS layout)
-      return fail(BIALIGN_E_UNSUPPORTED, "the dinucleotide model keeps a molecule's edge list in LDS: longest B molecule %d exceeds %d",
-                  b->null_max_m, BIALIGN_NULL_DINUCLEOTIDE_MAX_LEN);
-  }
-  if (int rc = bialign_batch_wait(b)) return rc;
-  b->null_model = model;
-  return BIALIGN_OK;
-}
-
-int bialign_batch_get_null_model(const bialign_batch* b, int32_t* model) {
-  if (!b || !model) return fail(BIALIGN_E_INVALID, "NULL argument");
-  if (!b->null_R) return fail(BIALIGN_E_INVALID, "not a null batch (bialign_batch_create_null)");
-  *model = b->null_model;
-  return BIALIGN_OK;
-}
-
-// What the three dumps below share once their own arguments are checked: the replica is in range, the batch idle and
-// uploaded, and virtual pair *v = pair * R + replica shuffled anew on the engine's stream.
-static int null_dump_begin(bialign_batch* b, int32_t pair, int32_t replica, int* v) {
-  if (pair < 0 || pair >= b->null_npairs) return fail(BIALIGN_E_INVALID, "pair %d out of range", pair);
-  if (replica < 0 || replica >= b->null_R) return fail(BIALIGN_E_INVALID, "replica %d out of range", replica);
-  if (int rc = bialign_batch_wait(b)) return rc;
-  HIP_TRY(hipSetDevice(b->eng->device));
-  HIP_TRY(hipStreamWaitEvent(b->eng->stream, b->uploaded, 0));
-  *v = pair * b->null_R + replica;
-  return launch_shuffle_null(b, *v, 1);
-}
-
-int bialign_batch_dump_null_codes(bialign_batch* b, int32_t pair, int32_t replica, uint8_t* seq, uint8_t* cls) {
-  if (!b || !seq || !cls) return fail(BIALIGN_E_INVALID, "NULL argument");
-  if (!b->null_R) return fail(BIALIGN_E_INVALID, "not a null batch (bialign_batch_create_null)");
-  int v;
-  if (int rc = null_dump_begin(b, pair, replica, &v)) return rc;
-  hipStream_t st = b->eng->stream;
-  const PairDesc& d = b->pairs[v];
-  HIP_TRY(hipMemcpyAsync(seq, b->d_seq_b.p + d.seq_b, (size_t)d.m, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(cls, b->d_cls_b.p + d.seq_b, (size_t)d.m, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return BIALIGN_OK;
-}
-
-int bialign_batch_dump_null_features(bialign_batch* b, int32_t pair, int32_t replica, double* up, double* down, double* unp) {
-  if (!b || !up || !down || !unp) return fail(BIALIGN_E_INVALID, "NULL argument");
-  if (!b->null_R || !b->feat) return fail(BIALIGN_E_INVALID, "not a FEATURE-form null batch (bialign_batch_create_null_features)");
-  int v;
-  if (int rc = null_dump_begin(b, pair, replica, &v)) return rc;
-  hipStream_t st = b->eng->stream;
-  const PairDesc& d = b->pairs[v];
-  double* const out[3] = {up, down, unp};
-  for (int f = 0; f < 3; ++f)
-    HIP_TRY(hipMemcpyAsync(out[f], b->d_feat_b.p + (size_t)f * b->feat_tot_b + d.seq_b, (size_t)d.m * sizeof(double),
-                           hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return BIALIGN_OK;
-}
-
-int bialign_batch_dump_null_tables(bialign_batch* b, int32_t pair, int32_t replica, int32_t* mu1_out, int32_t* mu2_out) {
-  if (!b) return fail(BIALIGN_E_INVALID, "NULL argument");
-  if (!b->null_R || !b->null_dense) return fail(BIALIGN_E_INVALID, "not a DENSE-form null batch (bialign_batch_create_null_dense)");
-  if (mu1_out && !b->dense1) return fail(BIALIGN_E_INVALID, "mu1_out given, but mu1 of this batch is in LOOKUP form");
-  if (mu2_out && !b->dense) return fail(BIALIGN_E_INVALID, "mu2_out given, but mu2 of this batch is in LOOKUP form");
-  // the replica's permutation, then its tables in their place in the chunk buffer (which may hold another chunk's by now;
-  // results of a run live elsewhere)
-  int v;
-  if (int rc = null_dump_begin(b, pair, replica, &v)) return rc;
-  hipStream_t st = b->eng->stream;
-  const int pos = (int)(std::find(b->order.begin(), b->order.end(), v) - b->order.begin());
-  if (int rc = launch_permute_tables(b, pos, 1)) return rc;
-  const PairDesc& d = b->pairs[v];
-  const size_t nm = (size_t)d.n * d.m;
-  if (mu2_out) HIP_TRY(hipMemcpyAsync(mu2_out, b->d_tab.p + d.tab_off, nm * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  if (mu1_out)
-    HIP_TRY(hipMemcpyAsync(mu1_out, b->d_tab.p + d.tab_off + (b->dense ? nm : 0), nm * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  info->build_ms = b->clock.ms(Stage::Tables);
   return BIALIGN_OK;
 }
 

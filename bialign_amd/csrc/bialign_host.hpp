@@ -82,6 +82,41 @@ struct bialign_engine {
   DevBuf<int32_t> tab_cache;     // FEATURE-form batches: the per-chunk mu2 table buffer of the last one, kept likewise
 };
 
+// Every HIP event that times a batch, and the time they gave each stage (fill_ms is the sweeps' alone).  A run marks points
+// on the stream as it enqueues; a mark may end a stage, which then began at the mark before it, so adjacent stages share a
+// mark (a chunk's fill end is its traceback start).  finish() waits for the last mark, whichever stage it ends, and adds up
+// every stage.  Events are created as marks need them and kept for the next run, which may need fewer (a re-planned batch).
+enum class Stage { Shuffle, Tables, Fill, Traceback, Hits, Stats, None };
+struct StageClock {
+  std::vector<hipEvent_t> pool;
+  std::vector<Stage> ends;  // the marks of the pending / last run: pool[0 .. ends.size()), and the stage each ends
+  double total[(int)Stage::None] = {};
+  ~StageClock() { for (hipEvent_t e : pool) (void)hipEventDestroy(e); }
+  void reset() { ends.clear(), std::fill(std::begin(total), std::end(total), 0.0); }
+  hipError_t mark(hipStream_t st, Stage stage_ended = Stage::None) {
+    if (ends.size() == pool.size()) {
+      hipEvent_t e = nullptr;
+      if (hipError_t err = hipEventCreate(&e)) return err;
+      pool.push_back(e);
+    }
+    ends.push_back(stage_ended);
+    return hipEventRecord(pool[ends.size() - 1], st);
+  }
+  hipError_t finish() {
+    std::fill(std::begin(total), std::end(total), 0.0);
+    if (!ends.empty())
+      if (hipError_t err = hipEventSynchronize(pool[ends.size() - 1])) return err;
+    for (size_t k = 1; k < ends.size(); ++k) {
+      if (ends[k] == Stage::None) continue;
+      float f = 0;
+      if (hipError_t err = hipEventElapsedTime(&f, pool[k - 1], pool[k])) return err;
+      total[(int)ends[k]] += f;
+    }
+    return hipSuccess;
+  }
+  double ms(Stage stage) const { return total[(int)stage]; }
+};
+
 struct bialign_batch : bialign::BatchPlan {  // the plan (bialign_plan.hpp), and what lives on the device
   bialign_engine* eng = nullptr;
   DevBuf<PairDesc> d_pairs;
@@ -104,75 +139,64 @@ struct bialign_batch : bialign::BatchPlan {  // the plan (bialign_plan.hpp), and
   bool used_pack = false;       // a fill launch of the pending / last run stored packed records (BatchPlan::pack)
   bool packed_layers = false;   // ... and so did the launch whose layers are in the buffer now
   DevBuf<uint8_t> d_seq_a, d_cls_a, d_seq_b, d_cls_b, d_trace;
-  DevBuf<int32_t> d_tab;  // dense forms: all pairs' n x m tables (per pair mu2's, then mu1's; PairDesc::tab_off)
+  DevBuf<TraceState> d_tstate;
+  // Score tables.  Dense forms: d_tab holds all pairs' n x m tables (per pair mu2's, then mu1's; PairDesc::tab_off).
   // FEATURE form of mu2 (bialign_batch_create_features, bialign_mu2_build.hpp): per-residue doubles in HBM, d_tab is
   // per-chunk scratch the builder kernel fills ahead of each chunk's sweep; PairDesc::tab_off is chunk-relative.
-  DevBuf<double> d_feat_a, d_feat_b;   // three planes each (up, down, unp), feat_tot_a / feat_tot_b doubles per plane
-  int64_t feat_tot_a = 0, feat_tot_b = 0;
-  DevBuf<int32_t> d_mu1;               // a dense mu1 next to feature mu2: its tables stay resident here, pair after pair,
-  DevBuf<int64_t> d_mu1_off;           // ... and the builder copies a chunk's behind the mu2 tables it writes
-  std::vector<hipEvent_t> build_evs;   // two per chunk, around the builder's launch
-  double build_ms = 0;                 // HIP-event time of the builder launches of the last run (not part of fill_ms)
-  int build_launches = 0;
+  struct Tables {
+    DevBuf<int32_t> d_tab;
+    DevBuf<double> d_feat_a, d_feat_b;  // three planes each (up, down, unp), feat_tot_a / feat_tot_b doubles per plane
+    int64_t feat_tot_a = 0, feat_tot_b = 0;
+    DevBuf<int32_t> d_mu1;      // a dense mu1 next to feature mu2: its tables stay resident here, pair after pair,
+    DevBuf<int64_t> d_mu1_off;  // ... and the builder copies a chunk's behind the mu2 tables it writes
+    int build_launches = 0;     // table builds (Stage::Tables) of the pending / last run
+  } tables;
   // Null batch (bialign_batch_create_null, bialign_null.hpp): d_seq_b / d_cls_b are the replica buffers the shuffle kernel
-  // fills ahead of a run's sweeps from the uploaded B codes kept in d_null_seq / d_null_cls (real pair p's at d_null_off[p]).
-  DevBuf<uint8_t> d_null_seq, d_null_cls;
-  DevBuf<int64_t> d_null_off;
-  // FEATURE-form null batch (bialign_batch_create_null_features): d_feat_b holds the replica planes (feat_tot_b = R * sum of
+  // fills ahead of a run's sweeps from the uploaded B codes kept in d_seq / d_cls (real pair p's at d_off[p]).
+  //   FEATURE form (bialign_batch_create_null_features): tables.d_feat_b holds the replica planes (feat_tot_b = R * sum of
   // len_b doubles per plane, indexed by the virtual pairs' seq_b like d_seq_b), shuffle_features_kernel fills them and
-  // d_seq_b from the uploaded B features kept here, three planes of d_null_seq.n doubles; d_cls_b stays zero.
-  DevBuf<double> d_null_feat;
-  // DENSE-form null batch (bialign_batch_create_null_dense): the real pairs' tables stay resident in d_null_tab (pair p's
-  // at d_null_tab_off[p]: mu2's, then mu1's), d_null_perm holds every replica's permutation (uint16, indexed by the virtual
-  // pairs' seq_b like d_seq_b; shuffle_index_kernel fills it), and d_tab is per-chunk scratch as in FEATURE form:
-  // permute_tables_kernel writes each chunk's tables there ahead of its sweep; tab_dwords, max_chunk_tab_dwords, build_evs,
-  // build_ms and build_launches serve it likewise.
-  DevBuf<int32_t> d_null_tab;
-  DevBuf<int64_t> d_null_tab_off;
-  DevBuf<uint16_t> d_null_perm;
-  DevBuf<int32_t> d_null_obs;               // observed scores of the last bialign_batch_get_null_stats
-  DevBuf<bialign_null_stats> d_null_stats;  // ... and its result
-  hipEvent_t null_evs[4] = {nullptr, nullptr, nullptr, nullptr};  // around the shuffle launch of a run, around the reduction
-  double shuffle_ms = 0, stats_ms = 0;      // HIP-event times (not part of fill_ms)
-  int32_t null_model = BIALIGN_NULL_MONO;   // bialign_batch_set_null_model: which permutation the shuffle kernels make
-  DevBuf<TraceState> d_tstate;
+  // d_seq_b from the uploaded B features kept in d_feat, three planes of d_seq.n doubles; d_cls_b stays zero.
+  //   DENSE form (bialign_batch_create_null_dense): the real pairs' tables stay resident in d_tab (pair p's at d_tab_off[p]:
+  // mu2's, then mu1's), d_perm holds every replica's permutation (uint16, indexed like d_seq_b; shuffle_index_kernel fills
+  // it), and tables.d_tab is per-chunk scratch as in FEATURE form, with the same plan fields, stage and launch count:
+  // permute_tables_kernel writes each chunk's tables there ahead of its sweep.  The rest of a null batch is BatchPlan::null_*.
+  struct Null {
+    DevBuf<uint8_t> d_seq, d_cls;
+    DevBuf<int64_t> d_off, d_tab_off;
+    DevBuf<double> d_feat;
+    DevBuf<int32_t> d_tab;
+    DevBuf<uint16_t> d_perm;
+    DevBuf<int32_t> d_obs;               // observed scores of the last bialign_batch_get_null_stats
+    DevBuf<bialign_null_stats> d_stats;  // ... and its result
+    StageClock stats_clock;              // ... and its time: the reduction runs outside a run, and leaves the run's marks alone
+    int32_t model = BIALIGN_NULL_MONO;   // bialign_batch_set_null_model: which permutation the shuffle kernels make
+  } null;
   // Hit search (bialign_batch_set_hits, bialign_hits.hpp): the spec (max_walks resolved) and the result buffers of the whole
-  // batch, reset ahead of every run.  hits_on false: a run touches none of this.
-  bool hits_on = false;
-  bialign_hit_spec hit_spec{};
-  DevBuf<int32_t> d_hit_profile, d_hit_head, d_hit_rec, d_hit_walks;  // HitArgs::profile, head, hits, walks
-  DevBuf<int64_t> d_hit_prof_off;
-  DevBuf<uint8_t> d_hit_trace;
-  std::vector<int64_t> hit_prof_off;  // [npairs + 1]
-  int hit_mask_words = 0;             // HitArgs::mask_words
-  int64_t hit_bytes = 0;
-  std::vector<hipEvent_t> hit_evs;    // two per chunk, around the search's launch
-  bool hits_pending = false;          // the pending run enqueued searches
-  bool hits_ran = false;              // the last completed run filled the result buffers
-  double search_ms = 0;
-  void release_hits() {
-    hits_on = hits_ran = false;
-    for (DevBuf<int32_t>* d : {&d_hit_profile, &d_hit_head, &d_hit_rec, &d_hit_walks}) d->release();
-    d_hit_prof_off.release();
-    d_hit_trace.release();
-    hit_bytes = 0;
-  }
+  // batch, reset ahead of every run.  on false: a run touches none of this.
+  struct Hits {
+    bool on = false;
+    bool pending = false, ran = false;  // the pending run enqueues searches; the last completed run filled the result buffers
+    bialign_hit_spec spec{};
+    DevBuf<int32_t> d_profile, d_head, d_rec, d_walks;  // HitArgs::profile, head, hits, walks
+    DevBuf<int64_t> d_prof_off;
+    DevBuf<uint8_t> d_trace;
+    std::vector<int64_t> prof_off;  // [npairs + 1]
+    int mask_words = 0;             // HitArgs::mask_words
+    int64_t bytes = 0;
+    void release() {
+      on = ran = false;
+      for (DevBuf<int32_t>* d : {&d_profile, &d_head, &d_rec, &d_walks}) d->release();
+      d_prof_off.release();
+      d_trace.release();
+      bytes = 0;
+    }
+  } hits;
+  StageClock clock;  // the stage times of the pending / last run (bialign_batch_wait copies fill and traceback into timing)
   bialign_timing timing{};
   bool ran = false, ran_trace = false;
   bool pending = false, pending_trace = false;  // an enqueued run not yet waited for
-  std::vector<hipEvent_t> evs;                  // three per chunk: before fill, after fill, after traceback
   hipEvent_t uploaded = nullptr;                // inputs are in HBM (recorded on the copy stream)
-  ~bialign_batch() {
-    for (hipEvent_t e : evs)
-      if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : build_evs)
-      if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : null_evs)
-      if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : hit_evs)
-      if (e) (void)hipEventDestroy(e);
-    if (uploaded) (void)hipEventDestroy(uploaded);
-  }
+  ~bialign_batch() { if (uploaded) (void)hipEventDestroy(uploaded); }
 
   DeviceBatch view() const {
     DeviceBatch v{};
@@ -188,7 +212,7 @@ struct bialign_batch : bialign::BatchPlan {  // the plan (bialign_plan.hpp), and
     v.trace_len = d_tlen.p;
     v.complete = d_complete.p;
     v.errflag = d_err.p;
-    v.dense_tab = (dense || dense1) ? d_tab.p : nullptr;
+    v.dense_tab = (dense || dense1) ? tables.d_tab.p : nullptr;
     v.dense_forms = (dense ? 1 : 0) | (dense1 ? 2 : 0);
     v.scratch = d_layers.p;  // a pair's scratch records follow its LEAN records in the same buffer
     // the wide-band affine sweep's ring follows the largest chunk's layers there (BatchPlan::ring_dwords; alloc_layers)
@@ -223,12 +247,17 @@ int xcu_serial_end(bialign_engine* e);
 int launch_build_mu2(bialign_batch* b, int first, int count);
 
 // Null batch (bialign_null.hip): write the replicas of virtual pairs first .. first + count into the replica buffers, and
-// reduce every real pair's replica scores (d_scores) into d_null_stats; both on the engine's stream.
+// reduce every real pair's replica scores (d_scores) into null.d_stats; both on the engine's stream.
 int launch_shuffle_null(bialign_batch* b, int first, int count);
 // DENSE-form null batch: permute the real tables' columns into the chunk's table buffer for virtual pairs
 // order[first .. first+count), on the engine's stream; launch_shuffle_null must have written their permutations.
 int launch_permute_tables(bialign_batch* b, int first, int count);
 int launch_null_stats(bialign_batch* b, const int32_t* d_observed);
+
+// Hit search (bialign_hits.hip): what a launch is given (search false: the profile only); its results' state ahead of a run
+struct HitArgs;
+HitArgs hit_args(const bialign_batch* b, bool search);
+int reset_hits(bialign_batch* b, hipStream_t st);
 
 // ---- launching: every kernel of the library starts through launch() or launch_team()
 // Dynamic LDS beyond 64 KiB has to be allowed per kernel, ahead of a launch or an occupancy query.

@@ -10,15 +10,15 @@ int launch_build_mu2(bialign_batch* b, int first, int count) {
   Mu2BuildArgs a{};
   a.pairs = b->d_pairs.p;
   a.order = b->d_order.p + first;
-  a.up_a = b->d_feat_a.p;
-  a.down_a = b->d_feat_a.p + b->feat_tot_a;
-  a.unp_a = b->d_feat_a.p + 2 * b->feat_tot_a;
-  a.up_b = b->d_feat_b.p;
-  a.down_b = b->d_feat_b.p + b->feat_tot_b;
-  a.unp_b = b->d_feat_b.p + 2 * b->feat_tot_b;
-  a.tab = b->d_tab.p;
-  a.mu1_src = b->dense1 ? b->d_mu1.p : nullptr;
-  a.mu1_off = b->dense1 ? b->d_mu1_off.p : nullptr;
+  a.up_a = b->tables.d_feat_a.p;
+  a.down_a = b->tables.d_feat_a.p + b->tables.feat_tot_a;
+  a.unp_a = b->tables.d_feat_a.p + 2 * b->tables.feat_tot_a;
+  a.up_b = b->tables.d_feat_b.p;
+  a.down_b = b->tables.d_feat_b.p + b->tables.feat_tot_b;
+  a.unp_b = b->tables.d_feat_b.p + 2 * b->tables.feat_tot_b;
+  a.tab = b->tables.d_tab.p;
+  a.mu1_src = b->dense1 ? b->tables.d_mu1.p : nullptr;
+  a.mu1_off = b->dense1 ? b->tables.d_mu1_off.p : nullptr;
   a.sw = b->feat_sw;
   int64_t groups = 1;  // workgroups per pair: one per MU2_WAVES tiles of the launch's largest table
   for (int t = first; t < first + count; ++t) {
