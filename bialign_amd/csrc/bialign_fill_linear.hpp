@@ -159,6 +159,18 @@ __global__ void __launch_bounds__(64 * TW) fill_linear_kernel(const DeviceBatch 
   int mu2w[W];
 #pragma unroll
   for (int bb = 0; bb < W; ++bb) mu2w[bb] = 0;
+  // A lane starts at column -(2 il + aa) and the feed hands it one new value a step, mu2(k, jj + S): its first is column
+  // S - 2 il - aa, so the first row's lanes with aa < S - 3 never get columns 1 .. S - 3 - aa (max_shift 4 and 5 only).  A
+  // sweep that begins at strip 0 has row 0 there; a wave whose first strip is a later one (teams, strip re-sweeps) reads
+  // them here: the window as the step before its first would have left it.
+  if constexpr (DENSE && S >= 4 && (RESW || XCU || TW > 1)) {
+    const int k0 = i + aa - S;
+#pragma unroll
+    for (int bb = 0; bb < W; ++bb) {
+      const int l0 = jj - 1 + bb - S;
+      if (k0 >= 1 && k0 <= n && l0 >= 1 && l0 <= m) mu2w[bb] = mu2tab[(int64_t)(k0 - 1) * m + (l0 - 1)];
+    }
+  }
   auto prefetch_block = [&](int h0, int half, int jj0) __attribute__((always_inline)) {
     wait_partner(h0 + GF::BLK - 1);
     GF::issue(lay, h0 + Qbase * P, blk_q, blk_rem, P, T, w, GOFF, rec_last, L, ring_lds + half * GF::SLOTS * 16);
