@@ -87,7 +87,7 @@ class NullInfo(ctypes.Structure):
 class HitSpec(ctypes.Structure):
     """bialign_hit_spec: the hit search of a FIT batch."""
     _fields_ = [("max_hits", ctypes.c_int32), ("max_walks", ctypes.c_int32), ("min_score", ctypes.c_int32),
-                ("reserved", ctypes.c_int32)]
+                ("flags", ctypes.c_int32)]
 
 
 class HitInfo(ctypes.Structure):
@@ -97,6 +97,7 @@ class HitInfo(ctypes.Structure):
 HITS_NOT_SEARCHED, HITS_EXHAUSTED, HITS_MAX_HITS, HITS_MAX_WALKS = 0, 1, 2, 3  # BIALIGN_HITS_*
 HIT_STATUS = ("not_searched", "exhausted", "max_hits", "max_walks")
 MAX_HITS = 256
+HITS_PEAKS = 1  # BIALIGN_HITS_PEAKS
 
 
 class BatchInfo(ctypes.Structure):
@@ -143,6 +144,8 @@ SYMBOLS = [
     ("bialign_batch_get_local_spans", ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p, c_i32p]),
     ("bialign_batch_get_overlap_spans", ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p, c_i32p]),
     ("bialign_batch_set_hits", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HitSpec)]),
+    ("bialign_batch_set_hit_thresholds", ctypes.c_int, [ctypes.c_void_p, c_i32p, ctypes.c_int32]),
+    ("bialign_batch_get_hit_thresholds", ctypes.c_int, [ctypes.c_void_p, c_i32p]),
     ("bialign_batch_get_hit_profile", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_i32p]),
     ("bialign_batch_get_hits", ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_u8p, c_i64p]),
     ("bialign_batch_get_hit_walks", ctypes.c_int, [ctypes.c_void_p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p]),

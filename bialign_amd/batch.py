@@ -78,8 +78,9 @@ def make_batch(pairs, params, engine=None, hbm_budget_bytes=0, recurrence=0, mu2
                score_only=False, lean_trace=False, mu1_dense=None, level_trace=False, null_dense=None, fit=False,
                local=False, overlap=False, hits=None):
     """``fit``: fit alignments, A inside a longer B with B's end gaps free (engine.Batch).
-    ``hits``: ``(max_hits, min_score)`` or ``(max_hits, min_score, max_walks)``, a shorthand for ``Batch.set_hits`` on a
-    ``fit`` batch in full storage: every run also searches each pair for its disjoint placements of A in B.
+    ``hits``: ``(max_hits, min_score)`` or ``(max_hits, min_score, max_walks)``, or a dict of ``Batch.set_hits``'s keywords
+    (``peaks``, ``min_scores``, ``min_permille`` among them), a shorthand for ``Batch.set_hits`` on a ``fit`` batch in full
+    storage: every run also searches each pair for its disjoint placements of A in B.
     ``local``: local alignments, the best-scoring parts of A and B with the ends of both free (engine.Batch).
     ``overlap``: overlap alignments, the global alignment with the end gaps of both molecules free (engine.Batch).
     ``mu1_dense`` / ``mu2_dense``: optional lists of one (len A, len B) int table per pair (engine.Batch).
@@ -88,7 +89,8 @@ def make_batch(pairs, params, engine=None, hbm_budget_bytes=0, recurrence=0, mu2
     (``significance.null_dense_batch``): score-only, no ``lean_trace`` / ``level_trace``."""
     _check_storage(score_only, lean_trace, level_trace)
     if hits is not None:
-        hits = check_hits_arg(hits, fit, score_only, null_dense)
+        pairs = pairs if isinstance(pairs, list) else list(pairs)
+        hits = check_hits_arg(hits, fit, score_only, null_dense, len(pairs))
     if null_dense is not None:
         from .significance import check_dense_args
         if lean_trace or level_trace:
@@ -102,7 +104,9 @@ def make_batch(pairs, params, engine=None, hbm_budget_bytes=0, recurrence=0, mu2
               params["max_shift"], hbm_budget_bytes=hbm_budget_bytes, recurrence=recurrence,
               mu2_dense=mu2_dense, score_only=score_only, lean_trace=lean_trace, mu1_dense=mu1_dense,
               level_trace=level_trace, fit=fit, local=local, overlap=overlap, **({} if null_dense is None else dict(null_dense=null_dense)))
-    if hits is not None:
+    if isinstance(hits, dict):
+        b.set_hits(**hits)
+    elif hits is not None:
         b.set_hits(*hits)
     return b
 
@@ -122,12 +126,51 @@ def check_hit_spec(max_hits, min_score, max_walks=0):
     return max_hits, min_score, max_walks
 
 
-def check_hits_arg(hits, fit, score_only, null=None):
-    """``hits=`` of ``make_batch`` -> ``(max_hits, min_score, max_walks)``: the search needs a fit batch in full storage."""
+HIT_KEYWORDS = ("max_hits", "min_score", "max_walks", "peaks", "min_scores", "min_permille")
+
+
+def check_hit_rules(peaks=False, min_scores=None, min_permille=0, npairs=None):
+    """The peak rule and the thresholds of a hit search as include/bialign.h states them -> ``(peaks, min_scores,
+    min_permille)``, ``min_scores`` an int32 array or None; ValueError before the library is called.  ``npairs`` given:
+    ``min_scores`` must have that many entries."""
+    if not isinstance(peaks, (bool, np.bool_)):
+        raise ValueError(f"peaks must be a bool, got {peaks!r}")
+    if isinstance(min_permille, (bool, np.bool_)) or not isinstance(min_permille, (int, np.integer)):
+        raise ValueError(f"min_permille must be an int in 0..1000, got {min_permille!r}")
+    if not 0 <= min_permille <= 1000:
+        raise ValueError(f"min_permille must be an int in 0..1000, got {min_permille}")
+    if min_scores is not None:
+        try:
+            arr = np.asarray(list(min_scores))
+        except TypeError:
+            raise ValueError("min_scores must be one int >= 1 per pair") from None
+        if arr.ndim != 1 or (arr.size and not np.issubdtype(arr.dtype, np.integer)) or arr.dtype == np.bool_:
+            raise ValueError("min_scores must be one int >= 1 per pair")
+        if npairs is not None and arr.size != npairs:
+            raise ValueError(f"min_scores must be one int >= 1 per pair: {arr.size} entries for {npairs} pairs")
+        if arr.size and (arr.min() < 1 or arr.max() > 0x7fffffff):
+            raise ValueError(f"min_scores must be one int >= 1 per pair (below 2^31), got {int(arr.min())}..{int(arr.max())}")
+        min_scores = np.ascontiguousarray(arr, dtype=np.int32)
+    return bool(peaks), min_scores, int(min_permille)
+
+
+def check_hits_arg(hits, fit, score_only, null=None, npairs=None):
+    """``hits=`` of ``make_batch`` -> ``(max_hits, min_score, max_walks)``, or for a dict of ``Batch.set_hits``'s keywords
+    the checked dict: the search needs a fit batch in full storage."""
     if not fit:
         raise ValueError("hits= needs fit=True: the hit search walks the placements of A in B of a fit batch")
     if score_only or null is not None:
         raise ValueError("hits= excludes score_only and null batches: the hit search walks through the full layers")
+    if isinstance(hits, dict):
+        unknown = sorted(set(hits) - set(HIT_KEYWORDS))
+        if unknown or "max_hits" not in hits or "min_score" not in hits:
+            raise ValueError(f"hits as a dict takes max_hits, min_score and any of {', '.join(HIT_KEYWORDS[2:])}"
+                             + (f"; not {', '.join(map(str, unknown))}" if unknown else ""))
+        max_hits, min_score, max_walks = check_hit_spec(hits["max_hits"], hits["min_score"], hits.get("max_walks", 0))
+        peaks, min_scores, min_permille = check_hit_rules(hits.get("peaks", False), hits.get("min_scores"),
+                                                            hits.get("min_permille", 0), npairs)
+        return dict(max_hits=max_hits, min_score=min_score, max_walks=max_walks, peaks=peaks, min_scores=min_scores,
+                    min_permille=min_permille)
     try:
         hits = tuple(hits)
     except TypeError:

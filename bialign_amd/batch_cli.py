@@ -36,7 +36,9 @@ fourth and fifth column under ``--score_only``, ``--zscore`` in the same mode.
 ``--fit --hits K --hit_min_score X`` also searches every pair for up to K disjoint placements of A in B that score at
 least X (include/bialign.h, "Hit search").  Behind each pair's block follow ``HITS: <n> (<status>)`` and one line per hit
 in the form of ``--fit``'s span line behind a hit index, ``hit <h>\tB span\t <start_b+1>..<end_b>\t<score>``; hit 0 is the
-pair's own alignment.  Not without ``--fit``, not with ``--score_only`` or ``--zscore``.
+pair's own alignment.  Not without ``--fit``, not with ``--score_only`` or ``--zscore``.  ``--hit_peaks`` takes only the
+peaks of a pair's end-score profile as candidates, which finds the farther copies of A within the default walk budget;
+``--hit_min_permille N`` also asks of a placement N thousandths of the pair's own fit score.  Both need ``--hits``.
 """
 import argparse
 import sys
@@ -95,6 +97,11 @@ def build_parser():
                         "molecule B and print one 'hit' line each behind the pair's block. Not with --score_only or --zscore.")
     p.add_argument("--hit_min_score", type=int, default=None, metavar="X",
                    help="The least score (>= 1) of a placement that --hits reports; required with --hits.")
+    p.add_argument("--hit_peaks", action="store_true",
+                   help="With --hits: only the peaks of a pair's end-score profile are candidate ends (the ends just "
+                        "behind a reported placement are not tried one by one).")
+    p.add_argument("--hit_min_permille", type=int, default=None, metavar="N",
+                   help="With --hits: a placement must also score at least N thousandths (0..1000) of the pair's fit score.")
     p.add_argument("--zscore_seed", type=int, default=0, metavar="N",
                    help="Seed of the shuffles (default 0); shuffle r of a pair is a function of the seed, r and the "
                         "pair's position among the pairs its process aligns.")
@@ -119,7 +126,10 @@ def hit_line(h, start_b, end_b, score):
 
 
 def check_hit_options(parser, args):
-    """``--hits`` / ``--hit_min_score`` -> ``hits=`` of ``make_batch`` or None; a parser error where they do not apply."""
+    """``--hits`` / ``--hit_min_score`` and the two options that refine them -> ``hits=`` of ``make_batch`` (today's tuple, or a dict once one of
+    ``--hit_peaks`` / ``--hit_min_permille`` is given) or None; a parser error where they do not apply."""
+    if not args.hits and (args.hit_peaks or args.hit_min_permille is not None):
+        parser.error("--hit_peaks and --hit_min_permille need --hits")
     if not args.hits and args.hit_min_score is None:
         return None
     if not args.hits or args.hit_min_score is None:
@@ -128,9 +138,13 @@ def check_hit_options(parser, args):
         parser.error("--hits needs --fit")
     if args.score_only or args.zscore:
         parser.error("--hits excludes --score_only and --zscore")
-    from .batch import check_hit_spec
+    from .batch import check_hit_rules, check_hit_spec
     try:
-        return check_hit_spec(args.hits, args.hit_min_score)
+        spec = check_hit_spec(args.hits, args.hit_min_score)
+        if not args.hit_peaks and args.hit_min_permille is None:
+            return spec
+        peaks, _, permille = check_hit_rules(args.hit_peaks, None, args.hit_min_permille or 0)
+        return dict(max_hits=spec[0], min_score=spec[1], max_walks=spec[2], peaks=peaks, min_permille=permille)
     except ValueError as e:
         parser.error(str(e))
 
@@ -211,7 +225,7 @@ def _main(argv=None):
     if args.zscore_shuffle and not args.zscore:
         parser.error("--zscore_shuffle needs --zscore")
     params = {k: v for k, v in vars(args).items()
-              if k not in ("pairs", "verbose", "score_only", "zscore", "zscore_seed", "zscore_shuffle", "fit", "local", "overlap", "hits", "hit_min_score")}
+              if k not in ("pairs", "verbose", "score_only", "zscore", "zscore_seed", "zscore_shuffle", "fit", "local", "overlap", "hits", "hit_min_score", "hit_peaks", "hit_min_permille")}
     if args.zscore:
         from .significance import check_null
         check_null((args.zscore, args.zscore_seed))

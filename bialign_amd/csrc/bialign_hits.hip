@@ -1,6 +1,6 @@
 // bialign_hits.hip -- the hit-search kernels of FIT batches (bialign_hits.hpp), instantiated as the generic tracebacks
 // are: max_shift 0..5, affine and one-layer, packed records (affine, max_shift 1..BIALIGN_MAX_SHIFT_PACKED), dense mu1;
-// and the search's C entry points (include/bialign.h).
+// each without and with the search's options (OPT); and the search's C entry points (include/bialign.h).
 #include "bialign_hits.hpp"
 
 namespace bialign {
@@ -11,7 +11,9 @@ template <int S, bool AFFINE, bool PACK, bool D1>
 int launch_one(const bialign_batch* b, const DeviceBatch& v, const HitArgs& h, int first, int count) {
   DeviceBatch w = v;
   w.order = v.order + first;
-  return launch(fit_hits_kernel<S, AFFINE, PACK, D1>, dim3(count), dim3(64), fit_hits_lds(h), b->eng->stream, w, h, count);
+  if (h.options())
+    return launch(fit_hits_kernel<S, AFFINE, PACK, D1, true>, dim3(count), dim3(64), fit_hits_lds(h), b->eng->stream, w, h, count);
+  return launch(fit_hits_kernel<S, AFFINE, PACK, D1, false>, dim3(count), dim3(64), fit_hits_lds(h), b->eng->stream, w, h, count);
 }
 
 template <int S>
@@ -45,6 +47,9 @@ HitArgs hit_args(const bialign_batch* b, bool search) {
   h.search = search ? 1 : 0;
   h.lds_inputs = (int32_t)((b->lds_trace + 15) & ~size_t(15));
   h.mask_words = b->hits.mask_words;
+  h.flags = b->hits.spec.flags;
+  h.min_permille = b->hits.min_permille;
+  h.min_scores = b->hits.d_min_scores.p;
   h.prof_off = b->hits.d_prof_off.p;
   h.profile = b->hits.d_profile.p;
   h.head = b->hits.d_head.p;
@@ -92,7 +97,7 @@ int bialign_batch_set_hits(bialign_batch* b, const bialign_hit_spec* spec) {
   if (spec->min_score < 1) return fail(BIALIGN_E_INVALID, "min_score must be >= 1, got %d", spec->min_score);
   if (spec->max_walks != 0 && spec->max_walks < spec->max_hits)
     return fail(BIALIGN_E_INVALID, "max_walks must be 0 (4 * max_hits) or >= max_hits = %d, got %d", spec->max_hits, spec->max_walks);
-  if (spec->reserved != 0) return fail(BIALIGN_E_INVALID, "bialign_hit_spec.reserved must be 0");
+  if (spec->flags & ~BIALIGN_HITS_PEAKS) return fail(BIALIGN_E_INVALID, "bialign_hit_spec.flags: unknown bits 0x%x", spec->flags & ~BIALIGN_HITS_PEAKS);
   bialign_hit_spec sp = *spec;
   if (sp.max_walks == 0) sp.max_walks = 4 * sp.max_hits;
   int max_m = 0;
@@ -125,6 +130,51 @@ int bialign_batch_set_hits(bialign_batch* b, const bialign_hit_spec* spec) {
   }
   b->hits.bytes = (int64_t)((prof + 4 * (size_t)b->npairs + recs + walks) * 4 + trace + (size_t)b->npairs * 8);
   b->hits.on = true;
+  return BIALIGN_OK;
+}
+
+int bialign_batch_set_hit_thresholds(bialign_batch* b, const int32_t* min_score, int32_t min_permille) {
+  if (!b) return fail(BIALIGN_E_INVALID, "NULL batch");
+  // (hits.on is host state that only bialign_batch_set_hits changes, and that call ends a pending run itself)
+  if (!b->hits.on) return fail(BIALIGN_E_INVALID, "no hit search is set on this batch (bialign_batch_set_hits)");
+  if (min_permille < 0 || min_permille > 1000) return fail(BIALIGN_E_INVALID, "min_permille must be 0..1000, got %d", min_permille);
+  if (min_score)
+    for (int p = 0; p < b->npairs; ++p)
+      if (min_score[p] < 1) return fail(BIALIGN_E_INVALID, "min_score[%d] must be >= 1, got %d", p, min_score[p]);
+  if (int rc = bialign_batch_wait(b)) return rc;  // the first device call: a pending run still reads the array released below
+  HIP_TRY(hipSetDevice(b->eng->device));
+  const int64_t had = (int64_t)b->hits.d_min_scores.n * 4;
+  if (min_score) {
+    DevBuf<int32_t> d;
+    hipStream_t st = b->eng->stream;
+    hipError_t err = d.upload(min_score, (size_t)b->npairs, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (err == hipSuccess && getenv("BIALIGN_TEST_FAIL_HITS_ALLOC")) err = hipErrorOutOfMemory;  // tests: pretend an allocation failed
+    if (err != hipSuccess) {  // the thresholds stay what they were
+      (void)hipGetLastError();
+      return fail(BIALIGN_E_NOMEM, "hit thresholds: allocating %zu bytes failed: %s", (size_t)b->npairs * 4, hipGetErrorString(err));
+    }
+    b->hits.d_min_scores.swap(d);
+  } else {
+    b->hits.d_min_scores.release();
+  }
+  b->hits.bytes += (int64_t)b->hits.d_min_scores.n * 4 - had;
+  b->hits.min_permille = min_permille;
+  return BIALIGN_OK;
+}
+
+int bialign_batch_get_hit_thresholds(const bialign_batch* b, int32_t* out) {
+  if (!b || !out) return fail(BIALIGN_E_INVALID, "NULL argument");
+  if (int rc = bialign_batch_wait(const_cast<bialign_batch*>(b))) return rc;
+  if (!b->hits.on) return fail(BIALIGN_E_INVALID, "no hit search is set on this batch (bialign_batch_set_hits)");
+  std::fill(out, out + b->npairs, -1);
+  if (!b->ran || !b->hits.ran) return BIALIGN_OK;  // no run yet
+  HIP_TRY(hipSetDevice(b->eng->device));
+  std::vector<int32_t> head(4 * (size_t)b->npairs);
+  HIP_TRY(hipMemcpy(head.data(), b->hits.d_head.p, sizeof(int32_t) * head.size(), hipMemcpyDeviceToHost));
+  for (int p = 0; p < b->npairs; ++p)  // NOT_SEARCHED: a fill-only run, which forms no threshold.  A search without
+    if (head[4 * (size_t)p + 2] != BIALIGN_HITS_NOT_SEARCHED)  // options leaves the word 0 (a T_p is >= 1): min_score
+      out[p] = head[4 * (size_t)p + 3] ? head[4 * (size_t)p + 3] : b->hits.spec.min_score;
   return BIALIGN_OK;
 }
 

@@ -183,9 +183,13 @@ struct bialign_batch : bialign::BatchPlan {  // the plan (bialign_plan.hpp), and
     std::vector<int64_t> prof_off;  // [npairs + 1]
     int mask_words = 0;             // HitArgs::mask_words
     int64_t bytes = 0;
+    // bialign_batch_set_hit_thresholds: the per-pair array (by pair id; empty: spec.min_score) and the permille
+    DevBuf<int32_t> d_min_scores;
+    int32_t min_permille = 0;
     void release() {
       on = ran = false;
-      for (DevBuf<int32_t>* d : {&d_profile, &d_head, &d_rec, &d_walks}) d->release();
+      min_permille = 0;
+      for (DevBuf<int32_t>* d : {&d_profile, &d_head, &d_rec, &d_walks, &d_min_scores}) d->release();
       d_prof_off.release();
       d_trace.release();
       bytes = 0;

@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import lib, check
-from .batch import check_hit_spec
+from .batch import check_hit_rules, check_hit_spec
 from .significance import check_dense_tables, check_null
 
 STATES = [(0, 1, 0, 1), (0, 1, 1, 0), (0, 1, 1, 1), (1, 0, 0, 1), (1, 0, 1, 0),
@@ -106,7 +106,7 @@ class Batch:
     global score of A against any substring of B, ``traces()`` that alignment, ``fit_spans()`` the substring.  Bands
     up to ``_lib.MAX_SHIFT_TILED``, full storage or ``score_only`` (and so null batches: the replicas are scored in
     the same mode); not with ``lean_trace`` / ``level_trace``.  In full storage ``set_hits()`` adds a search for every
-    placement of A in B: ``fit_hits()``, ``hit_profile()``, ``fit_hit_walks()``.
+    placement of A in B: ``fit_hits()``, ``hit_profile()``, ``fit_hit_walks()``, ``hit_thresholds()``.
     ``local``: local alignments (BIALIGN_BATCH_LOCAL): the best-scoring parts of A and B, the ends of both free.
     ``scores()`` is the best global score of any substring of A against any substring of B (>= 0), ``traces()`` that
     alignment, ``local_spans()`` the two substrings.  Bands up to ``_lib.MAX_SHIFT_TILED``, ``gap_opening_cost <= 0``
@@ -415,10 +415,14 @@ class Batch:
         check(lib.bialign_batch_get_fit_spans(self._h, _ptr(start, ctypes.c_int32), _ptr(end, ctypes.c_int32)))
         return start, end
 
-    def set_hits(self, max_hits, min_score=None, max_walks=0):
+    def set_hits(self, max_hits, min_score=None, max_walks=0, peaks=False, min_scores=None, min_permille=0):
         """Fit batch, full storage: search every later run for up to ``max_hits`` disjoint placements of A in B that
         score at least ``min_score`` (bialign_batch_set_hits; the model is stated in include/bialign.h).  ``max_walks``
-        bounds the walks a pair may cost, 0 means ``4 * max_hits``.  ``set_hits(None)`` removes the search again."""
+        bounds the walks a pair may cost, 0 means ``4 * max_hits``.  ``peaks``: only the peaks of a pair's end-score
+        profile are candidates (BIALIGN_HITS_PEAKS), which reaches the farther copies without a discarded walk from every
+        end behind a hit.  ``min_scores`` (one int >= 1 per pair) and ``min_permille`` (0..1000, of the pair's fit score)
+        give every pair its own threshold (bialign_batch_set_hit_thresholds; ``hit_thresholds()`` reports them).
+        ``set_hits(None)`` removes the search again."""
         if max_hits is None:
             check(lib.bialign_batch_set_hits(self._h, None))
             self.hit_spec = None
@@ -426,10 +430,22 @@ class Batch:
         if min_score is None:
             raise ValueError("set_hits needs min_score (set_hits(None) removes the search)")
         max_hits, min_score, max_walks = check_hit_spec(max_hits, min_score, max_walks)
-        spec = _lib.HitSpec(max_hits, max_walks, min_score, 0)
+        peaks, min_scores, min_permille = check_hit_rules(peaks, min_scores, min_permille, self.npairs)
+        spec = _lib.HitSpec(max_hits, max_walks, min_score, _lib.HITS_PEAKS if peaks else 0)
         self.hit_spec = None
         check(lib.bialign_batch_set_hits(self._h, ctypes.byref(spec)))
         self.hit_spec = (max_hits, max_walks or 4 * max_hits, min_score)
+        if min_scores is not None or min_permille:
+            check(lib.bialign_batch_set_hit_thresholds(
+                self._h, None if min_scores is None else _ptr(min_scores, ctypes.c_int32), min_permille))
+
+    def hit_thresholds(self):
+        """int32 ``T[p]``: the least score a candidate end of pair p had to reach in the last run (include/bialign.h,
+        "Thresholds"); -1 before a run and after a fill-only run."""
+        self._need_hits()
+        out = np.empty(self.npairs, dtype=np.int32)
+        check(lib.bialign_batch_get_hit_thresholds(self._h, _ptr(out, ctypes.c_int32)))
+        return out
 
     def _need_hits(self):
         if self.hit_spec is None:
@@ -469,12 +485,12 @@ class Batch:
                 for p in range(self.npairs)]
 
     def hit_info(self):
-        """bialign_batch_get_hit_info: the spec, the result buffers' bytes, the search kernels' time of the last run."""
+        """bialign_batch_get_hit_info: the spec with its flags, the result buffers' bytes, the search kernels' time of the last run."""
         self._need_hits()
         hi = _lib.HitInfo()
         check(lib.bialign_batch_get_hit_info(self._h, ctypes.byref(hi)))
         return dict(max_hits=hi.spec.max_hits, max_walks=hi.spec.max_walks, min_score=hi.spec.min_score,
-                    buffer_bytes=hi.buffer_bytes, search_ms=hi.search_ms)
+                    flags=hi.spec.flags, peaks=bool(hi.spec.flags & _lib.HITS_PEAKS), buffer_bytes=hi.buffer_bytes, search_ms=hi.search_ms)
 
     def local_spans(self):
         """Local batch: ``(start_a, end_a, start_b, end_b)`` as int32 arrays -- pair p's alignment is that of

@@ -289,6 +289,18 @@ def _with_model(batch, null_model):
     return batch
 
 
+def _null_moments(stats, p):
+    """Pair p of ``Batch.null_stats``'s exact integers -> (mean, std, defined): the sample standard deviation (ddof = 1,
+    nan where R is 1) and whether a z-score is defined (R > 1 and a variance above 0).  The variance's numerator
+    R * sumsq - sum^2 is formed in Python integers, so the same integers always give the same doubles."""
+    R, s1, s2 = int(stats["replicas"][p]), int(stats["sum"][p]), int(stats["sumsq"][p])
+    num = R * s2 - s1 * s1  # = R * (R - 1) * variance, exact
+    if num < 0:
+        raise ValueError(f"pair {p}: sums are inconsistent (R * sumsq < sum^2)")
+    std = (num / (R * (R - 1))) ** 0.5 if R > 1 else float("nan")
+    return s1 / R, std, R > 1 and num > 0
+
+
 def zscores_from_stats(score, stats):
     """Observed scores and the exact integer reductions of ``Batch.null_stats`` -> dict of arrays ``score``, ``mean``,
     ``std`` (sample standard deviation, ddof = 1), ``z`` (nan where std is 0 or R is 1), ``p_emp`` =
@@ -298,16 +310,56 @@ def zscores_from_stats(score, stats):
     n = len(score)
     mean, std, z = np.empty(n), np.empty(n), np.empty(n)
     for p in range(n):
-        R, s1, s2 = int(stats["replicas"][p]), int(stats["sum"][p]), int(stats["sumsq"][p])
-        mean[p] = s1 / R
-        num = R * s2 - s1 * s1  # = R * (R - 1) * variance, exact
-        if num < 0:
-            raise ValueError(f"pair {p}: sums are inconsistent (R * sumsq < sum^2)")
-        std[p] = (num / (R * (R - 1))) ** 0.5 if R > 1 else float("nan")
-        z[p] = (int(score[p]) - mean[p]) / std[p] if R > 1 and num > 0 else float("nan")
+        mean[p], std[p], defined = _null_moments(stats, p)
+        z[p] = (int(score[p]) - mean[p]) / std[p] if defined else float("nan")
     n_ge = np.asarray(stats["n_ge"], dtype=np.int64)
     reps = np.asarray(stats["replicas"], dtype=np.int64)
     return dict(score=score, mean=mean, std=std, z=z, p_emp=(n_ge + 1) / (reps + 1), n_ge=n_ge, replicas=reps)
+
+
+def hit_zscores(hits, stats):
+    """The hits of ``Batch.fit_hits()`` (per pair a list of ``(start_b, end_b, score, ...)``) and the exact integer
+    reductions ``null_stats()`` of a FIT null batch of the same pairs -> per pair a float array, per hit
+    ``z = (score - mean) / std`` in the arithmetic of ``zscores_from_stats`` (nan where std is 0 or R is 1).
+    What the null is: a replica's score is the best placement of A in a shuffled B, the maximum over every end.  That is
+    the null of hit 0, the pair's own fit score.  A hit beyond the first is not a maximum over all of B but is held to the
+    same null, so its z is conservative: it understates the hit's significance, never overstates it."""
+    if len(hits) != len(stats["replicas"]):
+        raise ValueError("hits and stats need one entry per pair")
+    out = []
+    for p, found in enumerate(hits):
+        mean, std, defined = _null_moments(stats, p)
+        out.append(np.array([(int(h[2]) - mean) / std if defined else float("nan") for h in found], dtype=np.float64))
+    return out
+
+
+def hit_significance(batch, pairs, params, replicas=100, seed=0, shuffle="mono", engine=None, hbm_budget_bytes=0):
+    """``hit_zscores`` for a hits batch that has run (``make_batch(pairs, params, fit=True, hits=...)``): makes the null
+    batch of ``pairs`` with ``fit=True``, runs it once, and reduces it once per hit rank with that rank's scores as
+    ``null_stats(observed=)``.  -> per pair a list with one dict per hit: ``score``, ``z``, ``mean``, ``std``, ``n_ge``,
+    ``replicas`` and ``p_emp = (n_ge + 1) / (R + 1)``.  The null is the best placement of A in a shuffled B, conservative
+    for hits beyond the first (``hit_zscores``).  The replicas are scored in the hits batch's recurrence (``batch.affine``)."""
+    from . import _lib
+    hits, _ = batch.fit_hits()
+    if len(hits) != len(pairs):
+        raise ValueError("pairs must be the pairs of the hits batch")
+    ranks = max((len(h) for h in hits), default=0)
+    nb = null_batch(pairs, params, replicas, seed=seed, engine=engine, hbm_budget_bytes=hbm_budget_bytes,
+                    recurrence=_lib.REC_AFFINE if batch.affine else _lib.REC_LINEAR, fit=True, shuffle=shuffle)
+
+    def per_rank(nb):
+        # (a pair without a hit of this rank is reduced against INT32_MAX and its n_ge dropped)
+        return [nb.null_stats(np.array([h[r][2] if r < len(h) else 2 ** 31 - 1 for h in hits], dtype=np.int32))
+                for r in range(max(ranks, 1))]
+    stats = _run_and_close(nb, per_rank)
+    z = hit_zscores(hits, stats[0])
+    out = []
+    for p, found in enumerate(hits):
+        mean, std, _ = _null_moments(stats[0], p)
+        R = int(stats[0]["replicas"][p])
+        out.append([dict(score=int(h[2]), z=float(z[p][r]), mean=mean, std=std, n_ge=int(stats[r]["n_ge"][p]), replicas=R,
+                         p_emp=(int(stats[r]["n_ge"][p]) + 1) / (R + 1)) for r, h in enumerate(found)])
+    return out
 
 
 def _run_and_close(batch, result):

@@ -494,13 +494,28 @@ int bialign_batch_get_overlap_spans(const bialign_batch* b, int32_t* start_a, in
  *        made.  (In this order: the walk that accepts hit max_hits as walk max_walks gives MAX_HITS.)
  *   Consequences.  Hits are disjoint in B.  Their scores do not increase in order of acceptance.  Hit 0 is the batch's own
  *     alignment, with the same span, score and trace bytes.
- *   Parameters.  min_score >= 1.  1 <= max_hits <= 256.  max_walks >= max_hits, and 0 means 4 * max_hits. */
+ *   Parameters.  min_score >= 1.  1 <= max_hits <= 256.  max_walks >= max_hits, and 0 means 4 * max_hits.
+ *   Peak candidates (flags bit BIALIGN_HITS_PEAKS).  The ends just behind an accepted hit's end each score only one gap
+ *     cost less, so they are the next-best candidates, and every one of them costs a discarded walk before a farther
+ *     copy's end is reached.  An end j is a peak of the profile E(0..m) when (j = 0 or E(j-1) < E(j)) and (j = m or
+ *     E(j+1) <= E(j)).  With the flag, every end that is not a peak is masked before the first round.  Steps 1-5 are
+ *     unchanged: the masks on acceptance, the log and the stop reasons all stay as they are.  Hit 0 is still the batch's
+ *     own alignment: the smallest j that attains the maximum has E(j-1) < E(j) (or j = 0) because it is the smallest, and
+ *     E(j+1) <= E(j) (or j = m) because E(j) is the maximum, so it is a peak.  The peaks are a property of the profile
+ *     only.  They do not depend on the mask's later state.  flags 0 is the search without the rule, bit for bit; any
+ *     other bit is BIALIGN_E_INVALID.
+ *   Thresholds (bialign_batch_set_hit_thresholds).  base_p = min_score[p] if the array is given, else spec.min_score.
+ *     Emax_p is the maximum of the pair's profile, which is its fit score.  T_p = max(base_p, Emax_p > 0 ?
+ *     ceil(min_permille * Emax_p / 1000) : 0), formed in 64 bits.  Candidates are the ends with E(j) >= T_p: T_p stands
+ *     where min_score stands in step 1.  Without thresholds T_p = spec.min_score. */
 typedef struct bialign_hit_spec {
   int32_t max_hits;
   int32_t max_walks;
   int32_t min_score;
-  int32_t reserved; /* 0 */
+  int32_t flags; /* BIALIGN_HITS_PEAKS or 0 (the former reserved word: same offset and size) */
 } bialign_hit_spec;
+
+#define BIALIGN_HITS_PEAKS 1u /* bialign_hit_spec.flags: only the profile's peaks are candidates */
 
 /* status of a pair's search */
 #define BIALIGN_HITS_NOT_SEARCHED 0 /* no run yet, or a BIALIGN_RUN_FILL_ONLY run */
@@ -525,6 +540,16 @@ typedef struct bialign_hit_info {
  * no launch, no event, no allocation.  With one, the results are reset ahead of every run, as the spans are; a
  * BIALIGN_RUN_FILL_ONLY run leaves the profile and status NOT_SEARCHED, with no hits and no walks. */
 int bialign_batch_set_hits(bialign_batch* b, const bialign_hit_spec* spec);
+/* Per-pair thresholds of the search ("Thresholds" above); after bialign_batch_set_hits, ahead of a run.  min_score is
+ * [npairs], indexed by pair id (not by launch slot), or NULL; min_permille is 0..1000.  The array is copied to HBM and its
+ * bytes count in bialign_hit_info.buffer_bytes.  A later bialign_batch_set_hits call, with a spec or with NULL, clears the
+ * thresholds; a later call of this function replaces them.  Refused before any device call, and the batch stays usable
+ * with the thresholds it had: no search set, an entry < 1 or a permille outside 0..1000: BIALIGN_E_INVALID; a failed
+ * allocation: BIALIGN_E_NOMEM. */
+int bialign_batch_set_hit_thresholds(bialign_batch* b, const int32_t* min_score /* [npairs] or NULL */, int32_t min_permille /* 0..1000 */);
+/* The T_p the last run used, with or without thresholds set; -1 for every pair after no run or after a
+ * BIALIGN_RUN_FILL_ONLY run.  No search set: BIALIGN_E_INVALID. */
+int bialign_batch_get_hit_thresholds(const bialign_batch* b, int32_t* out /* [npairs] */);
 /* Pair's profile E(0..m) of the last run.  No search set or no run since: BIALIGN_E_INVALID (so for the getters below). */
 int bialign_batch_get_hit_profile(const bialign_batch* b, int32_t pair, int32_t* out /* [m+1] */);
 /* The accepted hits, in order of acceptance.  nhits and status are [npairs]; start_b, end_b, score and trace_len are
